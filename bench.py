@@ -14,6 +14,8 @@ tile (36,864 columns) per rank instead (the kernel-level workload of round 1's f
 Extra objects on the JSON line: "roofline" (dominant kernel, HIP events on the library's own stream),
 "contract" (whole step against BASELINE.md §3's algorithmic bytes) and "cpu_baseline" (the oracle
 port timed on all host cores, one single-core worker per core, on a bounded sample).
+"ms_per_step" is the wall time of one timed step (--steps of them, after --warmup untimed ones).  --dump-outputs DIR writes what the
+last timed step computed (seeded inputs: the same arrays from run to run, so two builds can be compared output for output).
 """
 import argparse
 import json
@@ -171,6 +173,38 @@ def scheme_string(o, nh):
     return s
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6     # --dump-outputs: all arrays together
+DUMP_PER_ARRAY = 1 << 17            # values kept of one output field (1 MiB in float64)
+DUMP_SEED = 20250114
+
+
+def dump_sample_index(ntile, nk, ny, nx, n_arrays, seed=DUMP_SEED):
+    """Flat indices into a padded field [ntile, nk, ny + 7, nx + 7] (fv3lm_field_get) of a fixed, seeded sample of its compute
+    domain (halo 3 on every side): every point when the domain is small, else DUMP_PER_ARRAY of them, fewer if n_arrays of that
+    size would pass DUMP_LIMIT_BYTES.  Depends on the shape alone, so two builds dump the same points."""
+    import numpy as np
+    total = ntile * nk * ny * nx
+    m = min(total, DUMP_PER_ARRAY, (DUMP_LIMIT_BYTES // n_arrays - 1024) // 8)     # 1 KiB per file for the .npy header
+    pick = np.arange(total) if m == total else np.sort(np.random.default_rng(seed).choice(total, size=m, replace=False))
+    t, k, j, i = np.unravel_index(pick, (ntile, nk, ny, nx))
+    return np.ravel_multi_index((t, k, j + 3, i + 3), (ntile, nk, ny + 7, nx + 7))
+
+
+def sample_fields(dy, names, which, idx, prefix, out):
+    """out[prefix + name] = the sampled values of device field `name` (which: 0 trajectory, 1 perturbation / adjoint), float64"""
+    for n in names:
+        out[prefix + n] = dy.get(n, which).reshape(-1)[idx]
+
+
+def write_dump(directory, arrays):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for n, a in sorted(arrays.items()):
+        np.save(os.path.join(directory, n + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": directory, "arrays": len(arrays), "values_per_array": max(a.size for a in arrays.values()),
+            "bytes": sum(os.path.getsize(os.path.join(directory, n + ".npy")) for n in arrays)}
+
+
 def default_layout(world):
     """Whole faces while they deal out evenly (1, 2, 3, 6 GPUs); otherwise the 24 sub-face tiles of a 2 x 2 layout, dealt in position-major
     order: 4 GPUs hold the six tiles of one position each (one tile class, balanced -- six faces on four GPUs would be 2 + 2 + 1 + 1),
@@ -208,7 +242,15 @@ def main():
                     help="one GPU: every halo row between two resident tiles travels as a message through ncclSend / ncclRecv on a one-rank communicator "
                          "(the rank as its own peer) instead of the local gather -- the cost of the message path itself, not the headline configuration")
     ap.add_argument("--profile-out", default="")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="one GPU: write what the last timed step computed as DIR/<name>.npy (float64, a fixed seeded sample of each field's compute "
+                         "domain, under 64 MB in all): tl_traj_* / tl_pert_* after step_tl (the clock stops while they are copied out), "
+                         "ad_traj_* / ad_adj_* after step_nl + step_ad")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs is a one-GPU option")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process starts N fresh children, one rank per GPU, before anything here has
@@ -327,10 +369,12 @@ def main():
             c.dy.put(n, T[n], 0); c.dy.put(n, P[n], 1)
         c.dy.state_save()
 
-    def one_step():
+    def one_step(after_tl=None):
         if not active:
             return
         c.dy.state_restore(); c.dy.step_tl()
+        if after_tl is not None:
+            after_tl()
         c.dy.state_restore(); c.dy.step_nl(); c.dy.step_ad()
 
     def barrier():
@@ -343,14 +387,31 @@ def main():
         if active:
             c.dy.sync()
 
+    dumped, paused = {}, 0.0
+    if args.dump_outputs:
+        d = c.dy.dims
+        assert all(c.dy.levels(n) == args.npz for n in names)
+        dump_idx = dump_sample_index(d.ntile, args.npz, d.ny, d.nx, 4 * len(names))
+
+        def capture_tl():       # last timed step: step_tl's result is overwritten by the state_restore before step_nl
+            nonlocal paused
+            barrier()
+            t = time.perf_counter()
+            sample_fields(c.dy, names, 0, dump_idx, "tl_traj_", dumped)
+            sample_fields(c.dy, names, 1, dump_idx, "tl_pert_", dumped)
+            paused += time.perf_counter() - t
+
     for _ in range(args.warmup):
         one_step()
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        one_step()
+    for s in range(args.steps):
+        one_step(capture_tl if args.dump_outputs and s == args.steps - 1 else None)
     barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - paused
+    if args.dump_outputs:
+        sample_fields(c.dy, names, 0, dump_idx, "ad_traj_", dumped)
+        sample_fields(c.dy, names, 1, dump_idx, "ad_adj_", dumped)
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if args.rehearse_host_transport else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -404,6 +465,8 @@ def main():
                          "note": "whole TL+AD step against BASELINE.md §3 (2.75 x B_TL, %d B per cell and acoustic step); state resident in HBM: the host<->device "
                                  "copies of a drop-in step_tl/step_ad (DESIGN.md §6) are outside the timed region" % (1280 if args.nonhydrostatic else 880)},
         }
+        if args.dump_outputs:
+            out["dump_outputs"] = write_dump(args.dump_outputs, dumped)
         if args.profile_out:
             with open(args.profile_out, "w") as f:
                 f.write("# per-kernel HIP-event profile of one TL+AD step (bench.py roofline leg)\n")

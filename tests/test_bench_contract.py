@@ -52,3 +52,35 @@ def test_default_layout_balances_the_gpus():
     tl = cube.tiles(48, 2)
     for r in range(4):
         assert len({(tl[t][1], tl[t][2]) for t in cube.faces_of(r, 4, 24)}) == 1
+
+
+def test_dump_sample_is_fixed_and_inside_the_compute_domain():
+    import numpy as np
+    # the headline workload: six C192 faces, L127, 8 state fields, 4 arrays each (tl_traj, tl_pert, ad_traj, ad_adj)
+    a = bench.dump_sample_index(6, 127, 192, 192, 32)
+    assert np.array_equal(a, bench.dump_sample_index(6, 127, 192, 192, 32))
+    assert a.size == bench.DUMP_PER_ARRAY and np.all(np.diff(a) > 0)
+    assert 32 * (8 * a.size + 1024) <= bench.DUMP_LIMIT_BYTES
+    t, k, j, i = np.unravel_index(a, (6, 127, 199, 199))
+    assert j.min() >= 3 and j.max() < 195 and i.min() >= 3 and i.max() < 195 and len(set(t.tolist())) == 6 and len(set(k.tolist())) == 127
+    # many arrays: each gets fewer points, the total stays under the limit
+    b = bench.dump_sample_index(6, 127, 192, 192, 400)
+    assert 400 * (8 * b.size + 1024) <= bench.DUMP_LIMIT_BYTES
+    # a small domain is dumped whole, in order
+    c = bench.dump_sample_index(1, 2, 4, 5, 8)
+    x = np.zeros((1, 2, 11, 12)); x[:, :, 3:7, 3:8] = np.arange(40).reshape(1, 2, 4, 5)
+    assert np.array_equal(x.reshape(-1)[c], np.arange(40))
+
+
+def test_write_dump_writes_float64_npy(tmp_path):
+    import numpy as np
+    info = bench.write_dump(str(tmp_path / "d"), {"tl_pert_u": np.arange(5.0), "ad_adj_u": np.ones(5, dtype=np.float32)})
+    assert info["arrays"] == 2 and info["bytes"] <= bench.DUMP_LIMIT_BYTES
+    for n in ("tl_pert_u", "ad_adj_u"):
+        assert np.load(str(tmp_path / "d" / (n + ".npy"))).dtype == np.float64
+
+
+def test_bench_rejects_bad_arguments_before_touching_a_gpu():
+    for extra in (["--steps", "0"], ["--gpus", "2", "--dump-outputs", "x"]):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True)
+        assert p.returncode == 2 and "error" in p.stderr, (extra, p.stderr)
