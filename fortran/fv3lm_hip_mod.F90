@@ -18,6 +18,7 @@ module fv3lm_hip_mod
   public :: fv3lm_hip_create, fv3lm_hip_destroy, fv3lm_hip_put, fv3lm_hip_get
   public :: fv3lm_hip_step_tl, fv3lm_hip_step_ad
   public :: fv3lm_hip_traj_to_fv3, fv3lm_hip_pert_to_fv3, fv3lm_hip_fv3_to_pert
+  public :: fv3lm_hip_set_rayleigh, fv3lm_hip_rayleigh_profile
 
   integer, parameter :: ng = 3   ! halo width, tools/fv_mp_nlm_mod.F90:67
 
@@ -70,6 +71,19 @@ module fv3lm_hip_mod
       import :: c_ptr, c_int, c_double
       type(c_ptr), value :: h
       real(c_double), intent(in) :: edge(*), ecorner(*)
+      integer(c_int) :: rc
+    end function
+    function c_set_rayleigh(h, tau, rf_cutoff, c2l) bind(C, name="fv3lm_set_rayleigh") result(rc)
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h, c2l
+      real(c_double), value :: tau, rf_cutoff
+      integer(c_int) :: rc
+    end function
+    function c_rayleigh_profile(h, rf, kmax) bind(C, name="fv3lm_rayleigh_profile") result(rc)
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      real(c_double), intent(out) :: rf(*)
+      integer(c_int), intent(out) :: kmax
       integer(c_int) :: rc
     end function
     function c_set_exchange(h, kind, rows, nrows) bind(C, name="fv3lm_set_exchange") result(rc)
@@ -195,6 +209,27 @@ contains
     real(c_double), intent(in) :: edge(:, :, :), ecorner(:, :, :)
     call check(c_set_face_data(self%handle, edge, ecorner), 'set_face_data')
   end subroutine fv3lm_hip_set_face_data
+
+  !> Rayleigh damping of the upper layers (RAYLEIGH_SUPER): flagstruct%tau (days; 0 = off), flagstruct%rf_cutoff (Pa) and the
+  !! cubed-to-lat-lon matrices gridstruct%a11 a12 a21 a22 laid into the padded plane as (pi, pj, 4, ntile); c2l may be left out
+  !! when tau = 0.  Call after fv3lm_hip_create, before the first step.
+  subroutine fv3lm_hip_set_rayleigh(self, tau, rf_cutoff, c2l)
+    type(fv3lm_hip_type), intent(inout) :: self
+    real(c_double), intent(in) :: tau, rf_cutoff
+    real(c_double), intent(in), target, contiguous, optional :: c2l(:, :, :, :)
+    type(c_ptr) :: p
+    p = c_null_ptr
+    if (present(c2l)) p = c_loc(c2l)
+    call check(c_set_rayleigh(self%handle, tau, rf_cutoff, p), 'set_rayleigh')
+  end subroutine fv3lm_hip_set_rayleigh
+
+  !> rf(1:npz) (0 below the cutoff) and kmax as the library computed them
+  subroutine fv3lm_hip_rayleigh_profile(self, rf, kmax)
+    type(fv3lm_hip_type), intent(inout) :: self
+    real(c_double), intent(out) :: rf(:)
+    integer(c_int), intent(out) :: kmax
+    call check(c_rayleigh_profile(self%handle, rf, kmax), 'rayleigh_profile')
+  end subroutine fv3lm_hip_rayleigh_profile
 
   !> One halo-exchange table (kind 0..4, include/fv3lm.h): rows(7, n) for the faces resident on this GPU, and the
   !! per-peer send/receive lists for faces held by other ranks (replaces mpp_update_domains / mpp_get_boundary).

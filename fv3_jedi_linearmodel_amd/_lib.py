@@ -213,6 +213,30 @@ class Dycore:
         role: nonlinear sweep storing the stage checkpoints)."""
         self._chk(self.lib.L.fv3lm_step_ad(self.h))
 
+    # ---- Rayleigh damping of the upper layers (RAYLEIGH_SUPER, fv_dynamics_tlm.F90:1749-1899) ----
+    def set_rayleigh(self, tau, rf_cutoff, c2l=None):
+        """fv3lm_set_rayleigh: tau (days; 0 = off), rf_cutoff (Pa), c2l = a11 a12 a21 a22 as [ntile, 4, pj, pi] (None: NULL)."""
+        ptr = None
+        if c2l is not None:
+            a = np.ascontiguousarray(c2l, dtype=np.float64)
+            assert a.shape == (self.dims.ntile, 4, self.pj, self.pi), a.shape
+            self._c2l = a
+            ptr = _ptr(a)
+        self.lib.L.fv3lm_set_rayleigh.argtypes = [C.c_void_p, C.c_double, C.c_double, _dp]
+        self._chk(self.lib.L.fv3lm_set_rayleigh(self.h, float(tau), float(rf_cutoff), ptr))
+
+    def rayleigh_profile(self):
+        """-> (rf[npz], kmax) as the library computed them (rf = 0 below the cutoff)"""
+        rf = np.zeros(self.dims.npz); kmax = C.c_int(0)
+        self.lib.L.fv3lm_rayleigh_profile.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_int)]
+        self._chk(self.lib.L.fv3lm_rayleigh_profile(self.h, _ptr(rf), C.byref(kmax)))
+        return rf, kmax.value
+
+    def rayleigh(self, mode):
+        """the damping on its own (tests): u v pt (w; non-hydrostatic: heated temperature in field "rf_pt"); adjoint after a NL call"""
+        self.lib.L.fv3lm_rayleigh.argtypes = [C.c_void_p, C.c_int]
+        self._chk(self.lib.L.fv3lm_rayleigh(self.h, mode))
+
     # ---- the host's boundary copies on the device (compact arrays [ntile, nk, ny, nx], no halo) ----
     def _cptrs(self, d, names, out=False):
         keep = []

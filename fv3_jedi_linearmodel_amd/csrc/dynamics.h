@@ -5,6 +5,7 @@
 #pragma once
 #include "dycore.h"
 #include "remap.h"
+#include "rayleigh.h"
 
 namespace fv3 {
 
@@ -130,13 +131,23 @@ struct Dynamics : Dycore {
   void build_remap_nh();
   void remap_nh_run(int mode, int km);
   double* ck_k = nullptr;      // per-k_split checkpoints
-  double* ck_0 = nullptr;      // initial T and pkz
+  double* ck_0 = nullptr;      // T as pt_in reads it (after the Rayleigh damping of a hydrostatic step) and pkz
   size_t ck_k_stride = 0;
   int nsplt_max = 1;
   bool tracer_subcycle_error = false;
   std::vector<std::pair<double*, size_t>> tracer_zero;     // plan_adjoint(tracer_q, twork)
   std::vector<double*> snap;   // device snapshot of the prognostic state (fv3lm_state_save)
   double* stage_dev = nullptr;   // compact staging buffer of the boundary copies (one field)
+  // Rayleigh damping of the upper layers (rayleigh.h; fv3lm_set_rayleigh): off while rf_kmax = 0
+  int rf_kmax = 0;
+  std::vector<double> rf_host;                   // rf(k), k = 1..npz, 0 below the cutoff
+  std::vector<double> ak_host, bk_host;          // the reference pressures pm(k) of the damping
+  double *rf_lv = nullptr, *rf_c2l = nullptr, *rf_ck = nullptr;   // per-level constants, cubed-to-lat-lon matrices, wind checkpoint
+  Fld rf_pth;                                    // non-hydrostatic: the heated temperature of levels 1..kmax ("rf_pt")
+  Progs pt_in_rf;                                // non-hydrostatic pt_in with the damping on (stages.h DynPtInNhRf)
+  bool set_rayleigh(double tau, double rf_cutoff, const double* c2l);
+  RfArgs rf_args();
+  void rayleigh(int mode);
   // one field between the host's compact array and the device state.  which: 0 trajectory, 1 perturbation / adjoint
   void compact_in(const Fld& f, int which, const double* host) {
     const size_t n = (size_t)ntile_all * f.nk * g.tx * g.ty;
@@ -203,6 +214,7 @@ inline bool Dynamics::init2(const double* ak, const double* bk) {
   ak_dev = (double*)dev_alloc((npz + 1) * 8); bk_dev = (double*)dev_alloc((npz + 1) * 8);
   if (ak) h2d(ex, ak_dev, ak, (npz + 1) * 8);
   if (bk) h2d(ex, bk_dev, bk, (npz + 1) * 8);
+  if (ak && bk) { ak_host.assign(ak, ak + npz + 1); bk_host.assign(bk, bk + npz + 1); }
   if (nh) {
     if (!ak || !bk) { err = "non-hydrostatic: ak, bk needed (reference layer thicknesses)"; return false; }
     for (int k = 1; k <= npz; ++k) lev_host[k - 1].dp_ref = ak[k] - ak[k - 1] + (bk[k] - bk[k - 1]) * 1.e5;
@@ -249,6 +261,7 @@ inline bool Dynamics::init2(const double* ak, const double* bk) {
 }
 inline void Dynamics::destroy2() {
   dev_free(stage_dev); stage_dev = nullptr;
+  dev_free(rf_lv); dev_free(rf_c2l); dev_free(rf_ck); dev_free(rf_pth.t); dev_free(rf_pth.p);
   dev_free(ak_dev); dev_free(bk_dev); if (remap_ws_own) dev_free(remap_ws); dev_free(cmax_dev); dev_free(ck_k); dev_free(ck_0); dev_free(ck_nh);
   tshared.destroy(); twork.destroy();
   for (double* p : snap) dev_free(p);
@@ -487,9 +500,11 @@ inline void Dynamics::tracer_ad() {
 
 inline void Dynamics::fv_dynamics(int mode) {
   const size_t b3 = n3 * 8, b3p = n3p * 8;
+  const bool rf_nh = rf_kmax > 0 && nh;
   if (mode != MODE_AD) {
+    rayleigh(mode);       // RAYLEIGH_SUPER before the conversion (fv_dynamics_tlm.F90:535-562); nothing while it is off
     if (mode == MODE_NL) { dev_copy(ex, ck_0, f("pt").t, b3); dev_copy(ex, ck_0 + n3, f("pkz").t, b3); }
-    run_group(pt_in, nullptr, mode);
+    run_group(rf_nh ? pt_in_rf : pt_in, nullptr, mode);
     dev_copy(ex, f("pt").t, f("pt_o").t, b3);
     if (mode == MODE_TL) dev_copy(ex, f("pt").p, f("pt_o").p, b3);
     for (int km = 0; km < k_split; ++km) {
@@ -565,7 +580,84 @@ inline void Dynamics::fv_dynamics(int mode) {
   dev_copy(ex, f("pt").t, ck_0, b3); dev_copy(ex, f("pkz").t, ck_0 + n3, b3);
   if (nq > 0) dev_copy(ex, q[0].t, ckq(0, 0), b3);
   dev_copy(ex, f("pt_o").p, f("pt").p, b3); dev_zero(ex, f("pt").p, b3);
-  run_group(pt_in, nullptr, MODE_AD);
+  if (rf_nh) for (int t = 0; t < ntile_all; ++t) dev_zero(ex, rf_pth.p + (size_t)t * g.npz * g.plane, (size_t)rf_kmax * g.plane * 8);
+  run_group(rf_nh ? pt_in_rf : pt_in, nullptr, MODE_AD);
+  rayleigh(MODE_AD);
+}
+
+// fv3lm_set_rayleigh: rf(k) once per handle (the reference computes it once per module, rf_initialized, fv_dynamics_tlm.F90:1810-1829),
+// with pm(k) the reference pressures of the layers (:419-423, p_ref = 1e5: fv_arrays_nlm.F90:403) and bdt the step of fv_dynamics.
+inline bool Dynamics::set_rayleigh(double tau, double cutoff, const double* c2l) {
+  // by the bit pattern of a copy the compiler cannot see through: the library is built with -ffinite-math-only, under which
+  // std::isfinite, and even a bit test of an argument it assumes finite, fold to true
+  auto finite = [](double x) { volatile double v = x; const double y = v; uint64_t b; std::memcpy(&b, &y, 8); return ((b >> 52) & 0x7ffu) != 0x7ffu; };
+  if (!finite(tau) || !finite(cutoff)) { err = "fv3lm_set_rayleigh: tau and rf_cutoff must be finite"; return false; }
+  if (tau < 0.) { err = "fv3lm_set_rayleigh: tau < 0 (e-folding time in days; 0 switches the damping off)"; return false; }
+  if (tau > 0. && !(cutoff > opt.ptop)) { err = "fv3lm_set_rayleigh: tau > 0 needs rf_cutoff > ptop"; return false; }
+  if (tau > 0. && !c2l) { err = "fv3lm_set_rayleigh: tau > 0 needs the cubed-to-lat-lon matrices (c2l is null)"; return false; }
+  if (tau > 0. && ak_host.empty()) { err = "fv3lm_set_rayleigh: tau > 0 needs ak, bk (reference pressures), none were given to fv3lm_create"; return false; }
+  const int npz = g.npz;
+  const double pi_8 = 3.14159265358979323846, p_ref = 1.e5;     // FMS constants_mod pi_8
+  std::vector<double> lv;
+  rf_host.assign(npz, 0.);
+  int kmax = 0;
+  if (tau > 0.) {
+    const double tau0 = tau * 86400., dt = std::fabs(bdt);
+    for (int k = 1; k <= npz; ++k) {
+      const double ph1 = ak_host[k - 1] + bk_host[k - 1] * p_ref, ph2 = ak_host[k] + bk_host[k] * p_ref;
+      const double pm = (ph2 - ph1) / std::log(ph2 / ph1);
+      if (!(pm < cutoff)) break;
+      const double s = std::sin(0.5 * pi_8 * std::log(cutoff / pm) / std::log(cutoff / opt.ptop));
+      rf_host[k - 1] = dt / tau0 * (s * s);
+      lv.push_back(rf_host[k - 1]); lv.push_back(opt.cp_air - opt.rdgas * opt.ptop / pm);
+      kmax = k;
+    }
+  }
+  dev_free(rf_lv); dev_free(rf_c2l); dev_free(rf_ck); rf_lv = rf_c2l = rf_ck = nullptr;
+  rf_kmax = 0;
+  if (kmax == 0) return true;
+  const size_t pl = (size_t)ntile_all * g.plane;
+  rf_lv = (double*)dev_alloc(lv.size() * 8); h2d(ex, rf_lv, lv.data(), lv.size() * 8);
+  rf_c2l = (double*)dev_alloc(4 * pl * 8); h2d(ex, rf_c2l, c2l, 4 * pl * 8);
+  rf_ck = (double*)dev_alloc((nh ? 3 : 2) * pl * kmax * 8);
+  if (nh) {
+    if (!rf_pth.t) { rf_pth.t = (double*)dev_alloc(n3 * 8); rf_pth.p = (double*)dev_alloc(n3 * 8); rf_pth.nk = npz; F["rf_pt"] = rf_pth; }
+    pt_in_rf.c.assign(classes.size(), Program{}); pt_in_rf.cur = &cur_cls;
+    for (int c = 0; c < (int)classes.size(); ++c) {
+      set_class(c);
+      DynPtInNhRf s; s.in[0] = f("pt"); s.in[1] = nq > 0 ? q[0] : Fld{}; if (!s.in[1].t) s.in[1].nk = npz; s.in[2] = f("delp"); s.in[3] = f("delz");
+      s.in[4] = rf_pth; s.out[0] = f("pt_o"); s.out[1] = f("pkz"); s.orect[0] = s.orect[1] = R(g.is(), g.ie(), g.js(), g.je()); s.k1 = npz;
+      s.zvir = opt.zvir; s.akap = opt.akap; s.rdg = -opt.rdgas / opt.grav; s.has_q = nq > 0; s.kmax = kmax; add(pt_in_rf, "pt_in", s);
+    }
+    set_class(-1);
+  }
+  if (!sticky_error().empty()) { err = sticky_error(); return false; }
+  rf_kmax = kmax;
+  return true;
+}
+// for the class being run: its geometry, fields, metrics and the class's part of the matrices and of the checkpoint
+inline RfArgs Dynamics::rf_args() {
+  RfArgs a; a.g = g;
+  a.u = ex.sh(f("u")); a.v = ex.sh(f("v")); a.pt = ex.sh(f("pt"));
+  a.w = nh ? ex.sh(f("w")) : Fld{}; a.pth = nh ? ex.sh(rf_pth) : a.pt;
+  a.dx = ctx.m.dx; a.dy = ctx.m.dy;
+  a.c2l = rf_c2l + ex.cls_off * 4;
+  a.lv = rf_lv; a.rcv = 1. / (opt.cp_air - opt.rdgas); a.kmax = rf_kmax; a.nh = nh ? 1 : 0;
+  const size_t fs = (size_t)ntile_all * rf_kmax * g.plane, off = ex.cls_off * rf_kmax;
+  a.cu = rf_ck + off; a.cv = rf_ck + fs + off; a.cw = nh ? rf_ck + 2 * fs + off : nullptr;
+  return a;
+}
+// levels 1..kmax only; the adjoint needs the checkpoint of the last MODE_NL run
+inline void Dynamics::rayleigh(int mode) {
+  if (rf_kmax == 0) return;
+  each_class([&]() {
+    const RfArgs a = rf_args();
+    const Rect E{g.is(), g.ie() + 1, g.js(), g.je() + 1};
+    const int nz = g.ntile * rf_kmax;
+    if (mode == MODE_AD) { for_points(ex, E, nz, RfAdFn{a}, "rayleigh.ad"); return; }
+    for_points(ex, E, nz, RfHeatFn{a, mode}, mode == MODE_NL ? "rayleigh_heat.nl" : "rayleigh_heat.tl");
+    for_points(ex, E, nz, RfDampFn{a, mode}, mode == MODE_NL ? "rayleigh_damp.nl" : "rayleigh_damp.tl");
+  });
 }
 
 }  // namespace fv3

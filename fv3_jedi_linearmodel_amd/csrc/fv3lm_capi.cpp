@@ -96,6 +96,17 @@ int fv3lm_set_face_data(fv3lm_handle* h, const double* edge, const double* ecorn
   if (!edge || !ecorner) return fail("fv3lm_set_face_data: null argument");
   return h->d.set_face_data(edge, ecorner) ? 0 : fail(h->d.err);
 }
+int fv3lm_set_rayleigh(fv3lm_handle* h, double tau, double rf_cutoff, const double* c2l) {
+  if (!h) return fail("fv3lm_set_rayleigh: null handle");
+  if (!h->d.set_rayleigh(tau, rf_cutoff, c2l)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_rayleigh_profile(fv3lm_handle* h, double* rf, int* kmax) {
+  if (!h || !rf || !kmax) return fail("fv3lm_rayleigh_profile: null argument");
+  for (int k = 0; k < h->d.g.npz; ++k) rf[k] = k < (int)h->d.rf_host.size() ? h->d.rf_host[(size_t)k] : 0.;
+  *kmax = h->d.rf_kmax;
+  return 0;
+}
 int fv3lm_set_exchange(fv3lm_handle* h, int kind, const int* rows, int nrows) {
   if (!rows && nrows > 0) return fail("fv3lm_set_exchange: null table");
   return h->d.set_exchange(kind, rows, nrows) ? 0 : fail(h->d.err);
@@ -172,6 +183,11 @@ int fv3lm_traj_slots(fv3lm_handle* h) { return (int)h->d.traj_slot.size(); }   /
 int fv3lm_tracer_nsplt(fv3lm_handle* h) { return h->d.nsplt_max; }   /* largest sub-step count tracer_2d has used so far */
 int fv3lm_remap(fv3lm_handle* h, int mode, int last_step) { h->d.each_class([&]() { run_remap(h->d.ex, mode, h->d.remap_args(last_step != 0)); }); return status(h); }
 int fv3lm_fv_dynamics(fv3lm_handle* h, int mode) { h->d.fv_dynamics(mode); return status(h); }
+int fv3lm_rayleigh(fv3lm_handle* h, int mode) {
+  if (mode < 0 || mode > 2) return fail("bad mode");
+  h->d.rayleigh(mode);
+  return status(h);
+}
 int fv3lm_step_tl(fv3lm_handle* h) { h->d.step_tl(); return status(h); }
 int fv3lm_step_nl(fv3lm_handle* h) { h->d.step_nl(); return status(h); }
 int fv3lm_step_ad(fv3lm_handle* h) { h->d.step_ad(); return status(h); }

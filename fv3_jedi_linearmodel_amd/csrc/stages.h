@@ -1432,6 +1432,21 @@ struct DynPtInNh {
     o[0] = tv / pkz; o[1] = pkz;
   }
 };
+// ... with Rayleigh damping on (rayleigh.h): pkz from the temperature before the heating (fv_dynamics_tlm.F90:436-470 precede :535),
+// the heated temperature of levels 1..kmax divided by it (:564-590)
+struct DynPtInNhRf {
+  STAGE_COMMON("DynPtInNh", 5, 2)   // in: pt(T) qv delp delz pt(T, heated)   out: pt(theta_v) pkz
+  double zvir, akap, rdg; int has_q, kmax;
+  HD static constexpr Box box(int) { return Box{0, 0, 0, 0, 0, 0}; }
+  template <class T, class A>
+  HD void eval(const A& a, const Ctx& c, int tile, int i, int j, int k, T* o) const {
+    T d = has_q ? zvir * IN(1, i, j) : T(0.);
+    T tv = IN(0, i, j) * (1. + d);
+    T pkz = dexp(akap * dlog(rdg * IN(2, i, j) * tv / IN(3, i, j)));
+    if (k <= kmax) tv = IN(4, i, j) * (1. + d);
+    o[0] = tv / pkz; o[1] = pkz;
+  }
+};
 
 // one_grad_p wind update from corner pk, gz (dyn_core_tlm.F90:4128-4157); level 1 of pk is the
 // constant top value (:4068-4072).

@@ -433,8 +433,19 @@ def cubed_sphere_metrics(n, radius=6371.0e3, omega=7.292e-5):
                          ec(G(t, npx, npx), C(t, npx - 1, npx), C(t, npx - 2, npx + 1))]
         ecorner[t, 3] = [ec(G(t, 1, npx), C(t, 1, npx - 1), C(t, 2, npx - 2)), ec(G(t, 1, npx), C(t, 0, npx - 1), C(t, -1, npx - 2)),
                          ec(G(t, 1, npx), C(t, 1, npx), C(t, 2, npx + 1))]
+    # cubed-to-lat-lon matrices of C2L_ORD2 (fv_grid_utils_nlm.F90:2289-2303): z_mn = the cell-centre grid-line unit vector m (ec1 along i,
+    # ec2 along j: the frame of sin_sg5 above) dotted with the local east (n = 1) and north (n = 2) unit vectors
+    at, ec1, ec2 = views[5]
+    lon, lat = np.arctan2(at[..., 1], at[..., 0]), np.arcsin(np.clip(at[..., 2], -1, 1))
+    vlon = np.stack([-np.sin(lon), np.cos(lon), np.zeros_like(lon)], axis=-1)
+    vlat = np.stack([-np.sin(lat) * np.cos(lon), -np.sin(lat) * np.sin(lon), np.cos(lat)], axis=-1)
+    dot = lambda a, b: np.einsum("...i,...i", a, b)
+    s5 = m["sin_sg5"][sl]
+    c2l = np.zeros((6, 4, pj, pj))
+    for q, z in enumerate((0.5 * dot(ec2, vlat), -0.5 * dot(ec1, vlat), -0.5 * dot(ec2, vlon), 0.5 * dot(ec1, vlon))):   # a11 a12 a21 a22
+        c2l[:, q, :-1, :-1] = np.where(np.isfinite(z / s5), z / s5, 0.0)
     out = {k: np.ascontiguousarray(v) for k, v in m.items()}
-    return out, da_min, da_min_c, edge, ecorner, dict(corners=P, centers=ctr)
+    return out, da_min, da_min_c, edge, ecorner, dict(corners=P, centers=ctr, c2l=c2l)
 
 
 def cube_fields(n, npz, geo, seed, kind="traj", opt=None):

@@ -77,6 +77,15 @@ def synthetic_tile_metrics(nx, ny, dx0=2.0e5, skew=0.25, stretch=0.08, lat0=35.0
     return out, da_min, da_min_c
 
 
+def synthetic_tile_c2l(metrics):
+    """Cubed-to-lat-lon matrices a11 a12 a21 a22 (NLM/fv_grid_utils_nlm.F90:2300-2303) of the synthetic tile, [ntile, 4, pj, pi], in the
+    local frame its ALPHA implies: grid line i along east, grid line j at angle alpha from it, so that at the cell centre z11 = 1,
+    z12 = 0, z21 = cos alpha = cos_sg5, z22 = sin alpha = sin_sg5."""
+    s, c = metrics["sin_sg5"], metrics["cos_sg5"]
+    z11, z12, z21, z22 = np.ones_like(s), np.zeros_like(s), c, s
+    return np.ascontiguousarray(np.stack([0.5 * z22 / s, -0.5 * z12 / s, -0.5 * z21 / s, 0.5 * z11 / s], axis=1))
+
+
 def hybrid_levels(npz, ptop=1.0, p0=1.0e5):
     """Smooth synthetic hybrid coefficients: pe(k) = ak(k) + bk(k)*ps, pure pressure aloft."""
     s = np.linspace(0.0, 1.0, npz + 1) ** 1.6

@@ -16,18 +16,22 @@ class Case:
     def __init__(self, nx=12, ny=12, npz=8, n_split=2, k_split=1, dt=1800.0, backend="hip", seed=20250114, oracle=False, nq=0,
                  face=None, **optkw):
         """face=None: the doubly-periodic tile with no cube edge.  face=t (0..5): one whole face of a C<nx> cube with
-        the real gnomonic metrics of that face and arbitrary smooth halo data (kernel-group tests)."""
+        the real gnomonic metrics of that face and arbitrary smooth halo data (kernel-group tests).
+        tau=, rf_cutoff=: Rayleigh damping of the upper layers (fv3lm_set_rayleigh; off by default)."""
         self.nx, self.ny, self.npz = nx, ny, npz
+        self.tau, self.rf_cutoff = optkw.pop("tau", 0.0), optkw.pop("rf_cutoff", 0.0)
         self.opt = default_options(**optkw)
         self.face = face
         if face is None:
             self.metrics, self.da_min, self.da_min_c = synthetic_tile_metrics(nx, ny)
+            self.c2l = G.synthetic_tile_c2l(self.metrics)
         else:
             from . import cube
             assert nx == ny
-            m6, self.da_min, self.da_min_c, edge, ecorner, _ = cube.cubed_sphere_metrics(nx)
+            m6, self.da_min, self.da_min_c, edge, ecorner, geo = cube.cubed_sphere_metrics(nx)
             self.metrics = {k: np.ascontiguousarray(v[face:face + 1]) for k, v in m6.items()}
             self.edge, self.ecorner = np.ascontiguousarray(edge[face:face + 1]), np.ascontiguousarray(ecorner[face:face + 1])
+            self.c2l = np.ascontiguousarray(geo["c2l"][face:face + 1])
         self.traj, self.phis, self.ak, self.bk = G.synthetic_state(nx, ny, npz, self.opt, seed=seed)
         self.pert = G.synthetic_pert(nx, ny, npz, seed=seed + 1)
         for d in (self.traj, self.pert):
@@ -51,6 +55,8 @@ class Case:
         if face is not None:
             self.dy.set_face_data(self.edge, self.ecorner)
         self._after_create(backend)
+        if self.tau:
+            self.dy.set_rayleigh(self.tau, self.rf_cutoff, self.c2l)
 
     # hooks of tests/common.py (oracle as checker, host-emulation backend); the package itself knows the HIP library only
     def _make_oracle(self):
@@ -96,8 +102,10 @@ class CubeCase:
         self.layout = layout
         self.nt = self.nx = self.ny = n // layout
         self.npz, self.nq = npz, nq
+        self.tau, self.rf_cutoff = optkw.pop("tau", 0.0), optkw.pop("rf_cutoff", 0.0)
         self.opt = default_options(**optkw)
         self.metrics, self.da_min, self.da_min_c, self.edge, self.ecorner, self.geo = cube.cubed_sphere_metrics(n)
+        self.c2l = self.geo["c2l"]
         self.traj, self.phis, self.ak, self.bk = cube.cube_fields(n, npz, self.geo, seed, "traj", self.opt)
         self.pert = cube.cube_fields(n, npz, self.geo, seed + 1, "pert")
         aux = cube.cube_fields(n, npz, self.geo, seed + 11, "pert") if nq else None
@@ -110,6 +118,7 @@ class CubeCase:
             W = lambda a: cube.tile_window(a, tl, nt)
             self.face_fields = dict(traj=self.traj, pert=self.pert, phis=self.phis, qtraj=self.qtraj, qpert=self.qpert)      # on whole faces (the oracle's view)
             self.metrics = {k: W(v) for k, v in self.metrics.items()}
+            self.c2l = W(self.c2l)
             pt_ = nt + 7
             self.edge = np.ascontiguousarray(np.stack([np.stack([self.edge[f, e, (j0 if e < 2 else i0) - 1:(j0 if e < 2 else i0) - 1 + pt_] for e in range(4)]) for (f, i0, j0) in tl]))
             self.ecorner = np.ascontiguousarray(np.stack([self.ecorner[f] for (f, _, _) in tl]))
@@ -124,6 +133,7 @@ class CubeCase:
         if world > 1:
             F = self.faces
             self.metrics = {k: np.ascontiguousarray(v[F]) for k, v in self.metrics.items()}
+            self.c2l = np.ascontiguousarray(self.c2l[F])
             self.edge, self.ecorner, self.phis = np.ascontiguousarray(self.edge[F]), np.ascontiguousarray(self.ecorner[F]), np.ascontiguousarray(self.phis[F])
             self.traj = {k: np.ascontiguousarray(v[F]) for k, v in self.traj.items()}; self.pert = {k: np.ascontiguousarray(v[F]) for k, v in self.pert.items()}
             self.qtraj = [np.ascontiguousarray(v[F]) for v in self.qtraj]; self.qpert = [np.ascontiguousarray(v[F]) for v in self.qpert]
@@ -143,6 +153,8 @@ class CubeCase:
         self.dy = Dycore(self.lib, self.dims, self.opt, self.metrics, self.da_min, self.da_min_c, self.phis, self.ak, self.bk)
         self.dy.set_face_data(self.edge, self.ecorner)
         self._after_create(backend)
+        if self.tau:
+            self.dy.set_rayleigh(self.tau, self.rf_cutoff, self.c2l)
         for k, t in self.tables.items():
             if world > 1 or loopback:
                 self.dy.set_exchange_split(k, t, rank, world, ntiles, loopback)

@@ -89,6 +89,15 @@ int fv3lm_create(fv3lm_handle** h, const fv3lm_dims* dims, const fv3lm_options* 
  * extrap_corner factors x1/(x2-x1) of a2b_ord4's four corners (a2b_edge_tlm.F90:101-139, :1478-1487) as
  * [ntile][4: sw se ne nw][3], in the order the reference evaluates them. */
 int fv3lm_set_face_data(fv3lm_handle* h, const double* edge, const double* ecorner);
+/* Rayleigh damping of the upper layers (RAYLEIGH_SUPER, fv_dynamics_tlm.F90:1749-1899).  tau: e-folding time in days
+ * (flagstruct%tau; 0 switches it off, the default); rf_cutoff: pressure (Pa) above which levels are damped (flagstruct%rf_cutoff);
+ * c2l: the cubed-to-lat-lon matrices a11 a12 a21 a22 of fv_grid_type as [ntile][4][pj][pi] (padded plane, like the metrics).
+ * Call after fv3lm_create, before the first step; may be called again.  Refused: tau < 0, values that are not finite, and with
+ * tau > 0: rf_cutoff <= ptop, c2l == NULL, or a handle created without ak, bk.  Built for conserve = .true., not nested,
+ * grid_type < 4 (RAYLEIGH_FRICTION, grid_type >= 4, is not). */
+int fv3lm_set_rayleigh(fv3lm_handle* h, double tau, double rf_cutoff, const double* c2l);
+/* rf(k) for k = 1..npz (0 below the cutoff) and kmax, as the library computed them (tests, diagnostics). */
+int fv3lm_rayleigh_profile(fv3lm_handle* h, double* rf, int* kmax);
 /* Halo exchange between the resident faces: replaces the FMS calls mpp_update_domains / mpp_get_boundary that the
  * reference issues from DYN_CORE_TLM (dyn_core_tlm.F90:1744-1790, :1960-1990, :2280-2300, :2418-2434) and
  * FV_DYNAMICS_TLM (fv_dynamics_tlm.F90:646-651, :708-712).  One table per kind of exchange:
@@ -171,6 +180,9 @@ int fv3lm_traj_slots(fv3lm_handle* h);                          /* acoustic step
 int fv3lm_tracer_nsplt(fv3lm_handle* h);                        /* largest tracer sub-step count (nsplt, fv_tracer2d_tlm.F90:1317) used so far */
 int fv3lm_remap(fv3lm_handle* h, int mode, int last_step);      /* LAGRANGIAN_TO_EULERIAN_TLM fv_mapz_tlm.F90:69 / _FWD+_BWD */
 int fv3lm_fv_dynamics(fv3lm_handle* h, int mode);               /* FV_DYNAMICS_TLM fv_dynamics_tlm.F90:87 / _FWD+_BWD */
+int fv3lm_rayleigh(fv3lm_handle* h, int mode);                  /* RAYLEIGH_SUPER_TLM fv_dynamics_tlm.F90:1749 / _FWD+_BWD fv_dynamics_adm.F90:2327-2652
+                                                                   on u v pt (w); non-hydrostatic: the heated temperature goes to field "rf_pt",
+                                                                   pt keeps the one pt_in takes pkz from.  Adjoint: after a MODE_NL call */
 /* Per-kernel HIP-event profile of everything launched between begin and end, on the library's stream:
  * lines "kernel count total_ms algorithmic_bytes".  Returns the buffer length needed. */
 int fv3lm_profile_begin(fv3lm_handle* h);

@@ -1,5 +1,6 @@
 """Kernel-level timing on the MI355X: the headline workload (six C192 L127 faces) or a smaller one, one step_tl + step_nl + step_ad under the
 library's HIP-event profiler, per-kernel table filtered by name.  Usage: python tools/kbench.py [--lib path.so] [--nx 192] [--npz 127] [--grep Tp]
+[--tau 10 --rf-cutoff 750] (Rayleigh damping of the upper layers on)
 Variants of one translation unit are compared by linking them into differently named libraries (FV3LM_LIB)."""
 import argparse
 import os
@@ -19,6 +20,8 @@ def main():
     ap.add_argument("--grep", default="")
     ap.add_argument("--top", type=int, default=25)
     ap.add_argument("--nh", action="store_true")
+    ap.add_argument("--tau", type=float, default=0.0, help="Rayleigh damping e-folding time in days (0: off)")
+    ap.add_argument("--rf-cutoff", type=float, default=750.0, help="Rayleigh damping cutoff pressure (Pa)")
     ap.add_argument("--group", default="", help="after one ordinary step: time this kernel group alone (TL and NL), e.g. d_sw")
     ap.add_argument("--ad", action="store_true", help="group mode: time the adjoint of the group instead of TL + NL")
     ap.add_argument("--experiment", default="", help="comma list of FV3LM_TP2_EXPERIMENT values to time the group with (experiment builds only)")
@@ -27,6 +30,8 @@ def main():
         os.environ["FV3LM_LIB"] = os.path.abspath(args.lib)
     from fv3_jedi_linearmodel_amd.harness import CubeCase, cube_step_state, cube_nh_state
     kw = dict(hydrostatic=0) if args.nh else {}
+    if args.tau > 0:
+        kw.update(tau=args.tau, rf_cutoff=args.rf_cutoff)
     c = CubeCase(n=args.nx, npz=args.npz, n_split=6, k_split=2, dt=450.0, backend="hip", nq=args.nq, **kw)
     T, P = cube_step_state(c)
     if args.nh:
@@ -61,6 +66,8 @@ def main():
     c.dy.profile_begin(); step(); prof = c.dy.profile_end()
     tot = sum(v[1] for v in prof.values())
     print("lib %s: %.1f ms per TL+AD step (kernel time %.1f ms, %d launches)" % (args.lib or "default", 1e3 * dt, tot, sum(v[0] for v in prof.values())))
+    if args.tau > 0:
+        print("Rayleigh damping: tau %g days, rf_cutoff %g Pa, kmax %d of %d levels" % (args.tau, args.rf_cutoff, c.dy.rayleigh_profile()[1], args.npz))
     rows = sorted(prof.items(), key=lambda kv: -kv[1][1])
     if args.grep:
         rows = [r for r in rows if any(g in r[0] for g in args.grep.split(","))]
