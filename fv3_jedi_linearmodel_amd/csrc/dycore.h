@@ -743,6 +743,7 @@ inline bool Dycore::init(int nx, int ny, int npz, int ntile, int face, int nq_, 
     if (nh && o.nord > 1) { err = "non-hydrostatic with a trajectory nord > 1: the w / height damping would need the tangent of del6_vt_flux with nord 2 (sw_core_tlm.F90:1713-1726), not built"; return false; }
   }
   if (nh && npz < 3) { err = "non-hydrostatic solver needs npz >= 3"; return false; }
+  if (!nh && npz < 2) { err = "hydrostatic vertical remap: the column map (edge values of cs_profile / scalar_profile) needs npz >= 2"; return false; }
   if (nh && !(o.a_imp > 0.5)) { err = "non-hydrostatic: a_imp must be > 0.5 (semi-implicit solver; the reference's a_imp <= 0.5 Riemann-invariant solver is not built)"; return false; }
   // options whose other values are not built are refused, never silently replaced by what is built:
   //   remap profiles: only the linear one, |kord| > 16 (fv_mapz_tlm.F90:8653-8666; the limited profiles are the split_kord work of DESIGN.md §8)

@@ -129,7 +129,7 @@ struct Dynamics : Dycore {
   double* ck_nh = nullptr;     // per k_split step: delp, w, delz before the remap + ws
   double* cknh(int km, int n) { return ck_nh + (size_t)km * (3 * n3 + (size_t)ntile_all * g.plane) + (size_t)n * n3; }
   void build_remap_nh();
-  void remap_nh_run(int mode, int km);
+  void remap_nh_run(int mode, bool last);      // last: the remap of the last k_split step (the temperature hand-over)
   double* ck_k = nullptr;      // per-k_split checkpoints
   double* ck_0 = nullptr;      // T as pt_in reads it (after the Rayleigh damping of a hydrostatic step) and pkz
   size_t ck_k_stride = 0;
@@ -229,6 +229,7 @@ inline bool Dynamics::init2(const double* ak, const double* bk) {
     const size_t need = (size_t)remap_ws_slots(nq) * (npz + 2) * ntile_all * g.plane;
     remap_ws_own = need > work.cap;
     remap_ws = remap_ws_own ? (double*)dev_alloc(need * 8) : work.p;
+    if (std::getenv("FV3LM_VERBOSE")) std::fprintf(stderr, "fv3lm: remap workspace %zu doubles: %s\n", need, remap_ws_own ? "own allocation (larger than the work arena)" : "in the work arena");
   }
   cmax_dev = (double*)dev_alloc((size_t)ntile_all * npz * 8);
   tshared.init(n3 * 9);       // build_tracer's nine shared fields; its per-tracer work arena is sized by a dry run
@@ -327,9 +328,8 @@ inline void Dynamics::build_remap_nh() {
 }
 // Vertical remap, non-hydrostatic: scalars by the column operators above, winds by the kernels of remap.h.
 // Adjoint: the pre-remap trajectory (pt u v q pe peln pk delp w delz ws) must be in place.
-inline void Dynamics::remap_nh_run(int mode, int km) {
+inline void Dynamics::remap_nh_run(int mode, bool last) {
   const size_t b3 = n3 * 8;
-  const bool last = km == k_split - 1;
   remap_last = last;
   std::vector<std::pair<Fld, Fld>> back{{f("w"), w_m}, {f("delz"), dz_m}};
   for (int n = 0; n < nq; ++n) back.push_back({q[n], q_m[n]});
@@ -534,7 +534,7 @@ inline void Dynamics::fv_dynamics(int mode) {
             dev_copy(ex, cknh(km, 3), f("ws").t, (size_t)ntile_all * g.plane * 8);
           }
         }
-        if (nh) remap_nh_run(mode, km); else
+        if (nh) remap_nh_run(mode, km == k_split - 1); else
         each_class([&]() { run_remap(ex, mode, remap_args(km == k_split - 1)); });
       }
     }
@@ -556,7 +556,7 @@ inline void Dynamics::fv_dynamics(int mode) {
         const char* r4[3] = {"delp", "w", "delz"};
         for (int n = 0; n < 3; ++n) dev_copy(ex, f(r4[n]).t, cknh(km, n), b3);
         dev_copy(ex, f("ws").t, cknh(km, 3), (size_t)ntile_all * g.plane * 8);
-        remap_nh_run(MODE_AD, km);
+        remap_nh_run(MODE_AD, km == k_split - 1);
       } else
       each_class([&]() { run_remap(ex, MODE_AD, remap_args(km == k_split - 1)); });
     }

@@ -181,7 +181,12 @@ int fv3lm_tracer_2d(fv3lm_handle* h, int mode) {
 }
 int fv3lm_traj_slots(fv3lm_handle* h) { return (int)h->d.traj_slot.size(); }   /* acoustic steps whose intermediates stay resident */
 int fv3lm_tracer_nsplt(fv3lm_handle* h) { return h->d.nsplt_max; }   /* largest sub-step count tracer_2d has used so far */
-int fv3lm_remap(fv3lm_handle* h, int mode, int last_step) { h->d.each_class([&]() { run_remap(h->d.ex, mode, h->d.remap_args(last_step != 0)); }); return status(h); }
+int fv3lm_remap(fv3lm_handle* h, int mode, int last_step) {
+  if (mode < 0 || mode > 2) return fail("bad mode");
+  if (h->d.nh) h->d.remap_nh_run(mode, last_step != 0);      // w and delz mapped, pt as density temperature through delz
+  else h->d.each_class([&]() { run_remap(h->d.ex, mode, h->d.remap_args(last_step != 0)); });
+  return status(h);
+}
 int fv3lm_fv_dynamics(fv3lm_handle* h, int mode) { h->d.fv_dynamics(mode); return status(h); }
 int fv3lm_rayleigh(fv3lm_handle* h, int mode) {
   if (mode < 0 || mode > 2) return fail("bad mode");

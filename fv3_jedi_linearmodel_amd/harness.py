@@ -17,9 +17,11 @@ class Case:
                  face=None, **optkw):
         """face=None: the doubly-periodic tile with no cube edge.  face=t (0..5): one whole face of a C<nx> cube with
         the real gnomonic metrics of that face and arbitrary smooth halo data (kernel-group tests).
-        tau=, rf_cutoff=: Rayleigh damping of the upper layers (fv3lm_set_rayleigh; off by default)."""
+        tau=, rf_cutoff=: Rayleigh damping of the upper layers (fv3lm_set_rayleigh; off by default).
+        levels=(ak, bk): hybrid coefficients [npz+1] in place of grid.hybrid_levels; the state's delp follows them at the same ps."""
         self.nx, self.ny, self.npz = nx, ny, npz
         self.tau, self.rf_cutoff = optkw.pop("tau", 0.0), optkw.pop("rf_cutoff", 0.0)
+        levels = optkw.pop("levels", None)
         self.opt = default_options(**optkw)
         self.face = face
         if face is None:
@@ -33,6 +35,12 @@ class Case:
             self.edge, self.ecorner = np.ascontiguousarray(edge[face:face + 1]), np.ascontiguousarray(ecorner[face:face + 1])
             self.c2l = np.ascontiguousarray(geo["c2l"][face:face + 1])
         self.traj, self.phis, self.ak, self.bk = G.synthetic_state(nx, ny, npz, self.opt, seed=seed)
+        if levels is not None:
+            ak, bk = (np.array(x, dtype=np.float64) for x in levels)
+            assert ak.shape == bk.shape == (npz + 1,), "levels: ak, bk of npz+1 interfaces"
+            ps = self.opt.ptop + self.traj["delp"].sum(axis=1)
+            self.traj["delp"] = np.stack([(ak[k + 1] - ak[k]) + (bk[k + 1] - bk[k]) * ps for k in range(npz)], axis=1)
+            self.ak, self.bk = ak, bk
         self.pert = G.synthetic_pert(nx, ny, npz, seed=seed + 1)
         for d in (self.traj, self.pert):
             for k in d:

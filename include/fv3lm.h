@@ -178,7 +178,11 @@ int fv3lm_traj_slots(fv3lm_handle* h);                          /* acoustic step
                                                                    in HBM so that the backward sweep need not recompute them; chosen at create from free memory,
                                                                    FV3LM_TRAJ_SLOTS caps it */
 int fv3lm_tracer_nsplt(fv3lm_handle* h);                        /* largest tracer sub-step count (nsplt, fv_tracer2d_tlm.F90:1317) used so far */
-int fv3lm_remap(fv3lm_handle* h, int mode, int last_step);      /* LAGRANGIAN_TO_EULERIAN_TLM fv_mapz_tlm.F90:69 / _FWD+_BWD */
+int fv3lm_remap(fv3lm_handle* h, int mode, int last_step);      /* LAGRANGIAN_TO_EULERIAN_TLM fv_mapz_tlm.F90:69 / _FWD+_BWD, remap_option 0.
+                                                                   Hydrostatic: T_v in log p, tracers, u, v; new pe, peln, pk, pkz, delp.
+                                                                   Non-hydrostatic handle: the non-hydrostatic remap of fv_dynamics (density
+                                                                   temperature through delz, w with the surface value ws, delz as -delz/delp);
+                                                                   last_step as passed */
 int fv3lm_fv_dynamics(fv3lm_handle* h, int mode);               /* FV_DYNAMICS_TLM fv_dynamics_tlm.F90:87 / _FWD+_BWD */
 int fv3lm_rayleigh(fv3lm_handle* h, int mode);                  /* RAYLEIGH_SUPER_TLM fv_dynamics_tlm.F90:1749 / _FWD+_BWD fv_dynamics_adm.F90:2327-2652
                                                                    on u v pt (w); non-hydrostatic: the heated temperature goes to field "rf_pt",

@@ -28,6 +28,13 @@ def test_nonhydrostatic_needs_three_levels():
     assert "npz" in str(e.value)
 
 
+def test_hydrostatic_needs_two_levels():
+    """the column map's edge values (cs_profile / scalar_profile) read the second layer: npz = 1 would read past the column"""
+    from fv3_jedi_linearmodel_amd._lib import Fv3LmError
+    with pytest.raises(Fv3LmError, match="column map"):
+        Case(nx=8, ny=8, npz=1, backend="emul", oracle=False)
+
+
 def test_split_hord_needs_the_fused_transport(monkeypatch):
     """the values-only trajectory pass exists in the tiled fused fv_tp_2d only: with the staged form forced, create fails loudly"""
     monkeypatch.setenv("FV3LM_TP_FUSED", "0")
