@@ -11,13 +11,15 @@ Workload at N=1 (BASELINE.json configs[3] held by one GPU): the six faces of a C
 sphere (221,184 columns), k_split=2, n_split=6, dt=450 s, 4 tracers, all faces resident on the GPU with
 the table-driven face exchange (--tiles cube, default).  --tiles periodic runs one doubly-periodic C192
 tile (36,864 columns) per rank instead (the kernel-level workload of round 1's first measurements).
-Extra objects on the JSON line: "roofline" (dominant kernel, HIP events on the library's own stream),
-"contract" (whole step against BASELINE.md §3's algorithmic bytes) and "cpu_baseline" (the oracle
-port timed on all host cores, one single-core worker per core, on a bounded sample).
 "ms_per_step" is the wall time of one timed step (--steps of them, after --warmup untimed ones).  --dump-outputs DIR writes what the
 last timed step computed (seeded inputs: the same arrays from run to run, so two builds can be compared output for output).
+A plain run does only that: set-up, warm-up, the timed steps, the dump if asked for, and the JSON line with "contract" (whole step
+against BASELINE.md §3's algorithmic bytes).  --full adds the legs that take runs of their own: "roofline" (dominant kernel, HIP
+events on the library's own stream over one more step; --profile-out writes that step's per-kernel table) and "cpu_baseline" (the
+oracle port and the product's host-emulation build timed on the host cores, on bounded samples; --no-cpu-baseline leaves them out).
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -212,6 +214,57 @@ def default_layout(world):
     return 1 if 6 % world == 0 else 2
 
 
+CUBE_SEED = 20250114
+
+
+def _cube_call(name, args):
+    """Worker side of start_cube_inputs: cube.<name>(*args); cube_fields gets the cube's own geometry (cubed_sphere_metrics) as third argument"""
+    from fv3_jedi_linearmodel_amd import cube
+    if name == "cube_fields":
+        args = args[:2] + (cube.cubed_sphere_metrics(args[0])[5],) + args[2:]
+    return getattr(cube, name)(*args)
+
+
+def _cube_key(name, args):
+    """what identifies a call: its arguments, those of cube_fields (n, npz, geo, seed, kind[, opt]) without the geometry and the options"""
+    return name, (args[:2] + args[3:5] if name == "cube_fields" else args)
+
+
+def start_cube_inputs(n, npz, nq, layout):
+    """Host-side inputs of CubeCase(n, npz, nq, layout, seed=CUBE_SEED) that take long to build and are not needed first -- the synthetic
+    perturbation and tracer fields (cube.cube_fields) and the exchange tables -- started at once in fresh worker processes, so that
+    they are built while this process imports torch, opens the GPU and builds the trajectory fields itself.  Started before torch is
+    imported; the workers never touch the device.  -> (pool, {key: future}) for answered_ahead."""
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    calls = [("cube_fields", (n, npz, CUBE_SEED + 1, "pert"))]
+    if nq:
+        calls.append(("cube_fields", (n, npz, CUBE_SEED + 11, "pert")))
+    calls.append(("all_tables", (n,)) if layout == 1 else ("tiled_tables", (n, layout)))
+    pool = ProcessPoolExecutor(len(calls), mp_context=multiprocessing.get_context("spawn"))
+    return pool, {(name, a): pool.submit(_cube_call, name, a) for name, a in calls}
+
+
+@contextlib.contextmanager
+def answered_ahead(cube, started):
+    """Inside: a call of cube.<name> whose arguments match one of start_cube_inputs' takes that worker's result (the same function on the
+    same arguments, so the same arrays); any other call runs as before."""
+    saved = {name: getattr(cube, name) for name, _ in started}
+
+    def answer(name):
+        def f(*args):
+            fut = started.pop(_cube_key(name, args), None)
+            return fut.result() if fut is not None else saved[name](*args)
+        return f
+    for name in saved:
+        setattr(cube, name, answer(name))
+    try:
+        yield
+    finally:
+        for name, f in saved.items():
+            setattr(cube, name, f)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -234,14 +287,16 @@ def main():
     ap.add_argument("--layout", type=int, default=0,
                     help="tiles per face edge (fv_flags_type%%layout): 1 = whole faces, 2 = 24 sub-face tiles ... Default: 1 where six faces deal out evenly over the GPUs (1, 2, 3, 6), "
                          "else 2 (24 tiles: six per GPU at 4, three at 8 -- six whole faces would leave GPUs idle or half loaded)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beside the headline figure: the roofline step (HIP events per kernel) and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--rehearse-host-transport", action="store_true",
                     help="multi-rank rehearsal on ONE GPU (RCCL refuses two ranks per device): gloo process group, halo messages staged "
                          "through host memory by a transport callback; exercises everything but the RCCL send/recv calls themselves")
     ap.add_argument("--rccl-loopback", action="store_true",
                     help="one GPU: every halo row between two resident tiles travels as a message through ncclSend / ncclRecv on a one-rank communicator "
                          "(the rank as its own peer) instead of the local gather -- the cost of the message path itself, not the headline configuration")
-    ap.add_argument("--profile-out", default="")
+    ap.add_argument("--profile-out", default="", metavar="FILE", help="with --full: the roofline step's per-kernel table")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="one GPU: write what the last timed step computed as DIR/<name>.npy (float64, a fixed seeded sample of each field's compute "
                          "domain, under 64 MB in all): tl_traj_* / tl_pert_* after step_tl (the clock stops while they are copied out), "
@@ -251,6 +306,8 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         ap.error("--dump-outputs is a one-GPU option")
+    if args.profile_out and not args.full:
+        ap.error("--profile-out writes the roofline step of --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process starts N fresh children, one rank per GPU, before anything here has
@@ -272,6 +329,15 @@ def main():
 
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
+    cube_mode = args.tiles == "cube"
+    layout = args.layout if args.layout > 0 else default_layout(world)
+    ntiles = 6 * layout * layout
+    active = True
+    if cube_mode:
+        from fv3_jedi_linearmodel_amd import cube
+        active = len(cube.faces_of(rank, world, ntiles)) > 0
+        if active:
+            pool, started = start_cube_inputs(args.nx, args.npz, args.nq, layout)
     import torch
     dist = None
     if world > 1:
@@ -288,10 +354,7 @@ def main():
     from fv3_jedi_linearmodel_amd.harness import Case, CubeCase, step_state, cube_step_state, cube_nh_state
     lib = fv3.load_hip_library()
     lib.L.fv3lm_set_device(C.c_int(local))
-    cube_mode = args.tiles == "cube"
-    active = True
     if cube_mode:
-        from fv3_jedi_linearmodel_amd import cube
         from fv3_jedi_linearmodel_amd._lib import comm_init_rccl
         if world > 1 and args.rehearse_host_transport:
             import numpy as np
@@ -339,9 +402,6 @@ def main():
         if args.rccl_loopback:
             assert world == 1, "--rccl-loopback is a one-GPU measurement"
             comm_init_rccl(lib, 0, 1, lambda data: data)
-        layout = args.layout if args.layout > 0 else default_layout(world)
-        ntiles = 6 * layout * layout
-        active = len(cube.faces_of(rank, world, ntiles)) > 0
         if active:
             nhkw = dict(hydrostatic=0) if args.nonhydrostatic else {}
             if args.kord_traj:
@@ -352,8 +412,10 @@ def main():
                 nhkw.update(split_damp=1)
             if args.hord_traj:
                 nhkw.update(hord_mt=args.hord_traj, hord_vt=args.hord_traj, hord_tm=args.hord_traj, hord_dp=args.hord_traj, hord_tr=args.hord_traj)
-            c = CubeCase(n=args.nx, npz=args.npz, n_split=args.n_split, k_split=args.k_split, dt=args.dt, backend="hip", nq=args.nq,
-                         rank=rank, world=world, layout=layout, loopback=args.rccl_loopback, **nhkw)
+            with answered_ahead(cube, started):
+                c = CubeCase(n=args.nx, npz=args.npz, n_split=args.n_split, k_split=args.k_split, dt=args.dt, backend="hip", nq=args.nq,
+                             seed=CUBE_SEED, rank=rank, world=world, layout=layout, loopback=args.rccl_loopback, **nhkw)
+            pool.shutdown()
             T, P = cube_step_state(c)
             if args.nonhydrostatic:
                 Tn, Pn = cube_nh_state(c)
@@ -424,19 +486,15 @@ def main():
         cols_rank = args.nx * args.nx
         value = world * cols_rank / (elapsed / args.steps)
 
-    # roofline leg: per-kernel HIP-event durations on the library's stream over one more step
-    if active:
+    prof = None
+    if args.full and active:    # roofline leg: per-kernel HIP-event durations on the library's stream over one more step
         c.dy.profile_begin()
         one_step()
         prof = c.dy.profile_end()
     if rank == 0:
-        dom = max(prof.items(), key=lambda kv: kv[1][1])
-        cnt, ms, by = dom[1]
-        achieved = (by / cnt) / (ms / cnt * 1e-3) / 1e9 if ms > 0 and by > 0 else 0.0
         cells = cols_rank * args.npz
         b_step = algorithmic_bytes(cells, args.k_split, args.n_split, args.nq, args.nonhydrostatic)
         contract_gbps = b_step / (ms_per_step * 1e-3) / 1e9
-        traffic, traffic_src = pmc_traffic(dom[0], args, cube_mode, world)
         out = {
             "metric": "column-updates/s per TL+AD dyn step", "value": value, "unit": "column-updates/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
@@ -448,23 +506,29 @@ def main():
                                                               (", every row between two tiles as an ncclSend / ncclRecv message of the rank to itself (--rccl-loopback)" if args.rccl_loopback else "") if world == 1 else (", halo messages staged through host memory over gloo (rehearsal on one GPU, NOT RCCL)"
                                                                                     if args.rehearse_host_transport else ", RCCL point-to-point between ranks"))) if cube_mode
                                       else "1 doubly-periodic tile per GPU", cols_rank, args.k_split, args.n_split, args.dt, args.nq, scheme_string(c.opt, args.nonhydrostatic)),
-                       "columns_per_gpu": cols_rank, "launches_per_step": sum(v[0] for v in prof.values()),
+                       "columns_per_gpu": cols_rank,
                        "trajectory_slots": "%d of %d acoustic steps keep their intermediates in HBM (no recompute in the backward sweep)"
                                            % (lib.L.fv3lm_traj_slots(c.dy.h), args.n_split * args.k_split)},
-            "roofline": {"bound": "hbm", "kernel": dom[0], "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
-                         "launches_per_step": cnt, "avg_launch_ms": ms / cnt, "algorithmic_bytes_per_launch": by / cnt,
-                         "share_of_step_time": ms / sum(v[1] for v in prof.values()),
-                         # the next kernels by summed time, same accounting (the dominant kernel changed from the tangent to the adjoint
-                         # form of fv_tp_2d when the adjoint became one launch: its fraction is not comparable with earlier rounds' line)
-                         "next": [{"kernel": k, "launches_per_step": v[0], "avg_launch_ms": v[1] / v[0],
-                                   "achieved": (v[2] / 1e9) / (v[1] * 1e-3) if v[1] > 0 else 0.0,
-                                   "frac": ((v[2] / 1e9) / (v[1] * 1e-3) / HBM_PEAK_GBPS) if v[1] > 0 else 0.0}
-                                  for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])[1:4]]},
-            "contract": {"algorithmic_bytes_per_step": b_step, "achieved_GBps": contract_gbps, "frac": contract_gbps / HBM_PEAK_GBPS,
-                         "note": "whole TL+AD step against BASELINE.md §3 (2.75 x B_TL, %d B per cell and acoustic step); state resident in HBM: the host<->device "
-                                 "copies of a drop-in step_tl/step_ad (DESIGN.md §6) are outside the timed region" % (1280 if args.nonhydrostatic else 880)},
         }
+        if prof is not None:
+            dom = max(prof.items(), key=lambda kv: kv[1][1])
+            cnt, ms, by = dom[1]
+            achieved = (by / cnt) / (ms / cnt * 1e-3) / 1e9 if ms > 0 and by > 0 else 0.0
+            traffic, traffic_src = pmc_traffic(dom[0], args, cube_mode, world)
+            out["config"]["launches_per_step"] = sum(v[0] for v in prof.values())
+            out["roofline"] = {"bound": "hbm", "kernel": dom[0], "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
+                               "launches_per_step": cnt, "avg_launch_ms": ms / cnt, "algorithmic_bytes_per_launch": by / cnt,
+                               "share_of_step_time": ms / sum(v[1] for v in prof.values()),
+                               # the next kernels by summed time, same accounting (the dominant kernel changed from the tangent to the adjoint
+                               # form of fv_tp_2d when the adjoint became one launch: its fraction is not comparable with earlier rounds' line)
+                               "next": [{"kernel": k, "launches_per_step": v[0], "avg_launch_ms": v[1] / v[0],
+                                         "achieved": (v[2] / 1e9) / (v[1] * 1e-3) if v[1] > 0 else 0.0,
+                                         "frac": ((v[2] / 1e9) / (v[1] * 1e-3) / HBM_PEAK_GBPS) if v[1] > 0 else 0.0}
+                                        for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])[1:4]]}
+        out["contract"] = {"algorithmic_bytes_per_step": b_step, "achieved_GBps": contract_gbps, "frac": contract_gbps / HBM_PEAK_GBPS,
+                           "note": "whole TL+AD step against BASELINE.md §3 (2.75 x B_TL, %d B per cell and acoustic step); state resident in HBM: the host<->device "
+                                   "copies of a drop-in step_tl/step_ad (DESIGN.md §6) are outside the timed region" % (1280 if args.nonhydrostatic else 880)}
         if args.dump_outputs:
             out["dump_outputs"] = write_dump(args.dump_outputs, dumped)
         if args.profile_out:
@@ -473,7 +537,7 @@ def main():
                 f.write("# kernel launches total_ms avg_ms algorithmic_GB achieved_GBps\n")
                 for k, (n_, m_, b_) in sorted(prof.items(), key=lambda kv: -kv[1][1]):
                     f.write("%-22s %5d %10.3f %8.4f %9.3f %9.1f\n" % (k, n_, m_, m_ / n_, b_ / 1e9, (b_ / 1e9) / (m_ * 1e-3) if m_ > 0 else 0))
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, c.opt)
             except Exception as e:   # the baseline leg must never hide the measurement

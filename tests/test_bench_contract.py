@@ -80,7 +80,28 @@ def test_write_dump_writes_float64_npy(tmp_path):
         assert np.load(str(tmp_path / "d" / (n + ".npy"))).dtype == np.float64
 
 
+def test_cube_inputs_built_ahead_equal_the_case_built_in_place():
+    """start_cube_inputs + answered_ahead: the case gets the same fields and exchange tables as one that builds them itself, every call
+    started ahead is taken, and cube's functions are themselves again afterwards"""
+    import numpy as np
+    from fv3_jedi_linearmodel_amd import cube
+    from fv3_jedi_linearmodel_amd.harness import CubeCase
+    saved = (cube.cube_fields, cube.all_tables, cube.tiled_tables)
+    for layout, nq, kw in ((1, 2, {}), (2, 0, dict(hord_mt=5))):
+        pool, started = bench.start_cube_inputs(24, 8, nq, layout)
+        with bench.answered_ahead(cube, started):
+            a = CubeCase(n=24, npz=8, nq=nq, layout=layout, backend="none", seed=bench.CUBE_SEED, **kw)
+        pool.shutdown()
+        assert not started and (cube.cube_fields, cube.all_tables, cube.tiled_tables) == saved
+        b = CubeCase(n=24, npz=8, nq=nq, layout=layout, backend="none", **kw)
+        for k in ("traj", "pert"):
+            assert all(np.array_equal(getattr(a, k)[f], getattr(b, k)[f]) for f in getattr(b, k))
+        assert all(np.array_equal(x, y) for x, y in zip(a.qtraj + a.qpert, b.qtraj + b.qpert)) and len(a.qtraj) == nq
+        assert np.array_equal(a.phis, b.phis) and np.array_equal(a.ak, b.ak) and np.array_equal(a.bk, b.bk)
+        assert a.tables.keys() == b.tables.keys() and all(np.array_equal(a.tables[k], b.tables[k]) for k in b.tables)
+
+
 def test_bench_rejects_bad_arguments_before_touching_a_gpu():
-    for extra in (["--steps", "0"], ["--gpus", "2", "--dump-outputs", "x"]):
+    for extra in (["--steps", "0"], ["--gpus", "2", "--dump-outputs", "x"], ["--profile-out", "x"]):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True)
         assert p.returncode == 2 and "error" in p.stderr, (extra, p.stderr)
