@@ -19,6 +19,8 @@ module fv3lm_hip_mod
   public :: fv3lm_hip_step_tl, fv3lm_hip_step_ad
   public :: fv3lm_hip_traj_to_fv3, fv3lm_hip_pert_to_fv3, fv3lm_hip_fv3_to_pert
   public :: fv3lm_hip_set_rayleigh, fv3lm_hip_rayleigh_profile
+  public :: fv3lm_hip_turbulence_create, fv3lm_hip_turbulence_set_diagonals, fv3lm_hip_turbulence_set_simple
+  public :: fv3lm_hip_turbulence, fv3lm_hip_turbulence_get
 
   integer, parameter :: ng = 3   ! halo width, tools/fv_mp_nlm_mod.F90:67
 
@@ -165,6 +167,38 @@ module fv3lm_hip_mod
       import :: c_ptr, c_int
       type(c_ptr), value :: h, u, v, t, delp, w, delz
       type(c_ptr), intent(in) :: q(*)
+      integer(c_int) :: rc
+    end function
+    function c_turbulence_create(h, nslots) bind(C, name="fv3lm_turbulence_create") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), value :: nslots
+      integer(c_int) :: rc
+    end function
+    function c_turbulence_set_diagonals(h, slot, diag) bind(C, name="fv3lm_turbulence_set_diagonals") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), value :: slot
+      type(c_ptr), intent(in) :: diag(*)
+      integer(c_int) :: rc
+    end function
+    function c_turbulence_set_simple(h, slot, frocean) bind(C, name="fv3lm_turbulence_set_simple") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h, frocean
+      integer(c_int), value :: slot
+      integer(c_int) :: rc
+    end function
+    function c_turbulence(h, slot, mode) bind(C, name="fv3lm_turbulence") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), value :: slot, mode
+      integer(c_int) :: rc
+    end function
+    function c_turbulence_get(h, slot, out) bind(C, name="fv3lm_turbulence_get") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), value :: slot
+      type(c_ptr), intent(in) :: out(*)
       integer(c_int) :: rc
     end function
     function c_last_error() bind(C, name="fv3lm_last_error") result(p)
@@ -340,6 +374,55 @@ contains
     if (present(delz)) zp = c_loc(delz)
     call check(c_fv3_to_pert(self%handle, c_loc(u), c_loc(v), c_loc(t), c_loc(delp), qp, wp, zp), 'fv3_to_pert')
   end subroutine fv3lm_hip_fv3_to_pert
+
+  !> Linearised boundary-layer turbulence (physics/turbulence/fv3jedi_lm_turbulence_mod.F90).  Slots are numbered from 1 here, like
+  !! ltraj(conf%n) (:66-74); nslots = conf%nt with saveltraj, 1 without.  All arrays are the host's own, (isc:iec, jsc:jec, npz).
+  subroutine fv3lm_hip_turbulence_create(self, nslots)
+    type(fv3lm_hip_type), intent(in) :: self
+    integer, intent(in) :: nslots
+    call check(c_turbulence_create(self%handle, int(nslots, c_int)), 'turbulence_create')
+  end subroutine fv3lm_hip_turbulence_create
+
+  !> In set_ltraj after BL_DRIVER (:482-507), in place of the host's VTRILUPERT (:510-512): the diagonals as BL_DRIVER returns them.
+  !! pk comes from the trajectory delp resident on the device: call after fv3lm_hip_traj_to_fv3 and before the dynamics' step.
+  subroutine fv3lm_hip_turbulence_set_diagonals(self, slot, akv, bkv, ckv, aks, bks, cks, akq, bkq, ckq)
+    type(fv3lm_hip_type), intent(in) :: self
+    integer, intent(in) :: slot
+    real(c_double), intent(in), target, contiguous :: akv(:, :, :), bkv(:, :, :), ckv(:, :, :), aks(:, :, :), bks(:, :, :), cks(:, :, :)
+    real(c_double), intent(in), target, contiguous :: akq(:, :, :), bkq(:, :, :), ckq(:, :, :)
+    type(c_ptr) :: d(9)
+    d = [c_loc(akv), c_loc(bkv), c_loc(ckv), c_loc(aks), c_loc(bks), c_loc(cks), c_loc(akq), c_loc(bkq), c_loc(ckq)]
+    call check(c_turbulence_set_diagonals(self%handle, int(slot - 1, c_int), d), 'turbulence_set_diagonals')
+  end subroutine fv3lm_hip_turbulence_set_diagonals
+
+  !> The diagonals from BL_simp (turbulence/blsimp.F90) on the device, from the resident trajectory and traj%frocean(isc:iec, jsc:jec).
+  subroutine fv3lm_hip_turbulence_set_simple(self, slot, frocean)
+    type(fv3lm_hip_type), intent(in) :: self
+    integer, intent(in) :: slot
+    real(c_double), intent(in), target, contiguous :: frocean(:, :)
+    call check(c_turbulence_set_simple(self%handle, int(slot - 1, c_int), c_loc(frocean)), 'turbulence_set_simple')
+  end subroutine fv3lm_hip_turbulence_set_simple
+
+  !> mode 0: step_nl (:151-214) on the trajectory; 1: step_tl (:218-282) after fv3lm_hip_step_tl; 2: step_ad (:286-350) before
+  !! fv3lm_hip_step_ad.  In place of the seven VTRISOLVEPERT calls and the T <-> theta conversions around them.
+  subroutine fv3lm_hip_turbulence(self, slot, mode)
+    type(fv3lm_hip_type), intent(in) :: self
+    integer, intent(in) :: slot, mode
+    call check(c_turbulence(self%handle, int(slot - 1, c_int), int(mode, c_int)), 'turbulence')
+  end subroutine fv3lm_hip_turbulence
+
+  !> fac(:, :, :, 1:9) the LU factors in the order of set_diagonals, fac(:, :, :, 10) pk (diagnostics)
+  subroutine fv3lm_hip_turbulence_get(self, slot, fac)
+    type(fv3lm_hip_type), intent(in) :: self
+    integer, intent(in) :: slot
+    real(c_double), intent(inout), target, contiguous :: fac(:, :, :, :)
+    type(c_ptr) :: d(10)
+    integer :: n
+    do n = 1, 10
+      d(n) = c_loc(fac(1, 1, 1, n))
+    end do
+    call check(c_turbulence_get(self%handle, int(slot - 1, c_int), d), 'turbulence_get')
+  end subroutine fv3lm_hip_turbulence_get
 
   !> Replaces compute_fv3_pressures_tlm + fv_dynamics_tlm (fv3jedi_lm_dynamics_mod.F90:404-438).
   subroutine fv3lm_hip_step_tl(self)

@@ -237,6 +237,47 @@ class Dycore:
         self.lib.L.fv3lm_rayleigh.argtypes = [C.c_void_p, C.c_int]
         self._chk(self.lib.L.fv3lm_rayleigh(self.h, mode))
 
+    # ---- linearised boundary-layer turbulence (fv3jedi_lm_turbulence_mod.F90; csrc/turbulence.h), compact arrays [ntile, npz, ny, nx] ----
+    def _compact(self, a, nk=None):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        want = (self.dims.ntile,) + ((nk,) if nk else ()) + (self.dims.ny, self.dims.nx)
+        assert a.shape == want, (a.shape, want)
+        return a
+
+    def turbulence_create(self, nslots=1):
+        """fv3lm_turbulence_create: nslots x (9 factor arrays + pk) on the device (one slot per trajectory time kept)"""
+        self.lib.L.fv3lm_turbulence_create.argtypes = [C.c_void_p, C.c_int]
+        self._chk(self.lib.L.fv3lm_turbulence_create(self.h, int(nslots)))
+
+    def turbulence_set_diagonals(self, slot, diag):
+        """diag: AKV BKV CKV AKS BKS CKS AKQ BKQ CKQ (lower, main, upper; before the LU factorisation), nine compact arrays or None.
+        pk is taken from the resident trajectory delp at this call: call after traj_to_fv3, before step_tl / step_nl."""
+        if diag is None or len(diag) != 9:
+            raise Fv3LmError("turbulence_set_diagonals: nine arrays needed")
+        keep = [None if a is None else self._compact(a, self.dims.npz) for a in diag]
+        ptrs = (_dp * 9)(*[None if a is None else _ptr(a) for a in keep])
+        self.lib.L.fv3lm_turbulence_set_diagonals.argtypes = [C.c_void_p, C.c_int, C.POINTER(_dp)]
+        self._chk(self.lib.L.fv3lm_turbulence_set_diagonals(self.h, int(slot), ptrs))
+
+    def turbulence_set_simple(self, slot, frocean):
+        """BL_simp (blsimp.F90) on the device from the resident trajectory; frocean compact [ntile, ny, nx] (None: NULL)"""
+        a = None if frocean is None else self._compact(frocean)
+        self.lib.L.fv3lm_turbulence_set_simple.argtypes = [C.c_void_p, C.c_int, _dp]
+        self._chk(self.lib.L.fv3lm_turbulence_set_simple(self.h, int(slot), None if a is None else _ptr(a)))
+
+    def turbulence(self, slot, mode):
+        """the seven solves of a slot: NL on the trajectory, TL on the perturbation, AD the transposed sweeps on the adjoint"""
+        self.lib.L.fv3lm_turbulence.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        self._chk(self.lib.L.fv3lm_turbulence(self.h, int(slot), int(mode)))
+
+    def turbulence_get(self, slot):
+        """-> [10, ntile, npz, ny, nx]: the LU factors in the order of turbulence_set_diagonals, then pk"""
+        out = np.empty((10, self.dims.ntile, self.dims.npz, self.dims.ny, self.dims.nx))
+        ptrs = (_dp * 10)(*[_ptr(out[n]) for n in range(10)])
+        self.lib.L.fv3lm_turbulence_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(_dp)]
+        self._chk(self.lib.L.fv3lm_turbulence_get(self.h, int(slot), ptrs))
+        return out
+
     # ---- the host's boundary copies on the device (compact arrays [ntile, nk, ny, nx], no halo) ----
     def _cptrs(self, d, names, out=False):
         keep = []

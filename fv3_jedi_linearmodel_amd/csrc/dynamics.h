@@ -6,6 +6,7 @@
 #include "dycore.h"
 #include "remap.h"
 #include "rayleigh.h"
+#include "turbulence.h"
 
 namespace fv3 {
 
@@ -148,6 +149,17 @@ struct Dynamics : Dycore {
   bool set_rayleigh(double tau, double rf_cutoff, const double* c2l);
   RfArgs rf_args();
   void rayleigh(int mode);
+  // Linearised boundary-layer turbulence (turbulence.h; fv3lm_turbulence_*): nothing allocated until turb_create
+  struct Turbulence { int nslots = 0; std::vector<double*> slot; std::vector<char> set; double* fro = nullptr; int* flag = nullptr; } turb;
+  bool turb_create(int nslots);
+  bool turb_slot_ok(const char* who, int slot);
+  TurbArgs turb_args(int slot);
+  bool turb_factorise(const char* who, int slot);
+  bool turb_set_diagonals(int slot, const double* const* diag);
+  bool turb_set_simple(int slot, const double* frocean);
+  bool turb_run(int slot, int mode);
+  bool turb_get(int slot, double* const* out);
+  void turb_destroy();
   // one field between the host's compact array and the device state.  which: 0 trajectory, 1 perturbation / adjoint
   void compact_in(const Fld& f, int which, const double* host) {
     const size_t n = (size_t)ntile_all * f.nk * g.tx * g.ty;
@@ -262,6 +274,7 @@ inline bool Dynamics::init2(const double* ak, const double* bk) {
 }
 inline void Dynamics::destroy2() {
   dev_free(stage_dev); stage_dev = nullptr;
+  turb_destroy();
   dev_free(rf_lv); dev_free(rf_c2l); dev_free(rf_ck); dev_free(rf_pth.t); dev_free(rf_pth.p);
   dev_free(ak_dev); dev_free(bk_dev); if (remap_ws_own) dev_free(remap_ws); dev_free(cmax_dev); dev_free(ck_k); dev_free(ck_0); dev_free(ck_nh);
   tshared.destroy(); twork.destroy();
@@ -658,6 +671,92 @@ inline void Dynamics::rayleigh(int mode) {
     for_points(ex, E, nz, RfHeatFn{a, mode}, mode == MODE_NL ? "rayleigh_heat.nl" : "rayleigh_heat.tl");
     for_points(ex, E, nz, RfDampFn{a, mode}, mode == MODE_NL ? "rayleigh_damp.nl" : "rayleigh_damp.tl");
   });
+}
+
+// ---- linearised boundary-layer turbulence (turbulence.h) -------------------------------------------------------------------------------
+// fv3lm_turbulence_create: nslots x (9 factor arrays + pk), padded planes
+inline bool Dynamics::turb_create(int nslots) {
+  if (turb.nslots > 0) { err = "fv3lm_turbulence_create: already created for this handle"; return false; }
+  if (nslots < 1) { err = "fv3lm_turbulence_create: nslots < 1"; return false; }
+  if (g.npz < 2) { err = "fv3lm_turbulence_create: npz < 2 (a tridiagonal system needs two levels)"; return false; }
+  const size_t bytes = (size_t)TURB_NARR * n3 * 8;
+  if (std::getenv("FV3LM_VERBOSE")) std::fprintf(stderr, "fv3lm: turbulence arena %d slot(s) x %d arrays x %zu doubles = %zu bytes\n", nslots, TURB_NARR, n3, (size_t)nslots * bytes);
+  const bool clean = sticky_error().empty();
+  for (int n = 0; n < nslots; ++n) turb.slot.push_back((double*)dev_alloc(bytes));
+  turb.fro = (double*)dev_alloc((size_t)ntile_all * g.plane * 8); turb.flag = (int*)dev_alloc(8);
+  bool ok = turb.fro && turb.flag;
+  for (double* p : turb.slot) ok = ok && p;
+  if (!ok) {      // a refusal: what was allocated goes back, the handle stays usable
+    err = "fv3lm_turbulence_create: allocation of " + std::to_string((size_t)nslots * bytes) + " bytes failed" + (sticky_error().empty() ? std::string() : ": " + sticky_error());
+    if (clean) sticky_error().clear();
+    turb_destroy();
+    return false;
+  }
+  turb.set.assign((size_t)nslots, 0); turb.nslots = nslots;
+  return true;
+}
+inline void Dynamics::turb_destroy() {
+  for (double* p : turb.slot) dev_free(p);
+  dev_free(turb.fro); dev_free(turb.flag);
+  turb = Turbulence{};
+}
+inline bool Dynamics::turb_slot_ok(const char* who, int slot) {
+  if (turb.nslots == 0) { err = std::string(who) + ": call fv3lm_turbulence_create first"; return false; }
+  if (slot < 0 || slot >= turb.nslots) { err = std::string(who) + ": slot " + std::to_string(slot) + " out of range (0.." + std::to_string(turb.nslots - 1) + ")"; return false; }
+  return true;
+}
+inline TurbArgs Dynamics::turb_args(int slot) {      // inside each_class
+  TurbArgs a; a.g = g;
+  a.u = ex.sh(f("u")); a.v = ex.sh(f("v")); a.pt = ex.sh(f("pt")); a.delp = ex.sh(f("delp"));
+  a.nq = nq;
+  for (int n = 0; n < nq; ++n) a.q[n] = ex.sh(q[(size_t)n]);
+  a.fac = turb.slot[(size_t)slot] + ex.cls_off * g.npz; a.fs = n3;
+  a.fro = turb.fro + ex.cls_off; a.flag = turb.flag;
+  a.ptop = opt.ptop; a.akap = opt.akap; a.p00k = std::pow(1.0e5, opt.akap);
+  a.dt = bdt; a.grav = opt.grav_jedi; a.cp = opt.cp; a.zvir = opt.zvir;
+  return a;
+}
+// VTRILUPERT of the slot's three systems and pk from the resident trajectory delp; a bad pivot is reported here, by one flag
+inline bool Dynamics::turb_factorise(const char* who, int slot) {
+  dev_zero(ex, turb.flag, 8);
+  each_class([&]() { run_turb_factorise(ex, turb_args(slot)); });
+  int flag = 0;
+  d2h(ex, &flag, turb.flag, sizeof flag);
+  turb.set[(size_t)slot] = flag ? 0 : 1;
+  if (flag) { err = std::string(who) + ": the factorisation of a main diagonal gave a zero or non-finite pivot (slot " + std::to_string(slot) + " is not set)"; return false; }
+  return true;
+}
+inline bool Dynamics::turb_set_diagonals(int slot, const double* const* diag) {
+  if (!turb_slot_ok("fv3lm_turbulence_set_diagonals", slot)) return false;
+  if (!diag) { err = "fv3lm_turbulence_set_diagonals: null array"; return false; }
+  for (int n = 0; n < 9; ++n) if (!diag[n]) { err = "fv3lm_turbulence_set_diagonals: null array"; return false; }      // before anything is touched
+  turb.set[(size_t)slot] = 0;
+  for (int n = 0; n < 9; ++n) { Fld d; d.t = turb.slot[(size_t)slot] + (size_t)n * n3; d.nk = g.npz; compact_in(d, 0, diag[n]); }
+  return turb_factorise("fv3lm_turbulence_set_diagonals", slot);
+}
+inline bool Dynamics::turb_set_simple(int slot, const double* frocean) {
+  if (!turb_slot_ok("fv3lm_turbulence_set_simple", slot)) return false;
+  if (nq < 3) { err = "fv3lm_turbulence_set_simple: nq < 3 (BL_simp reads qv, ql, qi = q1, q2, q3)"; return false; }
+  if (!frocean) { err = "fv3lm_turbulence_set_simple: null array"; return false; }
+  turb.set[(size_t)slot] = 0;
+  { Fld d; d.t = turb.fro; d.nk = 1; compact_in(d, 0, frocean); }
+  each_class([&]() { run_turb_simple(ex, turb_args(slot)); });
+  return turb_factorise("fv3lm_turbulence_set_simple", slot);
+}
+inline bool Dynamics::turb_run(int slot, int mode) {
+  if (!turb_slot_ok("fv3lm_turbulence", slot)) return false;
+  if (mode < 0 || mode > 2) { err = "fv3lm_turbulence: bad mode"; return false; }
+  if (!turb.set[(size_t)slot]) { err = "fv3lm_turbulence: slot " + std::to_string(slot) + " was never set (fv3lm_turbulence_set_diagonals / _set_simple)"; return false; }
+  each_class([&]() { run_turb_solve(ex, mode, turb_args(slot)); });
+  return true;
+}
+inline bool Dynamics::turb_get(int slot, double* const* out) {
+  if (!turb_slot_ok("fv3lm_turbulence_get", slot)) return false;
+  if (!turb.set[(size_t)slot]) { err = "fv3lm_turbulence_get: slot " + std::to_string(slot) + " was never set"; return false; }
+  if (!out) { err = "fv3lm_turbulence_get: null array"; return false; }
+  for (int n = 0; n < TURB_NARR; ++n) if (!out[n]) { err = "fv3lm_turbulence_get: null array"; return false; }
+  for (int n = 0; n < TURB_NARR; ++n) { Fld d; d.t = turb.slot[(size_t)slot] + (size_t)n * n3; d.nk = g.npz; compact_out(d, 0, out[n]); }
+  return true;
 }
 
 }  // namespace fv3

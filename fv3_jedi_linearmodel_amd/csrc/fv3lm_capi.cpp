@@ -193,6 +193,32 @@ int fv3lm_rayleigh(fv3lm_handle* h, int mode) {
   h->d.rayleigh(mode);
   return status(h);
 }
+// linearised boundary-layer turbulence (turbulence.h)
+int fv3lm_turbulence_create(fv3lm_handle* h, int nslots) {
+  if (!h) return fail("fv3lm_turbulence_create: null handle");
+  if (!h->d.turb_create(nslots)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_turbulence_set_diagonals(fv3lm_handle* h, int slot, const double* const* diag) {
+  if (!h) return fail("fv3lm_turbulence_set_diagonals: null handle");
+  if (!h->d.turb_set_diagonals(slot, diag)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_turbulence_set_simple(fv3lm_handle* h, int slot, const double* frocean) {
+  if (!h) return fail("fv3lm_turbulence_set_simple: null handle");
+  if (!h->d.turb_set_simple(slot, frocean)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_turbulence(fv3lm_handle* h, int slot, int mode) {
+  if (!h) return fail("fv3lm_turbulence: null handle");
+  if (!h->d.turb_run(slot, mode)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_turbulence_get(fv3lm_handle* h, int slot, double* const* out) {
+  if (!h) return fail("fv3lm_turbulence_get: null handle");
+  if (!h->d.turb_get(slot, out)) return fail(h->d.err);
+  return status(h);
+}
 int fv3lm_step_tl(fv3lm_handle* h) { h->d.step_tl(); return status(h); }
 int fv3lm_step_nl(fv3lm_handle* h) { h->d.step_nl(); return status(h); }
 int fv3lm_step_ad(fv3lm_handle* h) { h->d.step_ad(); return status(h); }

@@ -187,6 +187,33 @@ int fv3lm_fv_dynamics(fv3lm_handle* h, int mode);               /* FV_DYNAMICS_T
 int fv3lm_rayleigh(fv3lm_handle* h, int mode);                  /* RAYLEIGH_SUPER_TLM fv_dynamics_tlm.F90:1749 / _FWD+_BWD fv_dynamics_adm.F90:2327-2652
                                                                    on u v pt (w); non-hydrostatic: the heated temperature goes to field "rf_pt",
                                                                    pt keeps the one pt_in takes pkz from.  Adjoint: after a MODE_NL call */
+/* Linearised boundary-layer turbulence (physics/turbulence/fv3jedi_lm_turbulence_mod.F90, do_phy_trb): a vertical diffusion of the
+ * perturbation with coefficients frozen on the trajectory, seven tridiagonal solves per column -- u, v on the V system, T (as potential
+ * temperature p00^kappa T / pk) on S, q1 on Q with ygswitch = 1 and q2 .. q_nq on Q with ygswitch = 0 (step_tl :258-269).  Column-local:
+ * only is..ie x js..je of every resident tile is read or written; the far edge rows u(:, je+1), v(ie+1, :), every halo, delp, w and
+ * delz are not touched.  Arrays are COMPACT, (isc:iec, jsc:jec, npz) per resident tile, tile slowest, like those of fv3lm_traj_to_fv3.
+ *   fv3lm_turbulence_create: nslots = one per trajectory time the host keeps (saveltraj ? conf%nt : 1; ltraj(conf%n) :66-74).
+ *       Allocates nslots x 10 x ntile x npz x pj x pi x 8 bytes on the device (FV3LM_VERBOSE=1 prints it); freed by fv3lm_destroy.
+ *       Refused: a second create on the handle, nslots < 1, npz < 2, an allocation that fails.
+ *   fv3lm_turbulence_set_diagonals: diag[9] = AKV BKV CKV AKS BKS CKS AKQ BKQ CKQ (lower, main, upper) as BL_DRIVER returns them,
+ *       BEFORE VTRILUPERT (:510-512): the device factorises (b(1) = 1/b(1); a(l) = a(l) b(l-1), b(l) = 1/(b(l) - c(l-1) a(l))).
+ *       Refused with the slot left unset: a pivot that is zero or a factor that is not finite.
+ *   fv3lm_turbulence_set_simple: the diagonals from BL_simp (turbulence/blsimp.F90) evaluated on the device from the resident
+ *       trajectory (u, v at (i, j), PTT = T / pk, PKT = pk, qv ql qi = q1 q2 q3, JEDI constants of the options) and frocean
+ *       (isc:iec, jsc:jec) per tile; needs nq >= 3.
+ *   Both take pk (compute_pressures, utils/fv3jedi_lm_utils_mod.F90:359-391) from the RESIDENT TRAJECTORY delp AT THE CALL, and a slot
+ *   keeps what its set call saw.  The reference's turbulence uses the trajectory at the start of the step, and fv3lm_step_tl /
+ *   fv3lm_step_nl advance the resident trajectory: call set_* after fv3lm_traj_to_fv3 and BEFORE fv3lm_step_tl / fv3lm_step_nl.
+ *   fv3lm_turbulence: mode 0 the solves on the trajectory (step_nl :151-214), 1 on the perturbation (step_tl), 2 the adjoint
+ *       (step_ad :286-350: the transposed sweeps).  The operator order is the host's, as in fv3jedi_lm_mod.F90:161-187:
+ *       tangent  fv3lm_step_tl ; fv3lm_turbulence(h, slot, 1)      adjoint  fv3lm_turbulence(h, slot, 2) ; fv3lm_step_ad.
+ *       Refused: before create, slot out of range, a slot never set, a mode outside 0..2.
+ *   fv3lm_turbulence_get: out[10] = the LU factors in the order of diag (A the multipliers, B the inverse pivots, C unchanged) and pk. */
+int fv3lm_turbulence_create(fv3lm_handle* h, int nslots);
+int fv3lm_turbulence_set_diagonals(fv3lm_handle* h, int slot, const double* const* diag);
+int fv3lm_turbulence_set_simple(fv3lm_handle* h, int slot, const double* frocean);
+int fv3lm_turbulence(fv3lm_handle* h, int slot, int mode);
+int fv3lm_turbulence_get(fv3lm_handle* h, int slot, double* const* out);
 /* Per-kernel HIP-event profile of everything launched between begin and end, on the library's stream:
  * lines "kernel count total_ms algorithmic_bytes".  Returns the buffer length needed. */
 int fv3lm_profile_begin(fv3lm_handle* h);
