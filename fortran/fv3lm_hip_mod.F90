@@ -21,6 +21,7 @@ module fv3lm_hip_mod
   public :: fv3lm_hip_set_rayleigh, fv3lm_hip_rayleigh_profile
   public :: fv3lm_hip_turbulence_create, fv3lm_hip_turbulence_set_diagonals, fv3lm_hip_turbulence_set_simple
   public :: fv3lm_hip_turbulence, fv3lm_hip_turbulence_get
+  public :: fv3lm_bl_params, fv3lm_hip_bl_default_params, fv3lm_hip_turbulence_set_driver
 
   integer, parameter :: ng = 3   ! halo width, tools/fv_mp_nlm_mod.F90:67
 
@@ -52,6 +53,12 @@ module fv3lm_hip_mod
     integer(c_int) :: nface = 0, pad_ = 0
     type(c_ptr) :: tile_ij0 = c_null_ptr
   end type fv3lm_dims
+
+  !> TURBPARAMS(22), TURBPARAMSI(4) of BL_DRIVER in the reference's order (fv3lm_bl_params of include/fv3lm.h)
+  type, bind(C) :: fv3lm_bl_params
+    real(c_double) :: r(22)
+    integer(c_int) :: i(4)
+  end type fv3lm_bl_params
 
   type :: fv3lm_hip_type
     type(c_ptr) :: handle = c_null_ptr
@@ -199,6 +206,20 @@ module fv3lm_hip_mod
       type(c_ptr), value :: h
       integer(c_int), value :: slot
       type(c_ptr), intent(in) :: out(*)
+      integer(c_int) :: rc
+    end function
+    subroutine c_bl_default_params(p, kpblmin) bind(C, name="fv3lm_bl_default_params")
+      import :: fv3lm_bl_params, c_int
+      type(fv3lm_bl_params), intent(out) :: p
+      integer(c_int), value :: kpblmin
+    end subroutine
+    function c_turbulence_set_driver(h, slot, p, dt, sfc, qa, qb, cloud_mode, raw_out) bind(C, name="fv3lm_turbulence_set_driver") result(rc)
+      import :: fv3lm_bl_params, c_ptr, c_int, c_double
+      type(c_ptr), value :: h, qa, qb, raw_out
+      integer(c_int), value :: slot, cloud_mode
+      type(fv3lm_bl_params), intent(in) :: p
+      real(c_double), value :: dt
+      type(c_ptr), intent(in) :: sfc(*)
       integer(c_int) :: rc
     end function
     function c_last_error() bind(C, name="fv3lm_last_error") result(p)
@@ -402,6 +423,30 @@ contains
     real(c_double), intent(in), target, contiguous :: frocean(:, :)
     call check(c_turbulence_set_simple(self%handle, int(slot - 1, c_int), c_loc(frocean)), 'turbulence_set_simple')
   end subroutine fv3lm_hip_turbulence_set_simple
+
+  !> TURBPARAMS / TURBPARAMSI as documented at bldriver.F90:100-127 (the reference never assigns lcnst%TURBPARAMS: they are the host's);
+  !! kpblmin = count(PREF < 50000.).
+  subroutine fv3lm_hip_bl_default_params(p, kpblmin)
+    type(fv3lm_bl_params), intent(out) :: p
+    integer, intent(in) :: kpblmin
+    call c_bl_default_params(p, int(kpblmin, c_int))
+  end subroutine fv3lm_hip_bl_default_params
+
+  !> In set_ltraj in place of compute_pressures, PTT1, the IceFraction split, BL_DRIVER and the three VTRILUPERT (:439-512): the
+  !! diagonals from the trajectory resident on the device.  Call after fv3lm_hip_traj_to_fv3 and before the dynamics' step.
+  !! qa, qb: traj%QI, traj%QL (cloud_mode 0, do_phy_mst == 0) or traj%QLS, traj%QCN (cloud_mode 1), (isc:iec, jsc:jec, npz).
+  subroutine fv3lm_hip_turbulence_set_driver(self, slot, p, dt, frland, frocean, varflt, zpbl, cm, ct, cq, ustar, bstar, qa, qb, cloud_mode)
+    type(fv3lm_hip_type), intent(in) :: self
+    integer, intent(in) :: slot, cloud_mode
+    type(fv3lm_bl_params), intent(in) :: p
+    real(c_double), intent(in) :: dt
+    real(c_double), intent(in), target, contiguous :: frland(:, :), frocean(:, :), varflt(:, :), zpbl(:, :), cm(:, :), ct(:, :), cq(:, :)
+    real(c_double), intent(in), target, contiguous :: ustar(:, :), bstar(:, :), qa(:, :, :), qb(:, :, :)
+    type(c_ptr) :: s(9)
+    s = [c_loc(frland), c_loc(frocean), c_loc(varflt), c_loc(zpbl), c_loc(cm), c_loc(ct), c_loc(cq), c_loc(ustar), c_loc(bstar)]
+    call check(c_turbulence_set_driver(self%handle, int(slot - 1, c_int), p, dt, s, c_loc(qa), c_loc(qb), int(cloud_mode, c_int), c_null_ptr), &
+               'turbulence_set_driver')
+  end subroutine fv3lm_hip_turbulence_set_driver
 
   !> mode 0: step_nl (:151-214) on the trajectory; 1: step_tl (:218-282) after fv3lm_hip_step_tl; 2: step_ad (:286-350) before
   !! fv3lm_hip_step_ad.  In place of the seven VTRISOLVEPERT calls and the T <-> theta conversions around them.

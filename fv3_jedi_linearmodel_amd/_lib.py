@@ -17,6 +17,11 @@ class Fv3LmError(RuntimeError):
     pass
 
 
+class BlParams(C.Structure):
+    """fv3lm_bl_params: TURBPARAMS(22), TURBPARAMSI(4) of BL_DRIVER in the reference's order"""
+    _fields_ = [("r", C.c_double * 22), ("i", C.c_int * 4)]
+
+
 class Fv3LmLibrary:
     def __init__(self, path):
         if not os.path.exists(path):
@@ -264,6 +269,42 @@ class Dycore:
         a = None if frocean is None else self._compact(frocean)
         self.lib.L.fv3lm_turbulence_set_simple.argtypes = [C.c_void_p, C.c_int, _dp]
         self._chk(self.lib.L.fv3lm_turbulence_set_simple(self.h, int(slot), None if a is None else _ptr(a)))
+
+    def bl_default_params(self, kpblmin):
+        """fv3lm_bl_default_params: the TURBPARAMS / TURBPARAMSI documented at bldriver.F90:100-127; KPBLMIN = count(PREF < 50000) is the caller's"""
+        p = BlParams()
+        self.lib.L.fv3lm_bl_default_params.argtypes = [C.POINTER(BlParams), C.c_int]
+        self.lib.L.fv3lm_bl_default_params.restype = None
+        self.lib.L.fv3lm_bl_default_params(C.byref(p), int(kpblmin))
+        return p
+
+    SFC_NAMES = ("FRLAND", "FROCEAN", "VARFLT", "ZPBL", "CM", "CT", "CQ", "USTAR", "BSTAR")
+    RAW_NAMES = ("AKV", "BKV", "CKV", "AKS", "BKS", "CKS", "AKQ", "BKQ", "CKQ", "EKV", "FKV", "ZPBL", "CT")
+
+    def turbulence_set_driver(self, slot, params, dt, sfc, qa=None, qb=None, cloud_mode=0, raw=False):
+        """BL_DRIVER (bldriver.F90) on the device from the resident trajectory, then the factorisation.  sfc: the nine surface fields
+        in the order of SFC_NAMES (a dict by these names or a sequence; an entry None: NULL), compact [ntile, ny, nx]; qa, qb: QI, QL
+        (cloud_mode 0) or QLS, QCN (cloud_mode 1), compact [ntile, npz, ny, nx] or None.  raw=True -> dict by RAW_NAMES of what BL_DRIVER
+        left before the factorisation."""
+        if isinstance(sfc, dict):
+            sfc = [sfc.get(n) for n in self.SFC_NAMES]
+        ptrs = None
+        if sfc is not None:
+            if len(sfc) != 9:
+                raise Fv3LmError("turbulence_set_driver: nine surface arrays needed")
+            keep = [None if a is None else self._compact(a) for a in sfc]
+            ptrs = (_dp * 9)(*[None if a is None else _ptr(a) for a in keep])
+        q = [None if a is None else self._compact(a, self.dims.npz) for a in (qa, qb)]
+        out, optrs = None, None
+        if raw:
+            shp = (self.dims.ntile, self.dims.npz, self.dims.ny, self.dims.nx)
+            out = {n: np.empty(shp if k < 11 else (shp[0],) + shp[2:]) for k, n in enumerate(self.RAW_NAMES)}
+            optrs = (_dp * 13)(*[_ptr(out[n]) for n in self.RAW_NAMES])
+        f = self.lib.L.fv3lm_turbulence_set_driver
+        f.argtypes = [C.c_void_p, C.c_int, C.POINTER(BlParams), C.c_double, C.POINTER(_dp), _dp, _dp, C.c_int, C.POINTER(_dp)]
+        self._chk(f(self.h, int(slot), None if params is None else C.byref(params), float(dt), ptrs, None if q[0] is None else _ptr(q[0]),
+                    None if q[1] is None else _ptr(q[1]), int(cloud_mode), optrs))
+        return out
 
     def turbulence(self, slot, mode):
         """the seven solves of a slot: NL on the trajectory, TL on the perturbation, AD the transposed sweeps on the adjoint"""

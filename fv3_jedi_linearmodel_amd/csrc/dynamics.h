@@ -7,6 +7,7 @@
 #include "remap.h"
 #include "rayleigh.h"
 #include "turbulence.h"
+#include "bldriver.h"
 
 namespace fv3 {
 
@@ -150,13 +151,17 @@ struct Dynamics : Dycore {
   RfArgs rf_args();
   void rayleigh(int mode);
   // Linearised boundary-layer turbulence (turbulence.h; fv3lm_turbulence_*): nothing allocated until turb_create
-  struct Turbulence { int nslots = 0; std::vector<double*> slot; std::vector<char> set; double* fro = nullptr; int* flag = nullptr; } turb;
+  struct Turbulence {
+    int nslots = 0; std::vector<double*> slot; std::vector<char> set; double* fro = nullptr; int* flag = nullptr;
+    double *bl_sfc = nullptr, *bl_tbl = nullptr, *bl_raw = nullptr;      // BL_DRIVER (bldriver.h): surface planes and table at its first call, EKV FKV at the first raw_out
+  } turb;
   bool turb_create(int nslots);
   bool turb_slot_ok(const char* who, int slot);
   TurbArgs turb_args(int slot);
   bool turb_factorise(const char* who, int slot);
   bool turb_set_diagonals(int slot, const double* const* diag);
   bool turb_set_simple(int slot, const double* frocean);
+  bool turb_set_driver(int slot, const BlParams* p, double dt, const double* const* sfc, const double* qa, const double* qb, int cloud_mode, double* const* raw_out);
   bool turb_run(int slot, int mode);
   bool turb_get(int slot, double* const* out);
   void turb_destroy();
@@ -697,7 +702,7 @@ inline bool Dynamics::turb_create(int nslots) {
 }
 inline void Dynamics::turb_destroy() {
   for (double* p : turb.slot) dev_free(p);
-  dev_free(turb.fro); dev_free(turb.flag);
+  dev_free(turb.fro); dev_free(turb.flag); dev_free(turb.bl_sfc); dev_free(turb.bl_tbl); dev_free(turb.bl_raw);
   turb = Turbulence{};
 }
 inline bool Dynamics::turb_slot_ok(const char* who, int slot) {
@@ -742,6 +747,61 @@ inline bool Dynamics::turb_set_simple(int slot, const double* frocean) {
   { Fld d; d.t = turb.fro; d.nk = 1; compact_in(d, 0, frocean); }
   each_class([&]() { run_turb_simple(ex, turb_args(slot)); });
   return turb_factorise("fv3lm_turbulence_set_simple", slot);
+}
+// BL_DRIVER on the resident trajectory (bldriver.h): the column's work vectors go through the slot's own planes, the nine diagonals
+// replace them, then the factorisation as after set_diagonals.  Every refusal stands before anything of the slot is touched, except
+// the parcel that never stops, which only the kernel can see: the slot is then left unset like after a zero pivot.
+inline bool Dynamics::turb_set_driver(int slot, const BlParams* p, double dt, const double* const* sfc, const double* qa, const double* qb, int cloud_mode,
+                                      double* const* raw_out) {
+  const char* who = "fv3lm_turbulence_set_driver";
+  auto no = [&](const std::string& m) { err = std::string(who) + ": " + m; return false; };
+  if (!turb_slot_ok(who, slot)) return false;
+  if (g.npz < 7) return no("npz < 7 (BL_DRIVER smooths the bottom six levels against the seventh)");
+  if (nq < 1) return no("nq < 1 (BL_DRIVER reads qv = q1)");
+  if (!p) return no("null parameters");
+  if (p->i[0] < 1 || p->i[0] > g.npz) return no("KPBLMIN = " + std::to_string(p->i[0]) + " outside 1.." + std::to_string(g.npz));
+  if (p->i[3] != 0) return no("RADLW_DEP != 0 (the reference reads an uninitialised RADLW there)");
+  if (turb_stored_nonfinite(&dt) || dt <= 0.) return no("dt <= 0 or not finite");
+  if (cloud_mode < 0 || cloud_mode > 1) return no("cloud_mode outside 0..1");
+  if (!sfc) return no("null array");
+  for (int n = 0; n < BL_NSFC; ++n) if (!sfc[n]) return no("null array");
+  if (raw_out) for (int n = 0; n < 13; ++n) if (!raw_out[n]) return no("null array in raw_out");
+  const size_t ss = (size_t)ntile_all * g.plane;
+  const bool clean = sticky_error().empty();
+  if (!turb.bl_tbl) {
+    turb.bl_tbl = (double*)dev_alloc((size_t)blc::TABLESIZE * 8);
+    if (turb.bl_tbl) { const std::vector<double> x = bl_esinit(); h2d(ex, turb.bl_tbl, x.data(), x.size() * 8); }
+  }
+  if (!turb.bl_sfc) turb.bl_sfc = (double*)dev_alloc(BL_NSFC * ss * 8);
+  if (raw_out && !turb.bl_raw) turb.bl_raw = (double*)dev_alloc(2 * n3 * 8);
+  if (!turb.bl_tbl || !turb.bl_sfc || (raw_out && !turb.bl_raw)) {
+    if (clean) sticky_error().clear();
+    return no("allocation failed");
+  }
+  turb.set[(size_t)slot] = 0;
+  double* S = turb.slot[(size_t)slot];
+  for (int n = 0; n < BL_NSFC; ++n) { Fld d; d.t = turb.bl_sfc + (size_t)n * ss; d.nk = 1; compact_in(d, 0, sfc[n]); }
+  const double* cl[2] = {qa, qb};
+  for (int n = 0; n < 2; ++n) {
+    double* dst = S + (size_t)(BLP_QI + n) * n3;
+    if (cl[n]) { Fld d; d.t = dst; d.nk = g.npz; compact_in(d, 0, cl[n]); } else dev_zero(ex, dst, n3 * 8);
+  }
+  dev_zero(ex, turb.flag, 8);
+  each_class([&]() {
+    BlArgs a; a.t = turb_args(slot); a.p = *p; a.dt = dt; a.tbl = turb.bl_tbl; a.sfc = turb.bl_sfc + ex.cls_off; a.ss = ss;
+    a.ekv = raw_out ? turb.bl_raw + ex.cls_off * g.npz : nullptr; a.fkv = raw_out ? a.ekv + n3 : nullptr;
+    a.cloud_mode = cloud_mode; a.flag = turb.flag + 1;
+    run_bl_driver(ex, a);
+  });
+  int flag[2] = {0, 0};
+  d2h(ex, flag, turb.flag, sizeof flag);
+  if (flag[1]) return no("a column's surface parcel never reaches its level of neutral buoyancy (mpbl_depth leaves ipbl unset; slot " + std::to_string(slot) + " is not set)");
+  if (raw_out) {
+    for (int n = 0; n < 11; ++n) { Fld d; d.t = n < 9 ? S + (size_t)n * n3 : turb.bl_raw + (size_t)(n - 9) * n3; d.nk = g.npz; compact_out(d, 0, raw_out[n]); }
+    { Fld d; d.t = turb.bl_sfc + (size_t)BL_ZPBL * ss; d.nk = 1; compact_out(d, 0, raw_out[11]); }
+    { Fld d; d.t = turb.bl_sfc + (size_t)BL_CT * ss; d.nk = 1; compact_out(d, 0, raw_out[12]); }
+  }
+  return turb_factorise(who, slot);
 }
 inline bool Dynamics::turb_run(int slot, int mode) {
   if (!turb_slot_ok("fv3lm_turbulence", slot)) return false;

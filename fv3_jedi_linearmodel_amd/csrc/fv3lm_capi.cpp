@@ -209,6 +209,19 @@ int fv3lm_turbulence_set_simple(fv3lm_handle* h, int slot, const double* frocean
   if (!h->d.turb_set_simple(slot, frocean)) return fail(h->d.err);
   return status(h);
 }
+void fv3lm_bl_default_params(fv3lm_bl_params* p, int kpblmin) {      // bldriver.F90:100-127
+  if (!p) return;
+  const double r[22] = {5.0, 160.0, 1.0, 160.0, 1.0, 3000., 3000., 0.1, 0.0030, 2.5101471e-8, 1500., 500., 1.0, 0.75, 0.50, 0.25, 0.85, 0.45, 20.0, 1.5e-3, 0.5, -999.};
+  for (int n = 0; n < 22; ++n) p->r[n] = r[n];
+  p->i[0] = kpblmin; p->i[1] = 1; p->i[2] = 1; p->i[3] = 0;
+}
+int fv3lm_turbulence_set_driver(fv3lm_handle* h, int slot, const fv3lm_bl_params* p, double dt, const double* const* sfc, const double* qa,
+                                const double* qb, int cloud_mode, double* const* raw_out) {
+  if (!h) return fail("fv3lm_turbulence_set_driver: null handle");
+  static_assert(sizeof(fv3lm_bl_params) == sizeof(BlParams), "fv3lm_bl_params and BlParams must agree");
+  if (!h->d.turb_set_driver(slot, reinterpret_cast<const BlParams*>(p), dt, sfc, qa, qb, cloud_mode, raw_out)) return fail(h->d.err);
+  return status(h);
+}
 int fv3lm_turbulence(fv3lm_handle* h, int slot, int mode) {
   if (!h) return fail("fv3lm_turbulence: null handle");
   if (!h->d.turb_run(slot, mode)) return fail(h->d.err);

@@ -214,6 +214,29 @@ int fv3lm_turbulence_set_diagonals(fv3lm_handle* h, int slot, const double* cons
 int fv3lm_turbulence_set_simple(fv3lm_handle* h, int slot, const double* frocean);
 int fv3lm_turbulence(fv3lm_handle* h, int slot, int mode);
 int fv3lm_turbulence_get(fv3lm_handle* h, int slot, double* const* out);
+/* BL_DRIVER (physics/turbulence/bldriver.F90, Louis + Lock) on the device: the nine diagonals set_ltraj
+ * (fv3jedi_lm_turbulence_mod.F90:376-540) computes, from the RESIDENT TRAJECTORY at the call -- u, v at (i, j), T, delp, qv = q1, pe
+ * accumulated from ptop, pk, theta = p00^kappa T / pk -- written into the slot together with pk and factorised like those of
+ * fv3lm_turbulence_set_diagonals; the same rules hold (call after fv3lm_traj_to_fv3 and before the step; the slot keeps what the call saw).
+ *   fv3lm_bl_params: TURBPARAMS(22), TURBPARAMSI(4) in the reference's order (LOUIS LAMBDAM LAMBDAM2 LAMBDAH LAMBDAH2 ZKMENV ZKHENV
+ *       MINTHICK MINSHEAR C_B LAMBDA_B AKHMMAX PRANDTLSFC PRANDTLRAD BETA_RAD BETA_SURF KHRADFAC KHSFCFAC TPFAC_SURF ENTRATE_SURF PCEFF_SURF
+ *       LOUIS_MEMORY; KPBLMIN LOCK_ON PBLHT_OPTION RADLW_DEP).  The reference never assigns them: they are the host's.
+ *       fv3lm_bl_default_params fills in the set documented at bldriver.F90:100-127; KPBLMIN = count(PREF < 50000) is the caller's.
+ *   sfc[9] = FRLAND FROCEAN VARFLT ZPBL CM CT CQ USTAR BSTAR, compact (isc:iec, jsc:jec) per tile; they are not modified.
+ *   cloud_mode 0: qa, qb = QI, QL (compact, npz deep; NULL = zero).  cloud_mode 1: qa, qb = QLS, QCN, split on the device by
+ *       IceFraction(T) as set_ltraj:455-464 does.
+ *   raw_out: NULL, or 13 compact arrays that receive what BL_DRIVER left BEFORE the factorisation: AKV BKV CKV AKS BKS CKS AKQ BKQ CKQ
+ *       (the order of diag), EKV, FKV (npz deep), then ZPBL and CT (2-D) as updated.  Its staging is only allocated when it is given.
+ *   LOCK_ON and PBLHT_OPTION are read and never tested by the reference; LOCK_DIFF always runs.  The constants are those of
+ *   fv3jedi_lm_const_mod, which the routine uses; pk and theta take akap and ptop of the options.
+ *   Refused with a message, the slot left unset: before fv3lm_turbulence_create; slot out of range; npz < 7 (the smooth of the bottom six
+ *   levels); nq < 1; KPBLMIN outside 1..npz; RADLW_DEP != 0 (the reference reads an uninitialised array there); dt <= 0; a NULL among
+ *   sfc or in a raw_out that is given; cloud_mode outside 0..1; a column with BSTAR > 0 whose surface parcel never reaches its level of
+ *   neutral buoyancy (the reference would index with an unset ipbl); a zero or non-finite pivot of the diagonals. */
+typedef struct { double r[22]; int i[4]; } fv3lm_bl_params;
+void fv3lm_bl_default_params(fv3lm_bl_params* p, int kpblmin);
+int fv3lm_turbulence_set_driver(fv3lm_handle* h, int slot, const fv3lm_bl_params* p, double dt, const double* const* sfc, const double* qa,
+                                const double* qb, int cloud_mode, double* const* raw_out);
 /* Per-kernel HIP-event profile of everything launched between begin and end, on the library's stream:
  * lines "kernel count total_ms algorithmic_bytes".  Returns the buffer length needed. */
 int fv3lm_profile_begin(fv3lm_handle* h);
