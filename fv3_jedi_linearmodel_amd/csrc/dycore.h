@@ -84,6 +84,37 @@ struct Arena {
   }
 };
 
+// Checkpoint store: a set of device arrays that are saved and restored together, in nrec records of one buffer.  Each item is declared
+// once (add), before alloc; its offset and the record stride follow from the declaration order.  save / restore are one dev_copy per item
+// on ex.stream, in that order.  A record or item out of range (or a set whose allocation failed) records a sticky error and does nothing.
+struct CkSet {
+  struct Item { std::string name; double* p; size_t n, off; };
+  std::string name; std::vector<Item> items; size_t stride = 0; int nrec = 0; double* buf = nullptr;
+  void add(const std::string& nm, double* p, size_t ndoubles) { items.push_back(Item{nm, p, ndoubles, stride}); stride += ndoubles; }
+  void add(const std::string& nm, const Fld& f, size_t plane) { add(nm, f.t, (size_t)f.nk * plane); }       // trajectory of a field, plane = points per level
+  void alloc(const char* nm, int nrec_) {      // an empty set allocates nothing
+    name = nm; buf = nrec_ > 0 ? (double*)dev_alloc(stride * nrec_ * 8) : nullptr; nrec = buf ? nrec_ : 0;
+    if (std::getenv("FV3LM_VERBOSE")) std::fprintf(stderr, "fv3lm: checkpoint set %s: %d records, %zu bytes\n", nm, nrec, stride * nrec * 8);
+  }
+  void destroy() { dev_free(buf); buf = nullptr; nrec = 0; }
+  int item(const char* nm) const {
+    for (int n = 0; n < (int)items.size(); ++n) if (items[(size_t)n].name == nm) return n;
+    set_sticky("internal error: checkpoint set " + name + " has no item " + nm); return -1;
+  }
+  size_t bytes(int item) const { return items[(size_t)item].n * 8; }
+  double* at(int rec, int item) const {         // where record rec keeps the item; null when there is no such place
+    if (buf && rec >= 0 && rec < nrec && item >= 0 && item < (int)items.size()) return buf + (size_t)rec * stride + items[(size_t)item].off;
+    set_sticky("internal error: checkpoint set " + name + ": record " + std::to_string(rec) + " item " + std::to_string(item) + " out of range"); return nullptr;
+  }
+  void save(Exec& ex, int rec, int item) const { if (double* q_ = at(rec, item)) dev_copy(ex, q_, items[(size_t)item].p, bytes(item)); }
+  void restore(Exec& ex, int rec, int item, double* to = nullptr) const {      // to: somewhere else than where the item was saved from
+    if (const double* q_ = at(rec, item)) dev_copy(ex, to ? to : items[(size_t)item].p, q_, bytes(item));
+  }
+  void save(Exec& ex, int rec) const { for (int n = 0; n < (int)items.size(); ++n) save(ex, rec, n); }
+  void restore(Exec& ex, int rec) const { for (int n = 0; n < (int)items.size(); ++n) restore(ex, rec, n); }
+  void redirect(Exec& ex, int rec, int item, const double* from) const { if (double* q_ = at(rec, item)) ex.redirect_t(from, q_); }   // exec.h Redir: read / write the item in the record
+};
+
 typedef fv3lm_options Options;   // include/fv3lm.h
 
 // Per-level selection, dyn_core_tlm.F90:741-921: both the schemes the tangent / adjoint is taken of and the trajectory's.
@@ -196,9 +227,8 @@ struct Dycore {
   void set_class(int c);              // c = -1: all tiles, no shift (exchanges, whole-field copies)
   template <class F_> void each_class(const F_& fn) { for (int c = 0; c < (int)classes.size(); ++c) { set_class(c); fn(); } set_class(-1); }
   Progs acoustic;                     // one acoustic step
-  double* ckpt = nullptr;             // [n_split*k_split][step state: u v delp pt (+ w delz zh)]
   std::vector<const char*> st_in, st_out;   // per-step prognostic fields and the work buffers the step writes them to
-  size_t ck_stride = 0;
+  CkSet acoustic_set;                 // the step state st_in: u v delp pt (+ w delz zh), one record per acoustic step of fv_dynamics
   bool nh = false;                    // non-hydrostatic
   double* nh_ws = nullptr; TapeMem nh_tape;   // column workspace and reverse-mode tape of the column solvers (nh.h)
   NhColArgs nh_args(double dt_) const;
@@ -207,7 +237,8 @@ struct Dycore {
   // Trajectory slots: as many acoustic steps as free HBM allows keep the trajectory of ALL their intermediates (one copy of
   // the work arena's trajectory side + pe, peln, pk, pkz each), written by the forward sweep of step_nl; the backward sweep
   // then skips the nonlinear recompute of those steps.  Steps without a slot are recomputed from their 4-field checkpoint.
-  std::vector<double*> traj_slot, traj_slot_p;   // work.t copy, (pe, peln, pk, pkz).t copy
+  std::vector<double*> traj_slot;     // work.t copy
+  CkSet slot_p_set;                   // pe peln pk pkz, one record per slot
   void init_traj_slots();
   bool has_slot(int a) const { return a < (int)traj_slot.size(); }
   int ck_base = 0;                    // first acoustic-step slot of the current k_split iteration
@@ -848,9 +879,9 @@ inline bool Dycore::init(int nx, int ny, int npz, int ntile, int face, int nq_, 
   }
   reuse_fields = false; set_class(-1);
   acoustic_zero.assign(zero_ranges.begin(), zero_ranges.end());
-  ck_stride = 0;
-  for (const char* n_ : st_in) ck_stride += (size_t)f(n_).nk * np;
-  ckpt = (double*)dev_alloc((size_t)n_split * k_split * ck_stride * 8);
+  for (const char* n_ : st_in) acoustic_set.add(n_, f(n_), np);      // sizes over all resident tiles (set_class(-1) above)
+  acoustic_set.alloc("acoustic", n_split * k_split);
+  for (const char* n_ : {"pe", "peln", "pk", "pkz"}) slot_p_set.add(n_, f(n_), np);
   ex.wlo = work.t; ex.whi = work.t + work.cap;
   return true;
 }
@@ -913,7 +944,7 @@ inline bool Dycore::set_exchange_remote(int kind, int npeers, const int* peers, 
 
 // called after every other allocation (Dynamics::init2): take what is left of the HBM, minus a reserve
 inline void Dycore::init_traj_slots() {
-  const size_t slot_bytes = work.used * 8, extra_bytes = (3 * n3p + n3) * 8;     // the fields taken, not the arena's capacity
+  const size_t slot_bytes = work.used * 8, extra_bytes = slot_p_set.stride * 8;     // the fields taken, not the arena's capacity
   if (std::getenv("FV3LM_VERBOSE")) std::fprintf(stderr, "fv3lm: face %d nh %d nq %d: work arena %zu of %zu doubles (%d + %d fields), state %zu of %zu (%d + %d fields)\n", g.face, (int)nh, nq, work.used, work.cap, nW3, nW3p, state.used, state.cap, nS3, nS3p);
   int want = n_split * k_split;
   if (const char* e = std::getenv("FV3LM_TRAJ_SLOTS")) want = std::min(want, std::max(0, std::atoi(e)));
@@ -924,18 +955,19 @@ inline void Dycore::init_traj_slots() {
   const int fit = fr > reserve ? (int)((fr - reserve) / (slot_bytes + extra_bytes)) : 0;
   if (want > fit) want = fit;
 #endif
-  for (int n = 0; n < want; ++n) { traj_slot.push_back((double*)dev_alloc(slot_bytes)); traj_slot_p.push_back((double*)dev_alloc(extra_bytes)); }
+  for (int n = 0; n < want; ++n) traj_slot.push_back((double*)dev_alloc(slot_bytes));
+  slot_p_set.alloc("slot pressures", want);
 }
 
 inline void Dycore::destroy() {
   for (double* p : metric_dev) dev_free(p);
-  dev_free(lev_dev); dev_free(hs_dev); dev_free(ckpt); dev_free(edge_dev); dev_free(ecorner_dev);
+  dev_free(lev_dev); dev_free(hs_dev); acoustic_set.destroy(); dev_free(edge_dev); dev_free(ecorner_dev);
   dev_free(nh_ws); dev_free(nh_tape.part); dev_free(nh_tape.idx); dev_free(nh_tape.adj); dev_free(nh_tape.overflow);
   for (ExTable& t : xt) { dev_free(t.rows); dev_free(t.src); dev_free(t.ptr); dev_free(t.dst); }
   for (ExRemote& x : xr) { dev_free(x.send_rows); dev_free(x.recv_rows); dev_free(x.asrc); dev_free(x.aptr); dev_free(x.apos); dev_free(x.sendbuf); dev_free(x.recvbuf); }
   state.destroy(); work.destroy();
   for (double* q_ : traj_slot) dev_free(q_);
-  for (double* q_ : traj_slot_p) dev_free(q_);
+  slot_p_set.destroy();
 #ifndef FV3LM_HOST_EMUL
   if (ex.stream) (void)hipStreamDestroy(ex.stream);
   if (ex.sstream) { (void)hipStreamDestroy(ex.sstream); if (ex.ev_s0) (void)hipEventDestroy(ex.ev_s0); if (ex.ev_s1) (void)hipEventDestroy(ex.ev_s1); }
@@ -1243,15 +1275,12 @@ inline void Dycore::build_acoustic() {
 
 // n_split acoustic steps.  NL/TL: state fields u,v,delp,pt are advanced in place (via the *_o
 // buffers).  AD: on entry the .p of u,v,delp,pt (and of mfx..cy, pe..pkz) hold the adjoint of the
-// outputs; on exit the adjoint of the inputs.  Trajectory checkpoints must have been stored by a
-// preceding MODE_NL sweep (store_ckpt=true).
+// outputs; on exit the adjoint of the inputs.  The trajectory must have been stored by a preceding
+// MODE_NL sweep (acoustic_set, and the slots of the steps that have one).
 inline void Dycore::dyn_core(int mode) {
   const std::vector<const char*>&names = st_in, &onames = st_out;
   const int ns = (int)names.size();
-  const char* pnames[4] = {"pe", "peln", "pk", "pkz"};
-  const size_t b3 = n3 * 8, np = (size_t)g.ntile * g.plane;
-  auto bytes = [&](int n) { return (size_t)f(names[n]).nk * np * 8; };
-  auto ck = [&](int a, int n) { double* q_ = ckpt + (size_t)a * ck_stride; for (int m = 0; m < n; ++m) q_ += (size_t)f(names[m]).nk * np; return q_; };
+  const size_t b3 = n3 * 8;
   // first acoustic step of the call: interface heights from the layer thicknesses, halo filled (dyn_core_tlm.F90:1779-1801)
   auto zh_init = [&](int md) {
     NhColArgs a = nh_args(0.); a.f[0] = f("delz"); a.f[1] = f("zh");
@@ -1259,14 +1288,6 @@ inline void Dycore::dyn_core(int mode) {
     auto cols = [&]() { each_class([&]() { NhColArgs b = a; b.g = g; run_nh_col(ex, md, b, NHC_ZH_INIT, R(g.is(), g.ie(), g.js(), g.je()), R(1, 0, 1, 0), "zh_init"); }); };
     if (md != MODE_AD) { cols(); halo(md, H_CELL, f("zh")); }
     else { halo(md, H_CELL, f("zh")); cols(); }
-  };
-  auto slot_io = [&](int a, bool save) {      // pe, peln, pk, pkz trajectory of step a <-> its slot
-    double* q_ = traj_slot_p[a];
-    for (int n = 0; n < 4; ++n) {
-      const size_t nb = (n < 3 ? n3p : n3) * 8;
-      if (save) dev_copy(ex, q_, f(pnames[n]).t, nb); else dev_copy(ex, f(pnames[n]).t, q_, nb);
-      q_ += (n < 3 ? n3p : n3);
-    }
   };
   // State rotation.  The prognostic fields are not copied between the acoustic steps: the step's program is pointed (exec.h Redir) at
   // where its inputs already are and at where its outputs are wanted.
@@ -1277,10 +1298,7 @@ inline void Dycore::dyn_core(int mode) {
   //   AD  the adjoint of a step's inputs is accumulated where the next (earlier) step expects the adjoint of its outputs.
   const bool p_in_slot = !nh;
   auto slot_out = [&](int a, int n) { return f(onames[n]).t + (traj_slot[a] - work.t); };      // step a's output n inside its slot
-  auto point_p_at_slot = [&](int a) {
-    double* q_ = traj_slot_p[a];
-    for (int n = 0; n < 4; ++n) { ex.redirect_t(f(pnames[n]).t, q_); q_ += (n < 3 ? n3p : n3); }
-  };
+  auto point_p_at_slot = [&](int a) { for (int n = 0; n < 4; ++n) slot_p_set.redirect(ex, a, n, slot_p_set.items[(size_t)n].p); };
   if (mode != MODE_AD) {
     for (const char* a : {"mfx", "mfy", "cx", "cy"}) { dev_zero(ex, f(a).t, b3); if (mode == MODE_TL) dev_zero(ex, f(a).p, b3); }
     if (nh) zh_init(mode);
@@ -1290,7 +1308,7 @@ inline void Dycore::dyn_core(int mode) {
       ex.nrt = ex.nrp = 0;
       if (mode == MODE_NL) {
         if (it > 0 && has_slot(a - 1)) { for (int n = 0; n < ns; ++n) ex.redirect_t(f(names[n]).t, slot_out(a - 1, n)); }
-        else for (int n = 0; n < ns; ++n) dev_copy(ex, ck(a, n), f(names[n]).t, bytes(n));
+        else acoustic_set.save(ex, a);
         ex.tshift = has_slot(a) ? traj_slot[a] - work.t : 0;
         if (has_slot(a) && p_in_slot) point_p_at_slot(a);
       } else if (it & 1) {
@@ -1302,13 +1320,13 @@ inline void Dycore::dyn_core(int mode) {
       last_acoustic = last;
       run_group(acoustic, nullptr, mode);
       if (mode == MODE_NL) {
-        if (last || !has_slot(a)) for (int n = 0; n < ns; ++n) dev_copy(ex, f(names[n]).t, f(onames[n]).t + ex.tshift, bytes(n));
+        if (last || !has_slot(a)) for (int n = 0; n < ns; ++n) dev_copy(ex, f(names[n]).t, f(onames[n]).t + ex.tshift, acoustic_set.bytes(n));
         if (has_slot(a)) {
-          if (!p_in_slot) slot_io(a, true);
-          else if (last) { ex.nrt = 0; slot_io(a, false); }         // what follows dyn_core reads the pressures in their own fields
+          if (!p_in_slot) slot_p_set.save(ex, a);
+          else if (last) { ex.nrt = 0; slot_p_set.restore(ex, a); }         // what follows dyn_core reads the pressures in their own fields
         }
       } else if (last && !(it & 1)) {
-        for (int n = 0; n < ns; ++n) { dev_copy(ex, f(names[n]).t, f(onames[n]).t, bytes(n)); dev_copy(ex, f(names[n]).p, f(onames[n]).p, bytes(n)); }
+        for (int n = 0; n < ns; ++n) { dev_copy(ex, f(names[n]).t, f(onames[n]).t, acoustic_set.bytes(n)); dev_copy(ex, f(names[n]).p, f(onames[n]).p, acoustic_set.bytes(n)); }
       }
       ex.tshift = 0; ex.nrt = ex.nrp = 0;
     }
@@ -1319,26 +1337,26 @@ inline void Dycore::dyn_core(int mode) {
       const int a = ck_base + it, r = n_split - 1 - it;
       ex.nrt = ex.nrp = 0;
       if (it > 0 && has_slot(a - 1)) { for (int n = 0; n < ns; ++n) ex.redirect_t(f(names[n]).t, slot_out(a - 1, n)); }
-      else for (int n = 0; n < ns; ++n) dev_copy(ex, f(names[n]).t, ck(a, n), bytes(n));
+      else acoustic_set.restore(ex, a);
       last_acoustic = (it == n_split - 1);
       if (has_slot(a)) {       // this step's intermediates were kept by the forward sweep
         ex.tshift = traj_slot[a] - work.t;
-        if (p_in_slot) point_p_at_slot(a); else slot_io(a, false);
+        if (p_in_slot) point_p_at_slot(a); else slot_p_set.restore(ex, a);
       } else {                 // recompute this step's nonlinear intermediates (flux capacitors left alone)
         ex.tshift = 0;
         run_group(acoustic, nullptr, MODE_NL, true);
       }
       for (auto& zr : acoustic_zero) dev_zero(ex, zr.first, zr.second * 8);      // the few work adjoints no stage launch stores first (plan_adjoint)
       if (!(r & 1)) {          // adjoint of the outputs in the input-named buffers: swap the two sides
-        for (int n = 0; n < ns; ++n) { ex.redirect_p(f(names[n]).p, f(onames[n]).p); ex.redirect_p(f(onames[n]).p, f(names[n]).p); dev_zero(ex, f(onames[n]).p, bytes(n)); }
-      } else for (int n = 0; n < ns; ++n) dev_zero(ex, f(names[n]).p, bytes(n));
+        for (int n = 0; n < ns; ++n) { ex.redirect_p(f(names[n]).p, f(onames[n]).p); ex.redirect_p(f(onames[n]).p, f(names[n]).p); dev_zero(ex, f(onames[n]).p, acoustic_set.bytes(n)); }
+      } else for (int n = 0; n < ns; ++n) dev_zero(ex, f(names[n]).p, acoustic_set.bytes(n));
       run_group(acoustic, nullptr, MODE_AD);
       // pe, peln, pk, pkz of earlier steps are overwritten by later ones: their adjoint is zero there
       for (const char* a_ : {"pe", "peln", "pk"}) dev_zero(ex, f(a_).p, n3p * 8);
       dev_zero(ex, f("pkz").p, b3);
       ex.tshift = 0; ex.nrt = ex.nrp = 0;
     }
-    if (n_split & 1) for (int n = 0; n < ns; ++n) dev_copy(ex, f(names[n]).p, f(onames[n]).p, bytes(n));      // an odd number of swaps
+    if (n_split & 1) for (int n = 0; n < ns; ++n) dev_copy(ex, f(names[n]).p, f(onames[n]).p, acoustic_set.bytes(n));      // an odd number of swaps
     if (nh) zh_init(MODE_AD);
   }
 }

@@ -120,7 +120,7 @@ struct Dynamics : Dycore {
   int cur_km = 0;                                   // k_split iteration being run (tracer checkpoints are per iteration)
   std::vector<std::vector<int>> tr_ksplt_km;        // per k_split iteration: sub-steps per level, from the forward sweep
   std::vector<int> tr_nsplt_km;
-  std::map<long, double*> sub_ck;                   // sub-step checkpoints (nsplt > 1 only): key (km, it, field)
+  std::map<int, CkSet> substep_sets;                // dp1 and q[n] before sub-step it of iteration km (nsplt > 1 only), allocated at first use
   std::vector<Fld> q;
   Fld dp1, qc, qc_o, pe2, pu_ad, pv_ad;
   double *ak_dev = nullptr, *bk_dev = nullptr, *remap_ws = nullptr, *cmax_dev = nullptr;
@@ -128,23 +128,23 @@ struct Dynamics : Dycore {
   // non-hydrostatic vertical remap (nh.h): column operators into the staging fields, handed back to the state afterwards
   Progs remap_nh;
   Fld t_m, w_m, dz_m; std::vector<Fld> q_m;
-  double* ck_nh = nullptr;     // per k_split step: delp, w, delz before the remap + ws
-  double* cknh(int km, int n) { return ck_nh + (size_t)km * (3 * n3 + (size_t)ntile_all * g.plane) + (size_t)n * n3; }
   void build_remap_nh();
   void remap_nh_run(int mode, bool last);      // last: the remap of the last k_split step (the temperature hand-over)
-  double* ck_k = nullptr;      // per-k_split checkpoints
-  double* ck_0 = nullptr;      // T as pt_in reads it (after the Rayleigh damping of a hydrostatic step) and pkz
-  size_t ck_k_stride = 0;
+  // trajectory the backward sweep restores, one record per k_split step: q[n] before tracer_2d and mfx mfy cx cy; pt u v q[n] pe peln pk
+  // (non-hydrostatic: + delp w delz ws) before the remap
+  CkSet tracer_set, remap_set;
+  CkSet entry_set;             // step entry: T as pt_in reads it (after the Rayleigh damping of a hydrostatic step) and pkz
   int nsplt_max = 1;
   bool tracer_subcycle_error = false;
   std::vector<std::pair<double*, size_t>> tracer_zero;     // plan_adjoint(tracer_q, twork)
-  std::vector<double*> snap;   // device snapshot of the prognostic state (fv3lm_state_save)
+  CkSet state_set;             // the prognostic state, trajectory and perturbation (fv3lm_state_save), allocated at the first save
   double* stage_dev = nullptr;   // compact staging buffer of the boundary copies (one field)
   // Rayleigh damping of the upper layers (rayleigh.h; fv3lm_set_rayleigh): off while rf_kmax = 0
   int rf_kmax = 0;
   std::vector<double> rf_host;                   // rf(k), k = 1..npz, 0 below the cutoff
   std::vector<double> ak_host, bk_host;          // the reference pressures pm(k) of the damping
   double *rf_lv = nullptr, *rf_c2l = nullptr, *rf_ck = nullptr;   // per-level constants, cubed-to-lat-lon matrices, wind checkpoint
+                                                 // (rf_ck is no CkSet: the Rayleigh kernels write it, in their own index space of levels 1..kmax)
   Fld rf_pth;                                    // non-hydrostatic: the heated temperature of levels 1..kmax ("rf_pt")
   Progs pt_in_rf;                                // non-hydrostatic pt_in with the damping on (stages.h DynPtInNhRf)
   bool set_rayleigh(double tau, double rf_cutoff, const double* c2l);
@@ -199,11 +199,31 @@ struct Dynamics : Dycore {
   void pressures(int mode);
   void tracer_fwd(int mode);
   void set_tracer_levels(const std::vector<int>& ksplt);
-  double* subck(int km, int it, int n) {
-    const long key = ((long)km * 64 + it) * 64 + n;
-    auto f_ = sub_ck.find(key);
-    if (f_ != sub_ck.end()) return f_->second;
-    double* p = (double*)dev_alloc(n3 * 8); sub_ck[key] = p; return p;
+  CkSet& substep_set(int km, int it) {      // items: dp1, then q[n]
+    CkSet& s = substep_sets[km * 64 + it];
+    if (s.items.empty()) { s.add("dp1", dp1, pl_all()); add_tracers(s); s.alloc("tracer sub-step", 1); }
+    return s;
+  }
+  size_t pl_all() const { return (size_t)ntile_all * g.plane; }      // points per level over all resident tiles
+  void add_tracers(CkSet& s) { for (int n = 0; n < nq; ++n) s.add("q" + std::to_string(n + 1), q[(size_t)n], pl_all()); }
+  // the prognostic fields u v pt delp q* (w delz)
+  std::vector<Fld> prognostic() {
+    std::vector<Fld> fs{f("u"), f("v"), f("pt"), f("delp")};
+    fs.insert(fs.end(), q.begin(), q.end());
+    if (nh) { fs.push_back(f("w")); fs.push_back(f("delz")); }
+    return fs;
+  }
+  // fn(field, the host's array for it) over that list; false (err set, nothing touched) when the host left an array out
+  template <class P, class Fn>
+  bool each_prognostic(const char* who, P u, P v, P t, P delp, P const* qs, P w, P delz, const Fn& fn) {
+    if (!u || !v || !t || !delp || (nq > 0 && !qs) || (nh && (!w || !delz))) { err = std::string(who) + ": null array"; return false; }
+    for (int n = 0; n < nq; ++n) if (!qs[n]) { err = std::string(who) + ": null tracer array"; return false; }
+    std::vector<P> host{u, v, t, delp};
+    host.insert(host.end(), qs, qs + nq);
+    if (nh) { host.push_back(w); host.push_back(delz); }
+    const std::vector<Fld> fs = prognostic();
+    for (size_t n = 0; n < fs.size(); ++n) fn(fs[n], host[n]);
+    return true;
   }
   void tracer_ad();
   void fv_dynamics(int mode);
@@ -219,10 +239,6 @@ struct Dynamics : Dycore {
   // in place (first acoustic checkpoint), from which the initial pressures are recomputed.
   void step_ad() { fv_dynamics(MODE_AD); if (!nh) { pressures(MODE_NL); pressures(MODE_AD); } halo(MODE_AD, H_DEDGE, f("u"), f("v")); }
 
-  double* ckq(int km, int n) { return ck_k + (size_t)km * ck_k_stride + (size_t)n * n3; }                       // q before tracer
-  double* ckm(int km, int n) { return ck_k + (size_t)km * ck_k_stride + (size_t)(nq + n) * n3; }                // mfx mfy cx cy
-  double* ckr3(int km, int n) { return ck_k + (size_t)km * ck_k_stride + (size_t)(nq + 4 + n) * n3; }           // pt u v q'[nq]
-  double* ckrp(int km, int n) { return ck_k + (size_t)km * ck_k_stride + (size_t)(2 * nq + 7) * n3 + (size_t)n * n3p; }  // pe peln pk
 };
 
 inline bool Dynamics::init2(const double* ak, const double* bk) {
@@ -270,10 +286,14 @@ inline bool Dynamics::init2(const double* ak, const double* bk) {
   }
   reuse_fields = false; set_class(-1);
   tracer_zero.assign(tzero.begin(), tzero.end());
-  if (nh) ck_nh = (double*)dev_alloc((3 * n3 + (size_t)ntile_all * g.plane) * k_split * 8);
-  ck_k_stride = (size_t)(2 * nq + 7) * n3 + 3 * n3p;
-  ck_k = (double*)dev_alloc(ck_k_stride * k_split * 8);
-  ck_0 = (double*)dev_alloc(2 * n3 * 8);
+  add_tracers(tracer_set);
+  for (const char* n_ : {"mfx", "mfy", "cx", "cy"}) tracer_set.add(n_, f(n_), pl_all());
+  for (const char* n_ : {"pt", "u", "v"}) remap_set.add(n_, f(n_), pl_all());
+  add_tracers(remap_set);
+  for (const char* n_ : {"pe", "peln", "pk"}) remap_set.add(n_, f(n_), pl_all());
+  if (nh) for (const char* n_ : {"delp", "w", "delz", "ws"}) remap_set.add(n_, f(n_), pl_all());
+  for (const char* n_ : {"pt", "pkz"}) entry_set.add(n_, f(n_), pl_all());
+  tracer_set.alloc("tracer", k_split); remap_set.alloc("remap", k_split); entry_set.alloc("entry", 1);
   init_traj_slots();
   return true;
 }
@@ -281,21 +301,17 @@ inline void Dynamics::destroy2() {
   dev_free(stage_dev); stage_dev = nullptr;
   turb_destroy();
   dev_free(rf_lv); dev_free(rf_c2l); dev_free(rf_ck); dev_free(rf_pth.t); dev_free(rf_pth.p);
-  dev_free(ak_dev); dev_free(bk_dev); if (remap_ws_own) dev_free(remap_ws); dev_free(cmax_dev); dev_free(ck_k); dev_free(ck_0); dev_free(ck_nh);
+  dev_free(ak_dev); dev_free(bk_dev); if (remap_ws_own) dev_free(remap_ws); dev_free(cmax_dev);
   tshared.destroy(); twork.destroy();
-  for (double* p : snap) dev_free(p);
-  for (auto& kv : sub_ck) dev_free(kv.second);
+  for (CkSet* s : {&tracer_set, &remap_set, &entry_set, &state_set}) s->destroy();
+  for (auto& kv : substep_sets) kv.second.destroy();
 }
 
 // traj_to_fv3 (DYN/fv3jedi_lm_dynamics_mod.F90:717-807): halos zeroed, interiors from the host's compact arrays, the D-grid edge rows
 // u(:, jec+1), v(iec+1, :) from the neighbours (mpp_get_boundary :781-793), halo of phis (:798), pe / peln / pk / pkz (:803-805)
 inline bool Dynamics::traj_to_fv3(const double* u, const double* v, const double* t, const double* delp, const double* const* qs, const double* w,
                                   const double* delz, const double* phis) {
-  if (!u || !v || !t || !delp || (nq > 0 && !qs) || (nh && (!w || !delz))) { err = "traj_to_fv3: null array"; return false; }
-  for (int n = 0; n < nq; ++n) if (!qs[n]) { err = "traj_to_fv3: null tracer array"; return false; }      // before anything is touched
-  compact_in(f("u"), 0, u); compact_in(f("v"), 0, v); compact_in(f("pt"), 0, t); compact_in(f("delp"), 0, delp);
-  for (int n = 0; n < nq; ++n) compact_in(q[n], 0, qs[n]);
-  if (nh) { compact_in(f("w"), 0, w); compact_in(f("delz"), 0, delz); }
+  if (!each_prognostic("traj_to_fv3", u, v, t, delp, qs, w, delz, [&](const Fld& x, const double* a) { compact_in(x, 0, a); })) return false;
   halo(MODE_NL, H_DEDGE, f("u"), f("v"));
   if (phis) { Fld hs; hs.t = hs_dev; hs.p = nullptr; hs.nk = 1; compact_in(hs, 0, phis); halo(MODE_NL, H_CELL, hs); }
   pressures(MODE_NL);
@@ -304,25 +320,11 @@ inline bool Dynamics::traj_to_fv3(const double* u, const double* v, const double
 // pert_to_fv3 (:846-889): perturbation / adjoint arrays, halos zeroed
 inline bool Dynamics::pert_to_fv3(const double* u, const double* v, const double* t, const double* delp, const double* const* qs, const double* w,
                                   const double* delz) {
-  if (!u || !v || !t || !delp || (nq > 0 && !qs) || (nh && (!w || !delz))) { err = "pert_to_fv3: null array"; return false; }
-  for (int n = 0; n < nq; ++n) if (!qs[n]) { err = "pert_to_fv3: null tracer array"; return false; }
-  compact_in(f("u"), 1, u); compact_in(f("v"), 1, v); compact_in(f("pt"), 1, t); compact_in(f("delp"), 1, delp);
-  for (int n = 0; n < nq; ++n) compact_in(q[n], 1, qs[n]);
-  if (nh) { compact_in(f("w"), 1, w); compact_in(f("delz"), 1, delz); }
-  return true;
+  return each_prognostic("pert_to_fv3", u, v, t, delp, qs, w, delz, [&](const Fld& x, const double* a) { compact_in(x, 1, a); });
 }
 // fv3_to_pert (:893-933): compute-domain values back to the host; the device perturbation is cleared as the reference clears FV_AtmP
 inline bool Dynamics::fv3_to_pert(double* u, double* v, double* t, double* delp, double* const* qs, double* w, double* delz) {
-  if (!u || !v || !t || !delp || (nq > 0 && !qs) || (nh && (!w || !delz))) { err = "fv3_to_pert: null array"; return false; }
-  for (int n = 0; n < nq; ++n) if (!qs[n]) { err = "fv3_to_pert: null tracer array"; return false; }
-  compact_out(f("u"), 1, u); compact_out(f("v"), 1, v); compact_out(f("pt"), 1, t); compact_out(f("delp"), 1, delp);
-  for (int n = 0; n < nq; ++n) compact_out(q[n], 1, qs[n]);
-  if (nh) { compact_out(f("w"), 1, w); compact_out(f("delz"), 1, delz); }
-  std::vector<Fld> fs{f("u"), f("v"), f("pt"), f("delp")};
-  for (auto& x : q) fs.push_back(x);
-  if (nh) { fs.push_back(f("w")); fs.push_back(f("delz")); }
-  for (const Fld& x : fs) dev_zero(ex, x.p, n3 * 8);
-  return true;
+  return each_prognostic("fv3_to_pert", u, v, t, delp, qs, w, delz, [&](const Fld& x, double* a) { compact_out(x, 1, a); dev_zero(ex, x.p, n3 * 8); });
 }
 
 inline void Dynamics::build_remap_nh() {
@@ -463,10 +465,7 @@ inline void Dynamics::tracer_fwd(int mode) {
   run_group(tracer_scale, nullptr, mode);
   for (int it = 1; it <= nsplt; ++it) {
     ctx.tr_it = it;
-    if (mode == MODE_NL && nsplt > 1) {     // trajectory of the later sub-steps for the backward sweep
-      dev_copy(ex, subck(km, it, nq), dp1.t, b3);
-      for (int n = 0; n < nq; ++n) dev_copy(ex, subck(km, it, n), q[n].t, b3);
-    }
+    if (mode == MODE_NL && nsplt > 1) substep_set(km, it).save(ex, 0);     // trajectory of the later sub-steps for the backward sweep
     run_group(tracer_pre, nullptr, mode);
     for (int n = 0; n < nq; ++n) {
       ex.nrt = ex.nrp = 0;             // the transport program reads tracer n where it is (exec.h Redir); its output cannot go there (neighbours' halos)
@@ -497,11 +496,12 @@ inline void Dynamics::tracer_ad() {
       for (int n = nq - 1; n >= 0; --n) halo(MODE_AD, H_CELL, q[n]);
       each_class([&]() { for_points(ex, Rect{g.is(), g.ie(), g.js(), g.je()}, g.ntile * npz, TrDp1Fn{g, ex.sh(dp1), ex.sh(tr_dp2), lev_dev, it, MODE_AD}, "tracer_dp1"); });
     }
-    if (nsplt > 1) dev_copy(ex, dp1.t, subck(km, it, nq), b3);
+    if (nsplt > 1) substep_set(km, it).restore(ex, 0, 0);      // dp1
     run_group(tracer_pre, nullptr, MODE_NL);
     for (int n = nq - 1; n >= 0; --n) {
       ex.nrt = ex.nrp = 0;             // trajectory of tracer n read where it is, the incoming adjoint likewise; the result is built in qc.p
-      ex.redirect_t(qc.t, nsplt > 1 ? subck(km, it, n) : q[n].t); ex.redirect_p(qc_o.p, q[n].p);
+      if (nsplt > 1) substep_set(km, it).redirect(ex, 0, 1 + n, qc.t); else ex.redirect_t(qc.t, q[n].t);
+      ex.redirect_p(qc_o.p, q[n].p);
       run_group(tracer_q, nullptr, MODE_NL);
       for (auto& zr : tracer_zero) dev_zero(ex, zr.first, zr.second * 8);       // plan_adjoint: the rest is stored by its first stage launch
       dev_zero(ex, qc.p, b3);
@@ -521,7 +521,7 @@ inline void Dynamics::fv_dynamics(int mode) {
   const bool rf_nh = rf_kmax > 0 && nh;
   if (mode != MODE_AD) {
     rayleigh(mode);       // RAYLEIGH_SUPER before the conversion (fv_dynamics_tlm.F90:535-562); nothing while it is off
-    if (mode == MODE_NL) { dev_copy(ex, ck_0, f("pt").t, b3); dev_copy(ex, ck_0 + n3, f("pkz").t, b3); }
+    if (mode == MODE_NL) entry_set.save(ex, 0);
     run_group(rf_nh ? pt_in_rf : pt_in, nullptr, mode);
     dev_copy(ex, f("pt").t, f("pt_o").t, b3);
     if (mode == MODE_TL) dev_copy(ex, f("pt").p, f("pt_o").p, b3);
@@ -533,25 +533,11 @@ inline void Dynamics::fv_dynamics(int mode) {
       dyn_core(mode);
       if (nq > 0) {
         for (int n = 0; n < nq; ++n) halo(mode, H_CELL, q[n]);
-        if (mode == MODE_NL) {
-          for (int n = 0; n < nq; ++n) dev_copy(ex, ckq(km, n), q[n].t, b3);
-          const char* mf[4] = {"mfx", "mfy", "cx", "cy"};
-          for (int n = 0; n < 4; ++n) dev_copy(ex, ckm(km, n), f(mf[n]).t, b3);
-        }
+        if (mode == MODE_NL) tracer_set.save(ex, km);
         tracer_fwd(mode);
       }
       if (g.npz > 4) {
-        if (mode == MODE_NL) {
-          const char* r3[3] = {"pt", "u", "v"}; const char* rp[3] = {"pe", "peln", "pk"};
-          for (int n = 0; n < 3; ++n) dev_copy(ex, ckr3(km, n), f(r3[n]).t, b3);
-          for (int n = 0; n < nq; ++n) dev_copy(ex, ckr3(km, 3 + n), q[n].t, b3);
-          for (int n = 0; n < 3; ++n) dev_copy(ex, ckrp(km, n), f(rp[n]).t, b3p);
-          if (nh) {
-            const char* r4[3] = {"delp", "w", "delz"};
-            for (int n = 0; n < 3; ++n) dev_copy(ex, cknh(km, n), f(r4[n]).t, b3);
-            dev_copy(ex, cknh(km, 3), f("ws").t, (size_t)ntile_all * g.plane * 8);
-          }
-        }
+        if (mode == MODE_NL) remap_set.save(ex, km);
         if (nh) remap_nh_run(mode, km == k_split - 1); else
         each_class([&]() { run_remap(ex, mode, remap_args(km == k_split - 1)); });
       }
@@ -565,26 +551,17 @@ inline void Dynamics::fv_dynamics(int mode) {
   if (nh) dev_zero(ex, f("ws").p, (size_t)ntile_all * g.plane * 8);
   for (int km = k_split - 1; km >= 0; --km) {
     if (g.npz > 4) {
-      const char* r3[3] = {"pt", "u", "v"}; const char* rp[3] = {"pe", "peln", "pk"};
-      for (int n = 0; n < 3; ++n) dev_copy(ex, f(r3[n]).t, ckr3(km, n), b3);
-      for (int n = 0; n < nq; ++n) dev_copy(ex, q[n].t, ckr3(km, 3 + n), b3);
-      for (int n = 0; n < 3; ++n) dev_copy(ex, f(rp[n]).t, ckrp(km, n), b3p);
+      remap_set.restore(ex, km);
       dev_zero(ex, f("pe").p, b3p);
-      if (nh) {
-        const char* r4[3] = {"delp", "w", "delz"};
-        for (int n = 0; n < 3; ++n) dev_copy(ex, f(r4[n]).t, cknh(km, n), b3);
-        dev_copy(ex, f("ws").t, cknh(km, 3), (size_t)ntile_all * g.plane * 8);
-        remap_nh_run(MODE_AD, km == k_split - 1);
-      } else
+      if (nh) remap_nh_run(MODE_AD, km == k_split - 1); else
       each_class([&]() { run_remap(ex, MODE_AD, remap_args(km == k_split - 1)); });
     }
     const char* mf[4] = {"mfx", "mfy", "cx", "cy"};
     for (int n = 0; n < 4; ++n) dev_zero(ex, f(mf[n]).p, b3);
     dev_zero(ex, dp1.p, b3);
     if (nq > 0) {
-      for (int n = 0; n < nq; ++n) dev_copy(ex, q[n].t, ckq(km, n), b3);
-      for (int n = 0; n < 4; ++n) dev_copy(ex, f(mf[n]).t, ckm(km, n), b3);
-      dev_copy(ex, dp1.t, ckpt + (size_t)(km * n_split) * ck_stride + 2 * n3, b3);   // delp at the start of this k_split step
+      tracer_set.restore(ex, km);
+      acoustic_set.restore(ex, km * n_split, acoustic_set.item("delp"), dp1.t);   // delp at the start of this k_split step
       cur_km = km;
       tracer_ad();
       for (int n = 0; n < nq; ++n) halo(MODE_AD, H_CELL, q[n]);
@@ -595,8 +572,8 @@ inline void Dynamics::fv_dynamics(int mode) {
     halo(MODE_AD, H_CELL, f("pt")); halo(MODE_AD, H_CELL, f("delp")); halo(MODE_AD, H_DVEC, f("u"), f("v"));
   }
   // pt_in: pt(theta_v) = T (1 + zvir qv) / pkz
-  dev_copy(ex, f("pt").t, ck_0, b3); dev_copy(ex, f("pkz").t, ck_0 + n3, b3);
-  if (nq > 0) dev_copy(ex, q[0].t, ckq(0, 0), b3);
+  entry_set.restore(ex, 0);
+  if (nq > 0) tracer_set.restore(ex, 0, 0);      // q1 before the first tracer_2d
   dev_copy(ex, f("pt_o").p, f("pt").p, b3); dev_zero(ex, f("pt").p, b3);
   if (rf_nh) for (int t = 0; t < ntile_all; ++t) dev_zero(ex, rf_pth.p + (size_t)t * g.npz * g.plane, (size_t)rf_kmax * g.plane * 8);
   run_group(rf_nh ? pt_in_rf : pt_in, nullptr, MODE_AD);
