@@ -22,6 +22,9 @@ module fv3lm_hip_mod
   public :: fv3lm_hip_turbulence_create, fv3lm_hip_turbulence_set_diagonals, fv3lm_hip_turbulence_set_simple
   public :: fv3lm_hip_turbulence, fv3lm_hip_turbulence_get
   public :: fv3lm_bl_params, fv3lm_hip_bl_default_params, fv3lm_hip_turbulence_set_driver
+  public :: fv3lm_ras_params, fv3lm_hip_ras_default_params, fv3lm_hip_convection_create, fv3lm_hip_convection_set
+  public :: fv3lm_hip_convection_get, fv3lm_hip_convection_get_sources, fv3lm_hip_convection_put_sources, fv3lm_hip_convection
+  public :: fv3lm_hip_convection_table
 
   integer, parameter :: ng = 3   ! halo width, tools/fv_mp_nlm_mod.F90:67
 
@@ -59,6 +62,11 @@ module fv3lm_hip_mod
     real(c_double) :: r(22)
     integer(c_int) :: i(4)
   end type fv3lm_bl_params
+
+  !> RASPARAMS(1:25) of the moist physics (fv3lm_ras_params of include/fv3lm.h)
+  type, bind(C) :: fv3lm_ras_params
+    real(c_double) :: r(25)
+  end type fv3lm_ras_params
 
   type :: fv3lm_hip_type
     type(c_ptr) :: handle = c_null_ptr
@@ -220,6 +228,49 @@ module fv3lm_hip_mod
       type(fv3lm_bl_params), intent(in) :: p
       real(c_double), value :: dt
       type(c_ptr), intent(in) :: sfc(*)
+      integer(c_int) :: rc
+    end function
+    subroutine c_ras_default_params(p, im) bind(C, name="fv3lm_ras_default_params")
+      import :: fv3lm_ras_params, c_int
+      type(fv3lm_ras_params), intent(out) :: p
+      integer(c_int), value :: im
+    end subroutine
+    function c_convection_create(h, nslots, p, do_phy_mst) bind(C, name="fv3lm_convection_create") result(rc)
+      import :: fv3lm_ras_params, c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), value :: nslots, do_phy_mst
+      type(fv3lm_ras_params), intent(in) :: p
+      integer(c_int) :: rc
+    end function
+    function c_convection_set(h, slot, ts, frland, kcbl) bind(C, name="fv3lm_convection_set") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h, ts, frland, kcbl
+      integer(c_int), value :: slot
+      integer(c_int) :: rc
+    end function
+    function c_convection_get(h, slot, out6, doconvec, jac2) bind(C, name="fv3lm_convection_get") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h, doconvec, jac2
+      integer(c_int), value :: slot
+      type(c_ptr), intent(in) :: out6(*)
+      integer(c_int) :: rc
+    end function
+    function c_convection_sources(h, put, src4) bind(C, name="fv3lm_convection_sources") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), value :: put
+      type(c_ptr), intent(in) :: src4(*)
+      integer(c_int) :: rc
+    end function
+    function c_convection_table(h, table, constants) bind(C, name="fv3lm_convection_table") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h, table, constants
+      integer(c_int) :: rc
+    end function
+    function c_convection(h, slot, mode) bind(C, name="fv3lm_convection") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), value :: slot, mode
       integer(c_int) :: rc
     end function
     function c_last_error() bind(C, name="fv3lm_last_error") result(p)
@@ -468,6 +519,81 @@ contains
     end do
     call check(c_turbulence_get(self%handle, int(slot - 1, c_int), d), 'turbulence_get')
   end subroutine fv3lm_hip_turbulence_get
+
+  !> Linearised RAS convection (physics/moist: RASE, RASE_D, RASE_B and the convective part of set_ltraj).  Slots are numbered from 1,
+  !! like ltraj(conf%n); arrays are the host's own, (isc:iec, jsc:jec[, npz]).  RASPARAMS as create :120-148 sets them (im = conf%im).
+  subroutine fv3lm_hip_ras_default_params(p, im)
+    type(fv3lm_ras_params), intent(out) :: p
+    integer, intent(in) :: im
+    call c_ras_default_params(p, int(im, c_int))
+  end subroutine fv3lm_hip_ras_default_params
+
+  subroutine fv3lm_hip_convection_create(self, nslots, p, do_phy_mst)
+    type(fv3lm_hip_type), intent(in) :: self
+    integer, intent(in) :: nslots, do_phy_mst
+    type(fv3lm_ras_params), intent(in) :: p
+    call check(c_convection_create(self%handle, int(nslots, c_int), p, int(do_phy_mst, c_int)), 'convection_create')
+  end subroutine fv3lm_hip_convection_create
+
+  !> In place of the convective part of set_ltraj (:700-832): call after fv3lm_hip_traj_to_fv3 and before the dynamics' step.
+  subroutine fv3lm_hip_convection_set(self, slot, ts, frland, kcbl)
+    type(fv3lm_hip_type), intent(in) :: self
+    integer, intent(in) :: slot
+    real(c_double), intent(in), target, contiguous :: ts(:, :), frland(:, :), kcbl(:, :)
+    call check(c_convection_set(self%handle, int(slot - 1, c_int), c_loc(ts), c_loc(frland), c_loc(kcbl)), 'convection_set')
+  end subroutine fv3lm_hip_convection_set
+
+  !> out(:, :, :, 1:6) = PTT_C QVT_C CNV_DQLDT_C CNV_MFD_C CNV_PRC3_C CNV_UPDF_C (what the cloud scheme reads), doconvec
+  subroutine fv3lm_hip_convection_get(self, slot, out, doconvec)
+    type(fv3lm_hip_type), intent(in) :: self
+    integer, intent(in) :: slot
+    real(c_double), intent(inout), target, contiguous :: out(:, :, :, :)
+    integer(c_int), intent(inout), target, contiguous :: doconvec(:, :)
+    type(c_ptr) :: d(6)
+    integer :: n
+    do n = 1, 6
+      d(n) = c_loc(out(1, 1, 1, n))
+    end do
+    call check(c_convection_get(self%handle, int(slot - 1, c_int), d, c_loc(doconvec), c_null_ptr), 'convection_get')
+  end subroutine fv3lm_hip_convection_get
+
+  !> src(:, :, :, 1:4) = CNV_DQLDT CNV_MFD CNV_PRC3 CNV_UPDF of the perturbation: read after a tangent run ...
+  subroutine fv3lm_hip_convection_get_sources(self, src)
+    type(fv3lm_hip_type), intent(in) :: self
+    real(c_double), intent(inout), target, contiguous :: src(:, :, :, :)
+    type(c_ptr) :: d(4)
+    integer :: n
+    do n = 1, 4
+      d(n) = c_loc(src(1, 1, 1, n))
+    end do
+    call check(c_convection_sources(self%handle, 0_c_int, d), 'convection_sources (get)')
+  end subroutine fv3lm_hip_convection_get_sources
+
+  !> ... and given before an adjoint run (the adjoints the cloud scheme's adjoint left in them)
+  subroutine fv3lm_hip_convection_put_sources(self, src)
+    type(fv3lm_hip_type), intent(in) :: self
+    real(c_double), intent(in), target, contiguous :: src(:, :, :, :)
+    type(c_ptr) :: d(4)
+    integer :: n
+    do n = 1, 4
+      d(n) = c_loc(src(1, 1, 1, n))
+    end do
+    call check(c_convection_sources(self%handle, 1_c_int, d), 'convection_sources (put)')
+  end subroutine fv3lm_hip_convection_put_sources
+
+  !> diagnostics: the saturation table on the device (18301 entries) and the kernels' nine constants (CP ALHL GRAV RGAS H2OMW AIRMW VIREPS P00 KAPPA)
+  subroutine fv3lm_hip_convection_table(self, table, constants)
+    type(fv3lm_hip_type), intent(in) :: self
+    real(c_double), intent(inout), target, contiguous :: table(:), constants(:)
+    call check(c_convection_table(self%handle, c_loc(table), c_loc(constants)), 'convection_table')
+  end subroutine fv3lm_hip_convection_table
+
+  !> mode 0 step_nl, 1 step_tl (after the turbulence), 2 step_ad (before the turbulence's adjoint) of the moist physics, convection only
+  subroutine fv3lm_hip_convection(self, slot, mode)
+    type(fv3lm_hip_type), intent(in) :: self
+    integer, intent(in) :: slot, mode
+    call check(c_convection(self%handle, int(slot - 1, c_int), int(mode, c_int)), 'convection')
+  end subroutine fv3lm_hip_convection
 
   !> Replaces compute_fv3_pressures_tlm + fv_dynamics_tlm (fv3jedi_lm_dynamics_mod.F90:404-438).
   subroutine fv3lm_hip_step_tl(self)

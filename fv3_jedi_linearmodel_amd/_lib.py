@@ -22,6 +22,11 @@ class BlParams(C.Structure):
     _fields_ = [("r", C.c_double * 22), ("i", C.c_int * 4)]
 
 
+class RasParams(C.Structure):
+    """fv3lm_ras_params: RASPARAMS(1:25) of the moist physics in the reference's order"""
+    _fields_ = [("r", C.c_double * 25)]
+
+
 class Fv3LmLibrary:
     def __init__(self, path):
         if not os.path.exists(path):
@@ -318,6 +323,65 @@ class Dycore:
         self.lib.L.fv3lm_turbulence_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(_dp)]
         self._chk(self.lib.L.fv3lm_turbulence_get(self.h, int(slot), ptrs))
         return out
+
+    # ---- linearised RAS convection (physics/moist/convection.F90; csrc/convection.h), compact arrays [ntile, (npz,) ny, nx] ----
+    SET_NAMES = ("PTT_C", "QVT_C", "CNV_DQLDT_C", "CNV_MFD_C", "CNV_PRC3_C", "CNV_UPDF_C")
+    SRC_NAMES = ("CNV_DQLDT", "CNV_MFD", "CNV_PRC3", "CNV_UPDF")
+
+    def ras_default_params(self, im):
+        """fv3lm_ras_default_params: RASPARAMS of create :120-148; entry 23 follows imsize = 4 im"""
+        p = RasParams()
+        self.lib.L.fv3lm_ras_default_params.argtypes = [C.POINTER(RasParams), C.c_int]
+        self.lib.L.fv3lm_ras_default_params.restype = None
+        self.lib.L.fv3lm_ras_default_params(C.byref(p), int(im))
+        return p
+
+    def convection_create(self, nslots, params, do_phy_mst):
+        """fv3lm_convection_create: the slots, the sources and the work spaces of one batch of columns; all device memory of the feature"""
+        self.lib.L.fv3lm_convection_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(RasParams), C.c_int]
+        self._chk(self.lib.L.fv3lm_convection_create(self.h, int(nslots), None if params is None else C.byref(params), int(do_phy_mst)))
+
+    def convection_set(self, slot, ts, frland, kcbl):
+        """the slot takes the resident trajectory u v pt(= T) delp q1 at this call; ts, frland, kcbl compact [ntile, ny, nx] (None: NULL)"""
+        a = [None if x is None else self._compact(x) for x in (ts, frland, kcbl)]
+        self.lib.L.fv3lm_convection_set.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
+        self._chk(self.lib.L.fv3lm_convection_set(self.h, int(slot), *[None if x is None else _ptr(x) for x in a]))
+
+    def convection_get(self, slot, jac=True):
+        """-> (dict by SET_NAMES [ntile, npz, ny, nx], doconvec [ntile, ny, nx] int32, jac2 [2, ntile, npz, ny, nx] or None)"""
+        shp = (self.dims.ntile, self.dims.npz, self.dims.ny, self.dims.nx)
+        out = {n: np.empty(shp) for n in self.SET_NAMES}
+        ptrs = (_dp * 6)(*[_ptr(out[n]) for n in self.SET_NAMES])
+        dc = np.zeros((shp[0],) + shp[2:], dtype=np.int32)
+        j2 = np.empty((2,) + shp) if jac else None
+        self.lib.L.fv3lm_convection_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(_dp), C.POINTER(C.c_int), _dp]
+        self._chk(self.lib.L.fv3lm_convection_get(self.h, int(slot), ptrs, dc.ctypes.data_as(C.POINTER(C.c_int)), None if j2 is None else _ptr(j2)))
+        return out, dc, j2
+
+    def convection_sources(self, src=None):
+        """src None: -> the four sources of the perturbation (dict by SRC_NAMES); src (dict or sequence, an entry None: NULL): put them"""
+        self.lib.L.fv3lm_convection_sources.argtypes = [C.c_void_p, C.c_int, C.POINTER(_dp)]
+        if src is None:
+            shp = (self.dims.ntile, self.dims.npz, self.dims.ny, self.dims.nx)
+            out = {n: np.empty(shp) for n in self.SRC_NAMES}
+            self._chk(self.lib.L.fv3lm_convection_sources(self.h, 0, (_dp * 4)(*[_ptr(out[n]) for n in self.SRC_NAMES])))
+            return out
+        if isinstance(src, dict):
+            src = [src.get(n) for n in self.SRC_NAMES]
+        keep = [None if a is None else self._compact(a, self.dims.npz) for a in src]
+        self._chk(self.lib.L.fv3lm_convection_sources(self.h, 1, (_dp * 4)(*[None if a is None else _ptr(a) for a in keep])))
+
+    def convection_table(self):
+        """-> (the saturation table as it lies on the device [18301], the kernels' constants CP ALHL GRAV RGAS H2OMW AIRMW VIREPS P00 KAPPA)"""
+        tbl, cst = np.empty(18301), np.empty(9)
+        self.lib.L.fv3lm_convection_table.argtypes = [C.c_void_p, _dp, _dp]
+        self._chk(self.lib.L.fv3lm_convection_table(self.h, _ptr(tbl), _ptr(cst)))
+        return tbl, cst
+
+    def convection(self, slot, mode):
+        """RAS convection in the DOCONVEC columns of the slot: NL on the trajectory, TL on the perturbation, AD on the adjoint"""
+        self.lib.L.fv3lm_convection.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        self._chk(self.lib.L.fv3lm_convection(self.h, int(slot), int(mode)))
 
     # ---- the host's boundary copies on the device (compact arrays [ntile, nk, ny, nx], no halo) ----
     def _cptrs(self, d, names, out=False):

@@ -8,6 +8,7 @@
 #include "rayleigh.h"
 #include "turbulence.h"
 #include "bldriver.h"
+#include "convection.h"
 
 namespace fv3 {
 
@@ -165,6 +166,25 @@ struct Dynamics : Dycore {
   bool turb_run(int slot, int mode);
   bool turb_get(int slot, double* const* out);
   void turb_destroy();
+  // Linearised RAS convection (convection.h; fv3lm_convection_*): nothing allocated until conv_create
+  struct Convection {
+    int nslots = 0, mst = 0, icmin = 0, nb = 0; RasParams p;
+    double* slot_block = nullptr; int* list_block = nullptr;
+    std::vector<double*> slot; std::vector<char> set; std::vector<int*> list; std::vector<int> nactive;
+    double *gw = nullptr, *tw = nullptr, *ew = nullptr, *ck = nullptr, *src = nullptr, *tbl = nullptr, *sige = nullptr; int* flag = nullptr;
+    TapeMem tape;
+  } conv;
+  size_t conv_ncol() const { return (size_t)ntile_all * g.tx * g.ty; }
+  size_t conv_slot_doubles() const { return ((size_t)RAS_NS * (g.npz + 1) + RAS_NSC) * conv_ncol(); }
+  bool conv_create(int nslots, const RasParams* p, int do_phy_mst);
+  bool conv_slot_ok(const char* who, int slot, bool need_set);
+  RasArgs conv_args(int slot);
+  bool conv_set(int slot, const double* ts, const double* frland, const double* kcbl);
+  bool conv_get(int slot, double* const* out6, int* doconvec, double* jac2);
+  bool conv_sources(int put, double* const* src4);
+  bool conv_table(double* table, double* constants);
+  bool conv_run(int slot, int mode);
+  void conv_destroy();
   // one field between the host's compact array and the device state.  which: 0 trajectory, 1 perturbation / adjoint
   void compact_in(const Fld& f, int which, const double* host) {
     const size_t n = (size_t)ntile_all * f.nk * g.tx * g.ty;
@@ -300,6 +320,7 @@ inline bool Dynamics::init2(const double* ak, const double* bk) {
 inline void Dynamics::destroy2() {
   dev_free(stage_dev); stage_dev = nullptr;
   turb_destroy();
+  conv_destroy();
   dev_free(rf_lv); dev_free(rf_c2l); dev_free(rf_ck); dev_free(rf_pth.t); dev_free(rf_pth.p);
   dev_free(ak_dev); dev_free(bk_dev); if (remap_ws_own) dev_free(remap_ws); dev_free(cmax_dev);
   tshared.destroy(); twork.destroy();
@@ -793,6 +814,179 @@ inline bool Dynamics::turb_get(int slot, double* const* out) {
   if (!out) { err = "fv3lm_turbulence_get: null array"; return false; }
   for (int n = 0; n < TURB_NARR; ++n) if (!out[n]) { err = "fv3lm_turbulence_get: null array"; return false; }
   for (int n = 0; n < TURB_NARR; ++n) { Fld d; d.t = turb.slot[(size_t)slot] + (size_t)n * n3; d.nk = g.npz; compact_out(d, 0, out[n]); }
+  return true;
+}
+
+// ---- linearised RAS convection (convection.h) --------------------------------------------------------------------------------------------
+// fv3lm_convection_create: the slots (what set saw of the trajectory, packed columns), the table, SIGE, the four sources of the
+// perturbation and the work spaces, checkpoints and tape of one batch of columns.  All device memory of the feature is allocated here.
+inline bool Dynamics::conv_create(int nslots, const RasParams* p, int do_phy_mst) {
+  const char* who = "fv3lm_convection_create";
+  auto no = [&](const std::string& m) { err = std::string(who) + ": " + m; return false; };
+  if (conv.nslots > 0) return no("already created for this handle");
+  if (nslots < 1) return no("nslots < 1");
+  if (!p) return no("null parameters");
+  if (do_phy_mst < 1 || do_phy_mst > 2) return no("do_phy_mst outside 1..2");
+  if (ak_host.empty()) return no("the handle has no ak, bk (PREF = ak + bk p00 gives ICMIN and SIGE)");
+  if (nq < 1) return no("nq < 1 (convection reads and writes qv = q1)");
+  for (int n = 0; n < 25; ++n) if (turb_stored_nonfinite(&p->r[n])) return no("a value that is not finite in the parameters");
+  const int lm = g.npz; const size_t nc = conv_ncol();
+  std::vector<double> sige((size_t)lm + 1);
+  int cnt = 0;
+  for (int l = 0; l <= lm; ++l) { sige[(size_t)l] = ak_host[(size_t)l] + bk_host[(size_t)l] * 100000.0; if (sige[(size_t)l] < 3000.0) ++cnt; }
+  const double pb = sige[(size_t)lm];
+  for (double& x : sige) x = x / pb;
+  Convection& c = conv;
+  c.nb = (int)(nc < (size_t)RAS_BATCH ? nc : (size_t)RAS_BATCH);
+  const size_t kw = (size_t)(lm + 2 < 7 ? 7 : lm + 2), nb = (size_t)c.nb;
+  const size_t b_slot = conv_slot_doubles() * 8, b_gw = RAS_NG * kw * nb * 8, b_tw = 2 * (size_t)RAS_NT * kw * nb * 8, b_ew = ((size_t)RAS_NT + RAS_NE) * kw * nb * 8,
+               b_ck = (5 * (size_t)lm + 1) * kw * nb * 8, b_src = 4 * nc * lm * 8;
+  const int cap = RAS_TAPE_PER_LEVEL * (int)kw;
+  const size_t b_tape = (size_t)cap * nb * (sizeof(TapePart) + sizeof(TapeIdx) + 8);
+  const size_t total = (size_t)nslots * (b_slot + nc * 4) + b_gw + b_tw + b_ew + b_ck + b_src + b_tape + (size_t)blc::TABLESIZE * 8 + sige.size() * 8 + 8;
+  if (std::getenv("FV3LM_VERBOSE"))
+    std::fprintf(stderr, "fv3lm: convection arena %zu bytes: %d slot(s) x %zu, batch of %d columns: work %zu, checkpoints %zu, tape %zu (%d entries a column); sources %zu\n",
+                 total, nslots, b_slot + nc * 4, c.nb, b_gw + b_tw + b_ew, b_ck, b_tape, cap, b_src);
+  const bool clean = sticky_error().empty();
+  bool ok = true;
+  // the slots and their lists are one block each, so that a request that cannot fit fails in one allocation
+  const bool fits = (size_t)nslots <= ((size_t)1 << 62) / (b_slot + nc * 4);
+  double* sb = fits ? (double*)dev_alloc((size_t)nslots * b_slot) : nullptr; int* lb = fits ? (int*)dev_alloc((size_t)nslots * nc * 4) : nullptr;
+  ok = sb && lb;
+  c.slot_block = sb; c.list_block = lb;
+  if (ok) for (int n = 0; n < nslots; ++n) { c.slot.push_back(sb + (size_t)n * (b_slot / 8)); c.list.push_back(lb + (size_t)n * nc); }
+  c.gw = (double*)dev_alloc(b_gw); c.tw = (double*)dev_alloc(b_tw); c.ew = (double*)dev_alloc(b_ew); c.ck = (double*)dev_alloc(b_ck); c.src = (double*)dev_alloc(b_src);
+  c.tbl = (double*)dev_alloc((size_t)blc::TABLESIZE * 8); c.sige = (double*)dev_alloc(sige.size() * 8); c.flag = (int*)dev_alloc(8);
+  c.tape.part = (TapePart*)dev_alloc((size_t)cap * nb * sizeof(TapePart)); c.tape.idx = (TapeIdx*)dev_alloc((size_t)cap * nb * sizeof(TapeIdx));
+  c.tape.adj = (double*)dev_alloc((size_t)cap * nb * 8); c.tape.overflow = c.flag ? c.flag + 1 : nullptr; c.tape.stride = nb; c.tape.cap = cap;
+  ok = ok && c.gw && c.tw && c.ew && c.ck && c.src && c.tbl && c.sige && c.flag && c.tape.part && c.tape.idx && c.tape.adj;
+  if (!ok) {
+    err = std::string(who) + ": allocation of " + std::to_string(total) + " bytes failed" + (sticky_error().empty() ? std::string() : ": " + sticky_error());
+    if (clean) sticky_error().clear();
+    conv_destroy();
+    return false;
+  }
+  { const std::vector<double> x = bl_esinit(); h2d(ex, c.tbl, x.data(), x.size() * 8); }
+  h2d(ex, c.sige, sige.data(), sige.size() * 8);
+  c.p = *p; c.mst = do_phy_mst; c.icmin = cnt > 1 ? cnt : 1;
+  c.set.assign((size_t)nslots, 0); c.nactive.assign((size_t)nslots, 0); c.nslots = nslots;
+  return true;
+}
+inline void Dynamics::conv_destroy() {
+  dev_free(conv.slot_block); dev_free(conv.list_block);
+  dev_free(conv.gw); dev_free(conv.tw); dev_free(conv.ew); dev_free(conv.ck); dev_free(conv.src); dev_free(conv.tbl); dev_free(conv.sige); dev_free(conv.flag);
+  dev_free(conv.tape.part); dev_free(conv.tape.idx); dev_free(conv.tape.adj);
+  conv = Convection{};
+}
+inline bool Dynamics::conv_slot_ok(const char* who, int slot, bool need_set) {
+  if (conv.nslots == 0) { err = std::string(who) + ": call fv3lm_convection_create first"; return false; }
+  if (slot < 0 || slot >= conv.nslots) { err = std::string(who) + ": slot " + std::to_string(slot) + " out of range (0.." + std::to_string(conv.nslots - 1) + ")"; return false; }
+  if (need_set && !conv.set[(size_t)slot]) { err = std::string(who) + ": slot " + std::to_string(slot) + " was never set (fv3lm_convection_set)"; return false; }
+  return true;
+}
+inline RasArgs Dynamics::conv_args(int slot) {      // all resident tiles at once: a column does not know where it lies
+  RasArgs a; a.g = g; a.ntile = ntile_all; a.lm = g.npz; a.icmin = conv.icmin; a.mst = conv.mst;
+  a.u = ex.sh(f("u")); a.v = ex.sh(f("v")); a.pt = ex.sh(f("pt")); a.delp = ex.sh(f("delp")); a.q1 = ex.sh(q[0]);
+  a.slot = conv.slot[(size_t)slot]; a.nc = conv_ncol(); a.list = nullptr; a.first = 0; a.n = 0;
+  a.gw = conv.gw; a.tw = conv.tw; a.ew = conv.ew; a.ck = conv.ck; a.tape = conv.tape; a.nb = conv.nb; a.src = conv.src;
+  a.tbl = conv.tbl; a.sige = conv.sige; a.p = conv.p;
+  a.dt = bdt; a.ptop = opt.ptop; a.akap = opt.akap; a.p00k = std::pow(1.0e5, opt.akap);
+  a.flag = conv.flag;
+  return a;
+}
+// the slot takes the trajectory from the resident u v pt(= T) delp q1 at this call; RASE0, the two filters and the list of DOCONVEC columns
+inline bool Dynamics::conv_set(int slot, const double* ts, const double* frland, const double* kcbl) {
+  const char* who = "fv3lm_convection_set";
+  auto no = [&](const std::string& m) { err = std::string(who) + ": " + m; return false; };
+  if (!conv_slot_ok(who, slot, false)) return false;
+  if (!ts || !frland || !kcbl) return no("null array");
+  const size_t nc = conv_ncol(); const int lm = g.npz;
+  for (size_t n = 0; n < nc; ++n) {
+    if (turb_stored_nonfinite(ts + n) || turb_stored_nonfinite(frland + n) || turb_stored_nonfinite(kcbl + n)) return no("a value that is not finite in ts, frland or kcbl");
+    const long k = std::lround(kcbl[n]);
+    if (k < conv.icmin + 1 || k > lm) return no("kcbl = " + std::to_string(k) + " outside ICMIN+1 .. npz = " + std::to_string(conv.icmin + 1) + " .. " + std::to_string(lm));
+  }
+  conv.set[(size_t)slot] = 0;
+  std::vector<double> kc(nc);
+  for (size_t n = 0; n < nc; ++n) kc[n] = (double)std::lround(kcbl[n]);      // nint
+  RasArgs a = conv_args(slot);
+  h2d(ex, &a.SC(SC_TS, 0), ts, nc * 8); h2d(ex, &a.SC(SC_FRLAND, 0), frland, nc * 8); h2d(ex, &a.SC(SC_KCBL, 0), kc.data(), nc * 8);
+  dev_zero(ex, conv.flag, 8);
+  a.first = 0; a.n = (int)nc;
+  run_ras(ex, -2, a);
+  int flag[2] = {0, 0};
+  d2h(ex, flag, conv.flag, sizeof flag);
+  if (flag[0]) return no("a value that is not finite in the resident trajectory (slot " + std::to_string(slot) + " is not set)");
+  for (size_t first = 0; first < nc; first += (size_t)conv.nb) { a.first = (int)first; a.n = (int)(nc - first < (size_t)conv.nb ? nc - first : (size_t)conv.nb); run_ras(ex, -1, a); }
+  std::vector<double> dc(nc);
+  d2h(ex, dc.data(), &a.SC(SC_DOCONVEC, 0), nc * 8);
+  std::vector<int> list;
+  for (size_t n = 0; n < nc; ++n) if (dc[n] == 1.0) list.push_back((int)n);
+  if (!list.empty()) h2d(ex, conv.list[(size_t)slot], list.data(), list.size() * 4);
+  conv.nactive[(size_t)slot] = (int)list.size();
+  if (!sticky_error().empty()) { err = sticky_error(); return false; }
+  conv.set[(size_t)slot] = 1;
+  return true;
+}
+inline bool Dynamics::conv_get(int slot, double* const* out6, int* doconvec, double* jac2) {
+  const char* who = "fv3lm_convection_get";
+  if (!conv_slot_ok(who, slot, true)) return false;
+  if (!out6 || !doconvec) { err = std::string(who) + ": null array"; return false; }
+  for (int n = 0; n < 6; ++n) if (!out6[n]) { err = std::string(who) + ": null array"; return false; }
+  const size_t nc = conv_ncol(), pc = (size_t)g.tx * g.ty; const int lm = g.npz;
+  const RasArgs a = conv_args(slot);
+  std::vector<double> buf((size_t)(lm + 1) * nc);
+  auto unpack = [&](int v, double* dst) {      // [level][column] -> [tile][level][point]
+    d2h(ex, buf.data(), &a.S(v, 0, 0), buf.size() * 8);
+    for (size_t col = 0; col < nc; ++col) for (int l = 0; l < lm; ++l) dst[((col / pc) * lm + l) * pc + col % pc] = buf[(size_t)l * nc + col];
+  };
+  for (int n = 0; n < 6; ++n) unpack(S_OUT + n, out6[n]);
+  if (jac2) { unpack(S_JAC, jac2); unpack(S_JAC + 1, jac2 + (size_t)lm * nc); }
+  d2h(ex, buf.data(), &a.SC(SC_DOCONVEC, 0), nc * 8);
+  for (size_t n = 0; n < nc; ++n) doconvec[n] = (int)buf[n];
+  return true;
+}
+inline bool Dynamics::conv_sources(int put, double* const* src4) {
+  const char* who = "fv3lm_convection_sources";
+  if (conv.nslots == 0) { err = std::string(who) + ": call fv3lm_convection_create first"; return false; }
+  if (!src4) { err = std::string(who) + ": null array"; return false; }
+  for (int n = 0; n < 4; ++n) if (!src4[n]) { err = std::string(who) + ": null array"; return false; }
+  const size_t n3c = conv_ncol() * g.npz;
+  if (put) for (size_t n = 0; n < 4 * n3c; ++n) if (turb_stored_nonfinite(src4[n / n3c] + n % n3c)) { err = std::string(who) + ": a value that is not finite"; return false; }
+  for (int n = 0; n < 4; ++n) { if (put) h2d(ex, conv.src + (size_t)n * n3c, src4[n], n3c * 8); else d2h(ex, src4[n], conv.src + (size_t)n * n3c, n3c * 8); }
+  return true;
+}
+// the table the kernels look up (ESINIT) as it lies on the device, and the nine constants they use, in the order of the fixture
+inline bool Dynamics::conv_table(double* table, double* constants) {
+  const char* who = "fv3lm_convection_table";
+  if (conv.nslots == 0) { err = std::string(who) + ": call fv3lm_convection_create first"; return false; }
+  if (!table || !constants) { err = std::string(who) + ": null array"; return false; }
+  d2h(ex, table, conv.tbl, (size_t)blc::TABLESIZE * 8);
+  const double c[9] = {rasc::CP, rasc::ALHL, rasc::GRAV, rasc::RGAS, rasc::H2OMW, rasc::AIRMW, rasc::VIREPS, blc::P00, blc::KAPPA};
+  for (int n = 0; n < 9; ++n) constants[n] = c[n];
+  return true;
+}
+// DOCONVEC columns only, in dense batches over the slot's list.  Tangent: the sources are cleared, then written in the active columns;
+// adjoint: the sources are the incoming adjoints, consumed and cleared.  The slot is read only.
+inline bool Dynamics::conv_run(int slot, int mode) {
+  const char* who = "fv3lm_convection";
+  if (!conv_slot_ok(who, slot, false)) return false;
+  if (mode < 0 || mode > 2) { err = std::string(who) + ": bad mode"; return false; }
+  if (!conv_slot_ok(who, slot, true)) return false;
+  RasArgs a = conv_args(slot);
+  a.list = conv.list[(size_t)slot];
+  const size_t n3c = conv_ncol() * g.npz;
+  const int na = conv.nactive[(size_t)slot];
+  if (mode == MODE_TL) dev_zero(ex, conv.src, 4 * n3c * 8);
+  if (mode == MODE_AD) dev_zero(ex, conv.flag, 8);
+  for (int first = 0; first < na; first += conv.nb) { a.first = first; a.n = na - first < conv.nb ? na - first : conv.nb; run_ras(ex, mode, a); }
+  if (mode == MODE_AD) {
+    dev_zero(ex, conv.src, 4 * n3c * 8);
+    int flag[2] = {0, 0};
+    d2h(ex, flag, conv.flag, sizeof flag);
+    if (flag[1]) { err = std::string(who) + ": the tape of a cloud type overflowed (RAS_TAPE_PER_LEVEL); the adjoint fields are not valid"; return false; }
+  }
+  if (!sticky_error().empty()) { err = sticky_error(); return false; }
   return true;
 }
 

@@ -232,6 +232,45 @@ int fv3lm_turbulence_get(fv3lm_handle* h, int slot, double* const* out) {
   if (!h->d.turb_get(slot, out)) return fail(h->d.err);
   return status(h);
 }
+// linearised RAS convection (convection.h)
+void fv3lm_ras_default_params(fv3lm_ras_params* p, int im) {      // fv3jedi_lm_moist_mod.F90:120-148
+  if (!p) return;
+  const double r[25] = {1.000, 0.05, 0.0, 8.0e-4, 1800., 43200.0, -300., 4.0, 0.0, 200., 7.5e-4, 1.0, -1.0, 1.3, 1.3, 263., 0.5, 1.0, 0.0, 0.1, 0.8, 1.0, 0.0, 0.5, 0.65};
+  for (int n = 0; n < 25; ++n) p->r[n] = r[n];
+  const long imsize = 4L * im;
+  p->r[22] = imsize <= 200 ? 4000.0 : imsize <= 400 ? 2000.0 : imsize <= 800 ? 700.0 : 450.0;
+}
+int fv3lm_convection_create(fv3lm_handle* h, int nslots, const fv3lm_ras_params* p, int do_phy_mst) {
+  if (!h) return fail("fv3lm_convection_create: null handle");
+  static_assert(sizeof(fv3lm_ras_params) == sizeof(RasParams), "fv3lm_ras_params and RasParams must agree");
+  if (!h->d.conv_create(nslots, reinterpret_cast<const RasParams*>(p), do_phy_mst)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_convection_set(fv3lm_handle* h, int slot, const double* ts, const double* frland, const double* kcbl) {
+  if (!h) return fail("fv3lm_convection_set: null handle");
+  if (!h->d.conv_set(slot, ts, frland, kcbl)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_convection_get(fv3lm_handle* h, int slot, double* const* out6, int* doconvec, double* jac2) {
+  if (!h) return fail("fv3lm_convection_get: null handle");
+  if (!h->d.conv_get(slot, out6, doconvec, jac2)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_convection_sources(fv3lm_handle* h, int put, double* const* src4) {
+  if (!h) return fail("fv3lm_convection_sources: null handle");
+  if (!h->d.conv_sources(put, src4)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_convection_table(fv3lm_handle* h, double* table, double* constants) {
+  if (!h) return fail("fv3lm_convection_table: null handle");
+  if (!h->d.conv_table(table, constants)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_convection(fv3lm_handle* h, int slot, int mode) {
+  if (!h) return fail("fv3lm_convection: null handle");
+  if (!h->d.conv_run(slot, mode)) return fail(h->d.err);
+  return status(h);
+}
 int fv3lm_step_tl(fv3lm_handle* h) { h->d.step_tl(); return status(h); }
 int fv3lm_step_nl(fv3lm_handle* h) { h->d.step_nl(); return status(h); }
 int fv3lm_step_ad(fv3lm_handle* h) { h->d.step_ad(); return status(h); }

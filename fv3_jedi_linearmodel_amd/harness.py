@@ -104,17 +104,23 @@ class CubeCase:
                  layout=1, loopback=False, **optkw):
         """rank/world: this process holds only cube.faces_of(rank, world, ntiles) (one process per GPU); state and metrics are the
         corresponding slices of the same global fields, so results can be compared with a single-process run.
-        loopback: the rows between this rank's own tiles go through the message path too (cube.split_table)."""
+        loopback: the rows between this rank's own tiles go through the message path too (cube.split_table).
+        levels=(ak, bk): hybrid coefficients [npz+1] handed to the library in place of the state's own (column physics that reads
+        PREF = ak + bk p00; the synthetic state is left as it is)."""
         from . import cube
         self.n = n
         self.layout = layout
         self.nt = self.nx = self.ny = n // layout
         self.npz, self.nq = npz, nq
         self.tau, self.rf_cutoff = optkw.pop("tau", 0.0), optkw.pop("rf_cutoff", 0.0)
+        levels = optkw.pop("levels", None)
         self.opt = default_options(**optkw)
         self.metrics, self.da_min, self.da_min_c, self.edge, self.ecorner, self.geo = cube.cubed_sphere_metrics(n)
         self.c2l = self.geo["c2l"]
         self.traj, self.phis, self.ak, self.bk = cube.cube_fields(n, npz, self.geo, seed, "traj", self.opt)
+        if levels is not None:
+            self.ak, self.bk = (np.array(x, dtype=np.float64) for x in levels)
+            assert self.ak.shape == self.bk.shape == (npz + 1,), "levels: ak, bk of npz+1 interfaces"
         self.pert = cube.cube_fields(n, npz, self.geo, seed + 1, "pert")
         aux = cube.cube_fields(n, npz, self.geo, seed + 11, "pert") if nq else None
         self.qtraj = [1e-3 * (m + 1) + 1e-2 * np.abs(aux["pt"] if m % 2 == 0 else 2e-3 * aux["delp"]) * (1.0 + 0.25 * m) for m in range(nq)]

@@ -237,6 +237,41 @@ typedef struct { double r[22]; int i[4]; } fv3lm_bl_params;
 void fv3lm_bl_default_params(fv3lm_bl_params* p, int kpblmin);
 int fv3lm_turbulence_set_driver(fv3lm_handle* h, int slot, const fv3lm_bl_params* p, double dt, const double* const* sfc, const double* qa,
                                 const double* qb, int cloud_mode, double* const* raw_out);
+/* Linearised relaxed Arakawa-Schubert convection (physics/moist/convection.F90 RASE, RASE0 with their tangents convection_tl.F90 and
+ * adjoint convection_ad.F90, and the part of fv3jedi_lm_moist_mod.F90 that concerns them: create :120-148, :226-238, set_ltraj :700-832 with
+ * jacobian_filter_tlm, step_nl / step_tl / step_ad up to the cloud scheme).  Column-local, like the turbulence: compact (isc:iec, jsc:jec
+ * [, npz]) arrays per resident tile, tile slowest; nothing outside is..ie x js..je is read or written; delp, w, delz, q2.. are not touched.
+ *   fv3lm_ras_params: RASPARAMS(1:25).  fv3lm_ras_default_params fills in create :120-148; entry 23 follows imsize = 4 im.
+ *   fv3lm_convection_create: nslots slots (one per trajectory time kept), do_phy_mst 1 | 2 (MAXCONDEP 1 | 10 of the heating-rate filter).
+ *       ICMIN and SIGE come from the handle's ak, bk; the table is ESINIT's; the MAPL constants are those of utils/MAPL_Constants.F90 in
+ *       double; p00 and kappa of T <-> theta are the options'.  ALL device memory of the feature is allocated here (FV3LM_VERBOSE=1
+ *       prints it) and freed by fv3lm_destroy.
+ *   fv3lm_convection_set: takes the trajectory from the RESIDENT u v pt(= T) delp q1 at the call (with dt, ptop of the handle) and ts,
+ *       frland, kcbl (nint of a real) of the host; runs RASE0 on copies, the heating-rate filter and the Jacobian filter (its loop is
+ *       L = 1, 1 in the reference: only the column of PT_pert = e_KCBL exists, thresholds 1e-4 and 1e-7) and lists the DOCONVEC columns.
+ *       A slot keeps what set saw and no run modifies it: this is the device's form of "a fresh set_ltraj every step".
+ *   fv3lm_convection_get: out6 = PTT_C QVT_C CNV_DQLDT_C CNV_MFD_C CNV_PRC3_C CNV_UPDF_C (npz deep), doconvec (one int a column), jac2
+ *       (NULL ok) = H_pert then M_pert of the Jacobian filter, npz deep each, zero where the heating-rate filter had already refused.
+ *   fv3lm_convection_sources: the four sources of the PERTURBATION, CNV_DQLDT CNV_MFD CNV_PRC3 CNV_UPDF (npz deep): put = 0 reads them
+ *       (after a tangent run), put = 1 writes them (the incoming adjoints, before an adjoint run).
+ *   fv3lm_convection: DOCONVEC columns only.  mode 0: RASE on the trajectory, u v T q1 written back (step_nl); 1: RASE_D on the
+ *       perturbation of u v pt q1, T -> theta by p00^kappa / pk in and back out, the sources cleared and then written in the active
+ *       columns; 2: RASE_B, theta = T pk / p00^kappa in and its inverse out, the sources are consumed and cleared.  Host order, as
+ *       fv3jedi_lm_mod.F90:161-187:  tangent  fv3lm_step_tl ; fv3lm_turbulence(1) ; fv3lm_convection(1)
+ *                                    adjoint  fv3lm_convection(2) ; fv3lm_turbulence(2) ; fv3lm_step_ad.
+ *   fv3lm_convection_table: diagnostics -- the 18301 entries of the saturation table as they lie on the device (ESINIT, 150 K .. 333 K in
+ *       steps of 0.01 K) and the nine constants of the kernels: CP ALHL GRAV RGAS H2OMW AIRMW VIREPS P00 KAPPA (MAPL_Constants in double).
+ *   Refused with a message, the slot left unset: before create or a second create; nslots < 1; do_phy_mst outside 1..2; a handle without
+ *   ak, bk; nq < 1; a slot out of range or never set; a mode outside 0..2; a NULL array; kcbl outside ICMIN+1 .. npz; a value that is
+ *   not finite; an allocation that fails. */
+typedef struct { double r[25]; } fv3lm_ras_params;
+void fv3lm_ras_default_params(fv3lm_ras_params* p, int im);
+int fv3lm_convection_create(fv3lm_handle* h, int nslots, const fv3lm_ras_params* p, int do_phy_mst);
+int fv3lm_convection_set(fv3lm_handle* h, int slot, const double* ts, const double* frland, const double* kcbl);
+int fv3lm_convection_get(fv3lm_handle* h, int slot, double* const* out6, int* doconvec, double* jac2);
+int fv3lm_convection_sources(fv3lm_handle* h, int put, double* const* src4);
+int fv3lm_convection(fv3lm_handle* h, int slot, int mode);
+int fv3lm_convection_table(fv3lm_handle* h, double* table, double* constants);
 /* Per-kernel HIP-event profile of everything launched between begin and end, on the library's stream:
  * lines "kernel count total_ms algorithmic_bytes".  Returns the buffer length needed. */
 int fv3lm_profile_begin(fv3lm_handle* h);

@@ -1,0 +1,80 @@
+"""-m gpu: the linearised RAS convection (fv3lm_convection_*; csrc/convection.h) through the C-ABI of the HIP library on an MI355X,
+against the fixture recorded from the reference's own RASE0, RASE0_D, RASE_D, RASE_B (tests/golden/convection_ref.npz).
+Checks: tests/convection_checks.py."""
+import pytest
+import convection_checks as CC
+
+pytestmark = pytest.mark.gpu
+
+BACKEND = "hip"
+LMS = [40, 72, 20]
+
+
+def tile(lm, face=None, nq=2, **kw):
+    """the periodic tile 12 x 10, or one 12 x 12 face of a C12 cube, on the fixture's levels"""
+    from common import Case
+    nx, ny = (12, 10) if face is None else (12, 12)
+    kw = kw or CC.case_kw(CC.fixture(lm))
+    return Case(nx=nx, ny=ny, npz=lm, n_split=2, dt=1800.0, nq=nq, backend=BACKEND, oracle=False, face=face, **kw)
+
+
+def cube(lm, layout=1, nq=1, n=12):
+    from common import CubeCase
+    return CubeCase(n=n, npz=lm, n_split=1, k_split=1, dt=1800.0, nq=nq, backend=BACKEND, layout=layout, **CC.case_kw(CC.fixture(lm)))
+
+
+@pytest.mark.parametrize("lm", LMS)
+@pytest.mark.parametrize("face", [None, 2])
+def test_set_against_the_reference(face, lm):
+    """check 1: PTT_C QVT_C and the four _C sources of RASE0 and the Jacobian column of RASE0_D within the fixture's tolerance (m x the
+    reference's own movement under 1e-15 perturbations, floor 1e-12), every column; DOCONVEC equal; ras_default_params, the device's table at the fixture's 184 samples and the kernels' constants equal"""
+    CC.check_set(tile(lm, face), lm)
+
+
+@pytest.mark.parametrize("lm", LMS)
+@pytest.mark.parametrize("face", [None, 2])
+def test_modes_against_the_reference(face, lm):
+    """checks 2 and 4: tangent against RASE_D, adjoint against RASE_B (the theta conversion restated in numpy, the four sources
+    compared), nonlinear against RASE's values; stable columns bitwise unchanged with zero sources"""
+    CC.check_modes(tile(lm, face), lm)
+
+
+@pytest.mark.parametrize("where", ["tile", "face", "six faces"])
+@pytest.mark.parametrize("lm", [40, 20])
+def test_dot_product(where, lm):
+    """check 3: <TL x, y> = <x, AD y> over the eight fields at 1e-12"""
+    CC.check_dot_product(tile(lm) if where == "tile" else tile(lm, 2) if where == "face" else cube(lm), lm)
+
+
+def test_position_independence():
+    """check 5: the L40 columns dealt over the six faces of a C16 cube and over its 2 x 2 sub-face layout (a tile needs 8 cells, so
+    C12 cannot be cut): every column's set outputs, Jacobian column, tangent fields and sources as on the small tile, bitwise"""
+    CC.check_position(lambda: tile(40, None, 1), lambda L: cube(40, L, 1, 16), 40, 2)
+
+
+@pytest.mark.parametrize("where", ["tile", "six faces"])
+def test_nothing_else_moves(where):
+    """check 6: halos, far edge rows, delp, q2.., the other slot, the turbulence slot and the host's arrays bitwise unchanged; set,
+    step_tl, run: the slot did not follow the resident trajectory"""
+    CC.check_nothing_else_moves(tile(20, None, 3) if where == "tile" else cube(20, 1, 3), 20)
+
+
+def test_a_handle_without_convection_steps_as_before():
+    """check 6, last item"""
+    CC.check_untouched_handle(lambda: tile(20, None, 2))
+
+
+def test_refusals():
+    """check 7: every item of the refusal list by its message, the slot left unset, a following good call works; the failed allocation by a slot count no machine can hold"""
+    CC.check_refusals(lambda nq, npz, **kw: tile(npz, None, nq, **kw))
+
+
+def test_at_size_c48l72():
+    """check 8: six faces C48 L72, the harness state with a moistened lower troposphere and synthetic surface fields: everything finite,
+    the dot product at 1e-12; the HIP-event times of set, tangent and adjoint and the active-column count are printed"""
+    from common import CubeCase
+    c = CubeCase(n=48, npz=72, n_split=2, k_split=1, dt=900.0, nq=2, backend=BACKEND)
+    times, nact, ncol, res = CC.check_at_size(c, 3, 1e-12)
+    for t in times:
+        print("convection C48 L72: " + " ".join("%s %.3f ms" % kv for kv in sorted(t.items())))
+    print("active columns %d of %d; dot product residual %.2e" % (nact, ncol, res))
