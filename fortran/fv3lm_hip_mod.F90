@@ -25,6 +25,8 @@ module fv3lm_hip_mod
   public :: fv3lm_ras_params, fv3lm_hip_ras_default_params, fv3lm_hip_convection_create, fv3lm_hip_convection_set
   public :: fv3lm_hip_convection_get, fv3lm_hip_convection_get_sources, fv3lm_hip_convection_put_sources, fv3lm_hip_convection
   public :: fv3lm_hip_convection_table
+  public :: fv3lm_cloud_params, fv3lm_hip_cloud_default_params, fv3lm_hip_cloud_create, fv3lm_hip_cloud_set, fv3lm_hip_cloud_get
+  public :: fv3lm_hip_cloud_get_cfcn, fv3lm_hip_cloud_put_cfcn, fv3lm_hip_cloud
 
   integer, parameter :: ng = 3   ! halo width, tools/fv_mp_nlm_mod.F90:67
 
@@ -67,6 +69,10 @@ module fv3lm_hip_mod
   type, bind(C) :: fv3lm_ras_params
     real(c_double) :: r(25)
   end type fv3lm_ras_params
+  !> CLOUDPARAMS(1:57) of the moist physics (fv3lm_cloud_params of include/fv3lm.h)
+  type, bind(C) :: fv3lm_cloud_params
+    real(c_double) :: r(57)
+  end type fv3lm_cloud_params
 
   type :: fv3lm_hip_type
     type(c_ptr) :: handle = c_null_ptr
@@ -268,6 +274,43 @@ module fv3lm_hip_mod
       integer(c_int) :: rc
     end function
     function c_convection(h, slot, mode) bind(C, name="fv3lm_convection") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), value :: slot, mode
+      integer(c_int) :: rc
+    end function
+    subroutine c_cloud_default_params(p, im) bind(C, name="fv3lm_cloud_default_params")
+      import :: fv3lm_cloud_params, c_int
+      type(fv3lm_cloud_params), intent(out) :: p
+      integer(c_int), value :: im
+    end subroutine
+    function c_cloud_create(h, p, iqi, iql) bind(C, name="fv3lm_cloud_create") result(rc)
+      import :: fv3lm_cloud_params, c_ptr, c_int
+      type(c_ptr), value :: h
+      type(fv3lm_cloud_params), intent(in) :: p
+      integer(c_int), value :: iqi, iql
+      integer(c_int) :: rc
+    end function
+    function c_cloud_set(h, slot, qls, qcn, cfcn, khl, khu) bind(C, name="fv3lm_cloud_set") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h, qls, qcn, cfcn, khl, khu
+      integer(c_int), value :: slot
+      integer(c_int) :: rc
+    end function
+    function c_cloud_get(h, slot, out8, frac4, pertmod) bind(C, name="fv3lm_cloud_get") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h, pertmod
+      integer(c_int), value :: slot
+      type(c_ptr), intent(in) :: out8(*), frac4(*)
+      integer(c_int) :: rc
+    end function
+    function c_cloud_cfcn(h, put, cfcn) bind(C, name="fv3lm_cloud_cfcn") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h, cfcn
+      integer(c_int), value :: put
+      integer(c_int) :: rc
+    end function
+    function c_cloud(h, slot, mode) bind(C, name="fv3lm_cloud") result(rc)
       import :: c_ptr, c_int
       type(c_ptr), value :: h
       integer(c_int), value :: slot, mode
@@ -594,6 +637,69 @@ contains
     integer, intent(in) :: slot, mode
     call check(c_convection(self%handle, int(slot - 1, c_int), int(mode, c_int)), 'convection')
   end subroutine fv3lm_hip_convection
+
+  !> Linearised cloud scheme (physics/moist: CLOUD_DRIVER, CLOUD_DRIVER_D, CLOUD_DRIVER_B and the cloud part of set_ltraj :834-874).
+  !! Slots are those of the convection, numbered from 1; arrays are the host's own, (isc:iec, jsc:jec[, npz]).  CLOUDPARAMS as create
+  !! :151-211 sets them (im = conf%im).  iqi, iql: the tracers (2..nq) that carry cloud ice and cloud liquid on the device.
+  subroutine fv3lm_hip_cloud_default_params(p, im)
+    type(fv3lm_cloud_params), intent(out) :: p
+    integer, intent(in) :: im
+    call c_cloud_default_params(p, int(im, c_int))
+  end subroutine fv3lm_hip_cloud_default_params
+
+  subroutine fv3lm_hip_cloud_create(self, p, iqi, iql)
+    type(fv3lm_hip_type), intent(in) :: self
+    type(fv3lm_cloud_params), intent(in) :: p
+    integer, intent(in) :: iqi, iql
+    call check(c_cloud_create(self%handle, p, int(iqi, c_int), int(iql, c_int)), 'cloud_create')
+  end subroutine fv3lm_hip_cloud_create
+
+  !> In place of the cloud part of set_ltraj (:834-874): call after fv3lm_hip_convection_set of the same slot.
+  subroutine fv3lm_hip_cloud_set(self, slot, qls, qcn, cfcn, khl, khu)
+    type(fv3lm_hip_type), intent(in) :: self
+    integer, intent(in) :: slot
+    real(c_double), intent(in), target, contiguous :: qls(:, :, :), qcn(:, :, :), cfcn(:, :, :), khl(:, :), khu(:, :)
+    call check(c_cloud_set(self%handle, int(slot - 1, c_int), c_loc(qls), c_loc(qcn), c_loc(cfcn), c_loc(khl), c_loc(khu)), 'cloud_set')
+  end subroutine fv3lm_hip_cloud_set
+
+  !> out(:, :, :, 1:8) = theta q QI_ls QL_ls QI_con QL_con CF_ls CF_con after CLOUD_DRIVER in values, frac(:, :, :, 1:4) = ILSF ICNF LLSF
+  !! LCNF, pertmod = the switch cloud_pertmod of every cell
+  subroutine fv3lm_hip_cloud_get(self, slot, out, frac, pertmod)
+    type(fv3lm_hip_type), intent(in) :: self
+    integer, intent(in) :: slot
+    real(c_double), intent(inout), target, contiguous :: out(:, :, :, :), frac(:, :, :, :)
+    integer(c_int), intent(inout), target, contiguous :: pertmod(:, :, :)
+    type(c_ptr) :: d(8), f(4)
+    integer :: n
+    do n = 1, 8
+      d(n) = c_loc(out(1, 1, 1, n))
+    end do
+    do n = 1, 4
+      f(n) = c_loc(frac(1, 1, 1, n))
+    end do
+    call check(c_cloud_get(self%handle, int(slot - 1, c_int), d, f, c_loc(pertmod)), 'cloud_get')
+  end subroutine fv3lm_hip_cloud_get
+
+  !> the perturbation's convective cloud fraction, which lives on the device: read after a run ...
+  subroutine fv3lm_hip_cloud_get_cfcn(self, cfcn)
+    type(fv3lm_hip_type), intent(in) :: self
+    real(c_double), intent(inout), target, contiguous :: cfcn(:, :, :)
+    call check(c_cloud_cfcn(self%handle, 0_c_int, c_loc(cfcn)), 'cloud_cfcn (get)')
+  end subroutine fv3lm_hip_cloud_get_cfcn
+
+  !> ... and given before one
+  subroutine fv3lm_hip_cloud_put_cfcn(self, cfcn)
+    type(fv3lm_hip_type), intent(in) :: self
+    real(c_double), intent(in), target, contiguous :: cfcn(:, :, :)
+    call check(c_cloud_cfcn(self%handle, 1_c_int, c_loc(cfcn)), 'cloud_cfcn (put)')
+  end subroutine fv3lm_hip_cloud_put_cfcn
+
+  !> mode 0 step_nl, 1 step_tl (after fv3lm_hip_convection(1)), 2 step_ad (before fv3lm_hip_convection(2)) of the moist physics, cloud scheme
+  subroutine fv3lm_hip_cloud(self, slot, mode)
+    type(fv3lm_hip_type), intent(in) :: self
+    integer, intent(in) :: slot, mode
+    call check(c_cloud(self%handle, int(slot - 1, c_int), int(mode, c_int)), 'cloud')
+  end subroutine fv3lm_hip_cloud
 
   !> Replaces compute_fv3_pressures_tlm + fv_dynamics_tlm (fv3jedi_lm_dynamics_mod.F90:404-438).
   subroutine fv3lm_hip_step_tl(self)

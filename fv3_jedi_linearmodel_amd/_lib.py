@@ -27,6 +27,11 @@ class RasParams(C.Structure):
     _fields_ = [("r", C.c_double * 25)]
 
 
+class CloudParams(C.Structure):
+    """fv3lm_cloud_params: CLOUDPARAMS(1:57) of the moist physics in the reference's order"""
+    _fields_ = [("r", C.c_double * 57)]
+
+
 class Fv3LmLibrary:
     def __init__(self, path):
         if not os.path.exists(path):
@@ -382,6 +387,58 @@ class Dycore:
         """RAS convection in the DOCONVEC columns of the slot: NL on the trajectory, TL on the perturbation, AD on the adjoint"""
         self.lib.L.fv3lm_convection.argtypes = [C.c_void_p, C.c_int, C.c_int]
         self._chk(self.lib.L.fv3lm_convection(self.h, int(slot), int(mode)))
+
+    # ---- linearised cloud scheme (physics/moist/cloud.F90; csrc/cloud.h), compact arrays [ntile, (npz,) ny, nx] ----
+    CLOUD_NAMES = ("th", "q", "QI_ls", "QL_ls", "QI_con", "QL_con", "CF_ls", "CF_con")
+    FRAC_NAMES = ("ILSF", "ICNF", "LLSF", "LCNF")
+
+    def cloud_default_params(self, im):
+        """fv3lm_cloud_default_params: CLOUDPARAMS of create :151-211; entries 42 and 46 follow imsize = 4 im"""
+        p = CloudParams()
+        self.lib.L.fv3lm_cloud_default_params.argtypes = [C.POINTER(CloudParams), C.c_int]
+        self.lib.L.fv3lm_cloud_default_params.restype = None
+        self.lib.L.fv3lm_cloud_default_params(C.byref(p), int(im))
+        return p
+
+    def cloud_create(self, params, iqi, iql):
+        """fv3lm_cloud_create: after convection_create; one cloud slot per convection slot; iqi, iql: the tracers of cloud ice and liquid"""
+        self.lib.L.fv3lm_cloud_create.argtypes = [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int]
+        self._chk(self.lib.L.fv3lm_cloud_create(self.h, None if params is None else C.byref(params), int(iqi), int(iql)))
+
+    def cloud_set(self, slot, qls, qcn, cfcn, khl, khu):
+        """after convection_set of the same slot: QLS QCN cfcn [ntile, npz, ny, nx], khl khu [ntile, ny, nx] (None: NULL)"""
+        a = [None if x is None else self._compact(x, self.dims.npz) for x in (qls, qcn, cfcn)] + [None if x is None else self._compact(x) for x in (khl, khu)]
+        self.lib.L.fv3lm_cloud_set.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]
+        self._chk(self.lib.L.fv3lm_cloud_set(self.h, int(slot), *[None if x is None else _ptr(x) for x in a]))
+
+    def cloud_get(self, slot, out=True, frac=True, pertmod=True):
+        """-> (dict by CLOUD_NAMES, dict by FRAC_NAMES, pertmod int32), each [ntile, npz, ny, nx] or None where not asked for"""
+        shp = (self.dims.ntile, self.dims.npz, self.dims.ny, self.dims.nx)
+        o = {n: np.empty(shp) for n in self.CLOUD_NAMES} if out else None
+        f = {n: np.empty(shp) for n in self.FRAC_NAMES} if frac else None
+        pm = np.zeros(shp, dtype=np.int32) if pertmod else None
+        self.lib.L.fv3lm_cloud_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(_dp), C.POINTER(_dp), C.POINTER(C.c_int)]
+        self._chk(self.lib.L.fv3lm_cloud_get(self.h, int(slot), None if o is None else (_dp * 8)(*[_ptr(o[n]) for n in self.CLOUD_NAMES]),
+                                             None if f is None else (_dp * 4)(*[_ptr(f[n]) for n in self.FRAC_NAMES]),
+                                             None if pm is None else pm.ctypes.data_as(C.POINTER(C.c_int))))
+        return o, f, pm
+
+    def cloud_cfcn(self, cfcn=None, null=False):
+        """cfcn None: -> the perturbation's convective cloud fraction [ntile, npz, ny, nx]; else put it (null: pass NULL)"""
+        self.lib.L.fv3lm_cloud_cfcn.argtypes = [C.c_void_p, C.c_int, _dp]
+        if null:
+            self._chk(self.lib.L.fv3lm_cloud_cfcn(self.h, 1, None))
+        if cfcn is None:
+            out = np.empty((self.dims.ntile, self.dims.npz, self.dims.ny, self.dims.nx))
+            self._chk(self.lib.L.fv3lm_cloud_cfcn(self.h, 0, _ptr(out)))
+            return out
+        keep = self._compact(cfcn, self.dims.npz)
+        self._chk(self.lib.L.fv3lm_cloud_cfcn(self.h, 1, _ptr(keep)))
+
+    def cloud(self, slot, mode):
+        """the cloud scheme in every column of the slot: NL writes the trajectory tracers iqi, iql; TL on the perturbation; AD on the adjoint"""
+        self.lib.L.fv3lm_cloud.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        self._chk(self.lib.L.fv3lm_cloud(self.h, int(slot), int(mode)))
 
     # ---- the host's boundary copies on the device (compact arrays [ntile, nk, ny, nx], no halo) ----
     def _cptrs(self, d, names, out=False):

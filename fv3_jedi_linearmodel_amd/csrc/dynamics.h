@@ -9,6 +9,7 @@
 #include "turbulence.h"
 #include "bldriver.h"
 #include "convection.h"
+#include "cloud.h"
 
 namespace fv3 {
 
@@ -185,6 +186,22 @@ struct Dynamics : Dycore {
   bool conv_table(double* table, double* constants);
   bool conv_run(int slot, int mode);
   void conv_destroy();
+  // Linearised cloud scheme (cloud.h; fv3lm_cloud_*): nothing allocated until cloud_create; one slot per convection slot
+  struct Cloud {
+    int created = 0, iqi = 0, iql = 0, nb = 0; CldParams p;
+    double* slot_block = nullptr; std::vector<double*> slot; std::vector<char> set;
+    double *gw = nullptr, *tw = nullptr, *ew = nullptr, *ck = nullptr, *cfcn = nullptr; int* flag = nullptr;
+    TapeMem tape;
+  } cld;
+  size_t cloud_slot_doubles() const { return ((size_t)CLD_NS * (g.npz + 1) + CLD_NSC) * conv_ncol(); }
+  bool cloud_create(const CldParams* p, int iqi, int iql);
+  bool cloud_slot_ok(const char* who, int slot, bool need_set);
+  CldArgs cloud_args(int slot);
+  bool cloud_set(int slot, const double* qls, const double* qcn, const double* cfcn, const double* khl, const double* khu);
+  bool cloud_get(int slot, double* const* out8, double* const* frac4, int* pertmod);
+  bool cloud_cfcn(int put, double* cfcn);
+  bool cloud_run(int slot, int mode);
+  void cloud_destroy();
   // one field between the host's compact array and the device state.  which: 0 trajectory, 1 perturbation / adjoint
   void compact_in(const Fld& f, int which, const double* host) {
     const size_t n = (size_t)ntile_all * f.nk * g.tx * g.ty;
@@ -320,6 +337,7 @@ inline bool Dynamics::init2(const double* ak, const double* bk) {
 inline void Dynamics::destroy2() {
   dev_free(stage_dev); stage_dev = nullptr;
   turb_destroy();
+  cloud_destroy();
   conv_destroy();
   dev_free(rf_lv); dev_free(rf_c2l); dev_free(rf_ck); dev_free(rf_pth.t); dev_free(rf_pth.p);
   dev_free(ak_dev); dev_free(bk_dev); if (remap_ws_own) dev_free(remap_ws); dev_free(cmax_dev);
@@ -907,6 +925,7 @@ inline bool Dynamics::conv_set(int slot, const double* ts, const double* frland,
     if (k < conv.icmin + 1 || k > lm) return no("kcbl = " + std::to_string(k) + " outside ICMIN+1 .. npz = " + std::to_string(conv.icmin + 1) + " .. " + std::to_string(lm));
   }
   conv.set[(size_t)slot] = 0;
+  if (cld.created) cld.set[(size_t)slot] = 0;      // the cloud slot reads this one: it has to be set again after it
   std::vector<double> kc(nc);
   for (size_t n = 0; n < nc; ++n) kc[n] = (double)std::lround(kcbl[n]);      // nint
   RasArgs a = conv_args(slot);
@@ -985,6 +1004,151 @@ inline bool Dynamics::conv_run(int slot, int mode) {
     int flag[2] = {0, 0};
     d2h(ex, flag, conv.flag, sizeof flag);
     if (flag[1]) { err = std::string(who) + ": the tape of a cloud type overflowed (RAS_TAPE_PER_LEVEL); the adjoint fields are not valid"; return false; }
+  }
+  if (!sticky_error().empty()) { err = sticky_error(); return false; }
+  return true;
+}
+
+// ---- linearised cloud scheme (cloud.h) -----------------------------------------------------------------------------------------------------
+// fv3lm_cloud_create: one slot per convection slot, the perturbation's convective cloud fraction and the work spaces, checkpoints and tape
+// of one batch of columns.  All device memory of the feature is allocated here.
+inline bool Dynamics::cloud_create(const CldParams* p, int iqi, int iql) {
+  const char* who = "fv3lm_cloud_create";
+  auto no = [&](const std::string& m) { err = std::string(who) + ": " + m; return false; };
+  if (conv.nslots == 0) return no("call fv3lm_convection_create first");
+  if (cld.created) return no("already created for this handle");
+  if (!p) return no("null parameters");
+  for (int n = 0; n < 57; ++n) if (turb_stored_nonfinite(&p->r[n])) return no("a value that is not finite in the parameters");
+  if ((int)p->r[56] != 1) return no("CLOUDPARAMS(57) = PDFFLAG /= 1 (only the top-hat PDF is built)");
+  if ((int)(p->r[34] + .001) < 1) return no("CLOUDPARAMS(35) = ICEFRPWR < 1");
+  if (iqi < 2 || iqi > nq || iql < 2 || iql > nq) return no("iqi = " + std::to_string(iqi) + ", iql = " + std::to_string(iql) + " outside 2..nq = 2.." + std::to_string(nq));
+  if (iqi == iql) return no("iqi = iql = " + std::to_string(iqi) + " (cloud ice and cloud liquid are two tracers)");
+  const int lm = g.npz, nslots = conv.nslots; const size_t nc = conv_ncol();
+  Cloud& c = cld;
+  c.nb = (int)(nc < (size_t)CLD_BATCH ? nc : (size_t)CLD_BATCH);
+  const size_t kw = (size_t)(lm + 2 < CLD_NSV + 2 ? CLD_NSV + 2 : lm + 2), nb = (size_t)c.nb;
+  const size_t b_slot = cloud_slot_doubles() * 8, b_gw = CLD_NG * kw * nb * 8, b_tw = 2 * (size_t)CLD_NE * kw * nb * 8, b_ew = 2 * (size_t)CLD_NE * kw * nb * 8,
+               b_ck = ((size_t)CLD_NCK + 1) * kw * nb * 8, b_cf = nc * lm * 8;
+  const int cap = CLD_TAPE;
+  const size_t b_tape = (size_t)cap * nb * (sizeof(TapePart) + sizeof(TapeIdx) + 8);
+  const size_t total = (size_t)nslots * b_slot + b_gw + b_tw + b_ew + b_ck + b_cf + b_tape + 8;
+  if (std::getenv("FV3LM_VERBOSE"))
+    std::fprintf(stderr, "fv3lm: cloud arena %zu bytes: %d slot(s) x %zu, batch of %d columns: work %zu, checkpoints %zu, tape %zu (%d entries a column); cfcn %zu\n",
+                 total, nslots, b_slot, c.nb, b_gw + b_tw + b_ew, b_ck, b_tape, cap, b_cf);
+  const bool clean = sticky_error().empty();
+  c.slot_block = (double*)dev_alloc((size_t)nslots * b_slot);
+  c.gw = (double*)dev_alloc(b_gw); c.tw = (double*)dev_alloc(b_tw); c.ew = (double*)dev_alloc(b_ew); c.ck = (double*)dev_alloc(b_ck); c.cfcn = (double*)dev_alloc(b_cf);
+  c.flag = (int*)dev_alloc(8);
+  c.tape.part = (TapePart*)dev_alloc((size_t)cap * nb * sizeof(TapePart)); c.tape.idx = (TapeIdx*)dev_alloc((size_t)cap * nb * sizeof(TapeIdx));
+  c.tape.adj = (double*)dev_alloc((size_t)cap * nb * 8); c.tape.overflow = c.flag ? c.flag + 1 : nullptr; c.tape.stride = nb; c.tape.cap = cap;
+  if (!(c.slot_block && c.gw && c.tw && c.ew && c.ck && c.cfcn && c.flag && c.tape.part && c.tape.idx && c.tape.adj)) {
+    err = std::string(who) + ": allocation of " + std::to_string(total) + " bytes failed" + (sticky_error().empty() ? std::string() : ": " + sticky_error());
+    if (clean) sticky_error().clear();
+    cloud_destroy();
+    return false;
+  }
+  for (int n = 0; n < nslots; ++n) c.slot.push_back(c.slot_block + (size_t)n * (b_slot / 8));
+  dev_zero(ex, c.cfcn, b_cf);
+  c.p = *p; c.iqi = iqi; c.iql = iql; c.set.assign((size_t)nslots, 0); c.created = 1;
+  return true;
+}
+inline void Dynamics::cloud_destroy() {
+  dev_free(cld.slot_block); dev_free(cld.gw); dev_free(cld.tw); dev_free(cld.ew); dev_free(cld.ck); dev_free(cld.cfcn); dev_free(cld.flag);
+  dev_free(cld.tape.part); dev_free(cld.tape.idx); dev_free(cld.tape.adj);
+  cld = Cloud{};
+}
+inline bool Dynamics::cloud_slot_ok(const char* who, int slot, bool need_set) {
+  if (!cld.created) { err = std::string(who) + ": call fv3lm_cloud_create first"; return false; }
+  if (slot < 0 || slot >= conv.nslots) { err = std::string(who) + ": slot " + std::to_string(slot) + " out of range (0.." + std::to_string(conv.nslots - 1) + ")"; return false; }
+  if (!conv.set[(size_t)slot]) { err = std::string(who) + ": the convection slot " + std::to_string(slot) + " was never set (fv3lm_convection_set)"; return false; }
+  if (need_set && !cld.set[(size_t)slot]) { err = std::string(who) + ": slot " + std::to_string(slot) + " was never set (fv3lm_cloud_set)"; return false; }
+  return true;
+}
+inline CldArgs Dynamics::cloud_args(int slot) {
+  CldArgs a; a.r = conv_args(slot); a.mst = conv.mst;
+  a.qi = ex.sh(q[(size_t)cld.iqi - 1]); a.ql = ex.sh(q[(size_t)cld.iql - 1]);
+  a.slot = cld.slot[(size_t)slot]; a.cfcn = cld.cfcn;
+  a.gw = cld.gw; a.tw = cld.tw; a.ew = cld.ew; a.ck = cld.ck; a.tape = cld.tape; a.nb = cld.nb; a.p = cld.p; a.flag = cld.flag;
+  return a;
+}
+// the slot takes QLS QCN cfcn khl khu from the host, PLE from the resident delp and everything else from the convection slot of the same
+// number; the split, the fractions, CLOUD_DRIVER in values and (do_phy_mst = 2) the per-cell switch
+inline bool Dynamics::cloud_set(int slot, const double* qls, const double* qcn, const double* cfcn, const double* khl, const double* khu) {
+  const char* who = "fv3lm_cloud_set";
+  auto no = [&](const std::string& m) { err = std::string(who) + ": " + m; return false; };
+  if (!cloud_slot_ok(who, slot, false)) return false;
+  if (!qls || !qcn || !cfcn || !khl || !khu) return no("null array");
+  const size_t nc = conv_ncol(), pc = (size_t)g.tx * g.ty; const int lm = g.npz;
+  for (size_t n = 0; n < nc * lm; ++n)
+    if (turb_stored_nonfinite(qls + n) || turb_stored_nonfinite(qcn + n) || turb_stored_nonfinite(cfcn + n)) return no("a value that is not finite in QLS, QCN or cfcn");
+  for (size_t n = 0; n < nc; ++n) {
+    if (turb_stored_nonfinite(khl + n) || turb_stored_nonfinite(khu + n)) return no("a value that is not finite in khl or khu");
+    const long l = std::lround(khl[n]), u = std::lround(khu[n]);
+    if (l < 1 || l > lm || u < 1 || u > lm) return no("khl = " + std::to_string(l) + ", khu = " + std::to_string(u) + " outside 1..npz = 1.." + std::to_string(lm));
+  }
+  cld.set[(size_t)slot] = 0;
+  CldArgs a = cloud_args(slot);
+  std::vector<double> buf((size_t)(lm + 1) * nc, 0.);
+  auto pack = [&](int v, const double* src) {      // [tile][level][point] -> [level][column]
+    for (size_t col = 0; col < nc; ++col) for (int l = 0; l < lm; ++l) buf[(size_t)l * nc + col] = src[((col / pc) * lm + l) * pc + col % pc];
+    h2d(ex, &a.S(v, 0, 0), buf.data(), buf.size() * 8);
+  };
+  pack(CS_QILS, qls); pack(CS_QICN, qcn); pack(CS_CFCN, cfcn);
+  std::vector<double> kh(2 * nc);
+  for (size_t n = 0; n < nc; ++n) { kh[n] = (double)std::lround(khl[n]); kh[nc + n] = (double)std::lround(khu[n]); }      // nint
+  h2d(ex, &a.SC(CSC_KHL, 0), kh.data(), kh.size() * 8);
+  dev_zero(ex, cld.flag, 8);
+  for (size_t first = 0; first < nc; first += (size_t)cld.nb) { a.r.first = (int)first; a.r.n = (int)(nc - first < (size_t)cld.nb ? nc - first : (size_t)cld.nb); run_cloud(ex, -1, a); }
+  int flag[2] = {0, 0};
+  d2h(ex, flag, cld.flag, sizeof flag);
+  if (flag[0]) return no("a value that is not finite in the resident trajectory (slot " + std::to_string(slot) + " is not set)");
+  if (!sticky_error().empty()) { err = sticky_error(); return false; }
+  cld.set[(size_t)slot] = 1;
+  return true;
+}
+inline bool Dynamics::cloud_get(int slot, double* const* out8, double* const* frac4, int* pertmod) {
+  const char* who = "fv3lm_cloud_get";
+  if (!cloud_slot_ok(who, slot, true)) return false;
+  if (out8) for (int n = 0; n < 8; ++n) if (!out8[n]) { err = std::string(who) + ": null array"; return false; }
+  if (frac4) for (int n = 0; n < 4; ++n) if (!frac4[n]) { err = std::string(who) + ": null array"; return false; }
+  const size_t nc = conv_ncol(), pc = (size_t)g.tx * g.ty; const int lm = g.npz;
+  const CldArgs a = cloud_args(slot);
+  std::vector<double> buf((size_t)(lm + 1) * nc);
+  auto unpack = [&](int v, double* dst, int* idst) {      // [level][column] -> [tile][level][point]
+    d2h(ex, buf.data(), &a.S(v, 0, 0), buf.size() * 8);
+    for (size_t col = 0; col < nc; ++col) for (int l = 0; l < lm; ++l) {
+      const size_t n = ((col / pc) * lm + l) * pc + col % pc;
+      if (dst) dst[n] = buf[(size_t)l * nc + col]; else idst[n] = (int)buf[(size_t)l * nc + col];
+    }
+  };
+  if (out8) for (int n = 0; n < 8; ++n) unpack(CS_OUT + n, out8[n], nullptr);
+  if (frac4) for (int n = 0; n < 4; ++n) unpack(CS_FRAC + n, frac4[n], nullptr);
+  if (pertmod) unpack(CS_PMOD, nullptr, pertmod);
+  return true;
+}
+inline bool Dynamics::cloud_cfcn(int put, double* cfcn) {
+  const char* who = "fv3lm_cloud_cfcn";
+  if (!cld.created) { err = std::string(who) + ": call fv3lm_cloud_create first"; return false; }
+  if (!cfcn) { err = std::string(who) + ": null array"; return false; }
+  const size_t n3c = conv_ncol() * g.npz;
+  if (put) for (size_t n = 0; n < n3c; ++n) if (turb_stored_nonfinite(cfcn + n)) { err = std::string(who) + ": a value that is not finite"; return false; }
+  if (put) h2d(ex, cld.cfcn, cfcn, n3c * 8); else d2h(ex, cfcn, cld.cfcn, n3c * 8);
+  return true;
+}
+// every column, in dense batches.  The slot is read only; mode 0 writes the trajectory tracers iqi, iql
+inline bool Dynamics::cloud_run(int slot, int mode) {
+  const char* who = "fv3lm_cloud";
+  if (!cloud_slot_ok(who, slot, false)) return false;
+  if (mode < 0 || mode > 2) { err = std::string(who) + ": bad mode"; return false; }
+  if (!cloud_slot_ok(who, slot, true)) return false;
+  CldArgs a = cloud_args(slot);
+  const size_t nc = conv_ncol();
+  if (mode == MODE_AD) dev_zero(ex, cld.flag, 8);
+  for (size_t first = 0; first < nc; first += (size_t)cld.nb) { a.r.first = (int)first; a.r.n = (int)(nc - first < (size_t)cld.nb ? nc - first : (size_t)cld.nb); run_cloud(ex, mode, a); }
+  if (mode == MODE_AD) {
+    int flag[2] = {0, 0};
+    d2h(ex, flag, cld.flag, sizeof flag);
+    if (flag[1]) { err = std::string(who) + ": the tape of a segment overflowed (CLD_TAPE); the adjoint fields are not valid"; return false; }
   }
   if (!sticky_error().empty()) { err = sticky_error(); return false; }
   return true;

@@ -271,6 +271,43 @@ int fv3lm_convection(fv3lm_handle* h, int slot, int mode) {
   if (!h->d.conv_run(slot, mode)) return fail(h->d.err);
   return status(h);
 }
+// linearised cloud scheme (cloud.h)
+void fv3lm_cloud_default_params(fv3lm_cloud_params* p, int im) {      // fv3jedi_lm_moist_mod.F90:151-211
+  if (!p) return;
+  const double r[57] = {10.0, 4.0, 4.0, 1.0, 2.0e-3, 8.0e-4, 2.0, 1.0, -1.0, 0.0, 1.3, 1.0e-9, 3.3e-4, 20., 4.8, 4.8, 230., 1.0, 1.0, 230., 14400., 50., 0.01, 0.1, 200., 0., 0., 0.5,
+                        0.5, 2000., 0.8, 0.5, -40.0, 1.0, 4.0, 0.0, 0.0, 0.0, 1.0e-3, 8.0e-4, 1.0, 0.80, 1.0, 0.0, 750.0, 0.81, 1.0, 1.0, 0.0, 0.0, 10.e-6, 20.e-6, 21.e-6, 40.e-6,
+                        30.e-6, 1.0, 1.0};
+  for (int n = 0; n < 57; ++n) p->r[n] = r[n];
+  const long imsize = 4L * im;
+  p->r[41] = imsize <= 200 ? 0.80 : imsize <= 400 ? 0.90 : imsize <= 800 ? 0.93 : imsize <= 1600 ? 0.95 : 0.97;
+  p->r[45] = p->r[41] + 0.01;
+}
+int fv3lm_cloud_create(fv3lm_handle* h, const fv3lm_cloud_params* p, int iqi, int iql) {
+  if (!h) return fail("fv3lm_cloud_create: null handle");
+  static_assert(sizeof(fv3lm_cloud_params) == sizeof(CldParams), "fv3lm_cloud_params and CldParams must agree");
+  if (!h->d.cloud_create(reinterpret_cast<const CldParams*>(p), iqi, iql)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_cloud_set(fv3lm_handle* h, int slot, const double* qls, const double* qcn, const double* cfcn, const double* khl, const double* khu) {
+  if (!h) return fail("fv3lm_cloud_set: null handle");
+  if (!h->d.cloud_set(slot, qls, qcn, cfcn, khl, khu)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_cloud_get(fv3lm_handle* h, int slot, double* const* out8, double* const* frac4, int* pertmod) {
+  if (!h) return fail("fv3lm_cloud_get: null handle");
+  if (!h->d.cloud_get(slot, out8, frac4, pertmod)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_cloud_cfcn(fv3lm_handle* h, int put, double* cfcn) {
+  if (!h) return fail("fv3lm_cloud_cfcn: null handle");
+  if (!h->d.cloud_cfcn(put, cfcn)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_cloud(fv3lm_handle* h, int slot, int mode) {
+  if (!h) return fail("fv3lm_cloud: null handle");
+  if (!h->d.cloud_run(slot, mode)) return fail(h->d.err);
+  return status(h);
+}
 int fv3lm_step_tl(fv3lm_handle* h) { h->d.step_tl(); return status(h); }
 int fv3lm_step_nl(fv3lm_handle* h) { h->d.step_nl(); return status(h); }
 int fv3lm_step_ad(fv3lm_handle* h) { h->d.step_ad(); return status(h); }

@@ -272,6 +272,43 @@ int fv3lm_convection_get(fv3lm_handle* h, int slot, double* const* out6, int* do
 int fv3lm_convection_sources(fv3lm_handle* h, int put, double* const* src4);
 int fv3lm_convection(fv3lm_handle* h, int slot, int mode);
 int fv3lm_convection_table(fv3lm_handle* h, double* table, double* constants);
+/* Linearised cloud scheme of the moist physics (physics/moist/cloud.F90 CLOUD_DRIVER, its tangent cloud_tl.F90 CLOUD_DRIVER_D and adjoint
+ * cloud_ad.F90 CLOUD_DRIVER_B, and the part of fv3jedi_lm_moist_mod.F90 after the rase loops: create :151-211, set_ltraj :834-874, step_nl
+ * :365-388, step_tl :429-438 / :495-501, step_ad :542-551 / :607-616).  Column-local; it follows the convection in every column and reads
+ * that feature's slot of the same number.  Compact arrays as for the convection.
+ *   fv3lm_cloud_params: CLOUDPARAMS(1:57).  fv3lm_cloud_default_params fills in create :151-211; entries 42 and 46 follow imsize = 4 im.
+ *   fv3lm_cloud_create: after fv3lm_convection_create, whose do_phy_mst, table, constants and slot count it takes (one cloud slot per
+ *       convection slot).  iqi, iql (2..nq, distinct) name the tracers that carry cloud ice and cloud liquid, of the perturbation and of the
+ *       trajectory.  ALL device memory of the feature is allocated here (FV3LM_VERBOSE=1 prints it) and freed by fv3lm_destroy.
+ *   fv3lm_cloud_set: after fv3lm_convection_set of the same slot, on the same resident trajectory (PLE in Pa is taken from the resident
+ *       delp).  QLS, QCN, cfcn (npz deep) and khl, khu (nint of a real) are the host's; PTT_C, QVT_C, the four _C sources, ple, pk and frland
+ *       are the convection slot's.  Computes fQi = IceFraction(TEMP) with the GEOS pk, QILST QLLST QICNT QLCNT, the fractions ILSF ICNF
+ *       LLSF LCNF, CLOUD_DRIVER in values and, for do_phy_mst = 2, the per-cell switch cloud_pertmod (the eigenvalues of the 8 x 8
+ *       Jacobian of LS_CLOUD_D and its four entry thresholds, cloud_tl.F90:405-481).  No later call modifies a slot; a later
+ *       fv3lm_convection_set of that slot unsets it.  The reference's cloud_driver_d updates its saved trajectory in place, so a second
+ *       call on a saved ltraj sees a trajectory that has been through the cloud scheme already: that is not reproduced.
+ *   fv3lm_cloud_get: out8 = theta, q, QI_ls, QL_ls, QI_con, QL_con, CF_ls, CF_con after CLOUD_DRIVER in values; frac4 = ILSF ICNF LLSF
+ *       LCNF; pertmod = the switch, one int a cell (all 1 for do_phy_mst = 1).  NULL is allowed for each.
+ *   fv3lm_cloud_cfcn: the perturbation's convective cloud fraction (npz deep), which the feature owns on the device: put = 0 reads, 1 writes.
+ *   fv3lm_cloud: every column.  mode 0: CLOUD_DRIVER in values on copies of the slot; qi = QI_ls + QI_con and ql = QL_ls + QL_con go to
+ *       the resident trajectory tracers iqi, iql (CF_con is what get returns); T and qv are not touched.  1: T -> theta by p00^kappa / pk,
+ *       qi and ql split by the fractions, cflsp = 0, cfcn as put, the four sources as fv3lm_convection(1) left them; after the driver
+ *       the parts are summed, theta goes back to T, cfcn is updated.  2: theta = T pk / p00^kappa, both parts of qi and ql receive the
+ *       full adjoint; after the driver they are combined with the fractions and the adjoints of the four sources are written where
+ *       fv3lm_convection(2) consumes them.  Host order:
+ *           tangent  fv3lm_step_tl ; fv3lm_turbulence(1) ; fv3lm_convection(1) ; fv3lm_cloud(1)
+ *           adjoint  fv3lm_cloud(2) ; fv3lm_convection(2) ; fv3lm_turbulence(2) ; fv3lm_step_ad.
+ *   Refused with a message, the slot left unset: before fv3lm_convection_create or a second create; iqi / iql out of range or equal;
+ *   CLOUDPARAMS(57) /= 1 (only the top-hat PDF is built); a slot whose convection slot was never set; a slot out of range or never set; a
+ *   mode outside 0..2; a NULL array where one is required; khl / khu outside 1..npz; a value that is not finite; an allocation that
+ *   fails; a tape that overflows in the adjoint. */
+typedef struct { double r[57]; } fv3lm_cloud_params;
+void fv3lm_cloud_default_params(fv3lm_cloud_params* p, int im);
+int fv3lm_cloud_create(fv3lm_handle* h, const fv3lm_cloud_params* p, int iqi, int iql);
+int fv3lm_cloud_set(fv3lm_handle* h, int slot, const double* qls, const double* qcn, const double* cfcn, const double* khl, const double* khu);
+int fv3lm_cloud_get(fv3lm_handle* h, int slot, double* const* out8, double* const* frac4, int* pertmod);
+int fv3lm_cloud_cfcn(fv3lm_handle* h, int put, double* cfcn);
+int fv3lm_cloud(fv3lm_handle* h, int slot, int mode);
 /* Per-kernel HIP-event profile of everything launched between begin and end, on the library's stream:
  * lines "kernel count total_ms algorithmic_bytes".  Returns the buffer length needed. */
 int fv3lm_profile_begin(fv3lm_handle* h);
