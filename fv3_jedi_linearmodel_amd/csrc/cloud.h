@@ -24,7 +24,9 @@
 namespace fv3 {
 
 constexpr int CLD_BATCH = 2048;
-constexpr int CLD_TAPE = 6144;      // entries a column; the largest segment is pre / post at (leaves 15 + about 25 operations) a level
+// entries a column.  A segment is one level, or pre / post, never the column: the largest recorded in the host emulation over the mode tests
+// is 616 entries at L20, L40 and L72 alike (the device has not been measured), a tenth of the capacity
+constexpr int CLD_TAPE = 6144;
 constexpr int CLD_KTOP = 30;
 // state vectors (units of T); CE_SV holds the carried scalars at "levels" 1..18
 enum { CE_T = 0, CE_Q, CE_QILS, CE_QLLS, CE_QICN, CE_QLCN, CE_CFLS, CE_CFCN, CE_DQL, CE_MFD, CE_PRC3, CE_UPDF, CE_QS, CE_DZET, CE_QDDF3, CE_SV, CLD_NE };

@@ -228,49 +228,163 @@ def check_dot_product(c, tag, chain=False, tol=1e-12):
 
 
 # ---- 7: position independence
-def check_position(make_small, make_cube, tag, layout=2):
-    """a column's set outputs and tangent results on the six faces, and on their sub-face layout, equal those on the small tile: bitwise"""
+FIELDS = ("pt", "q1", "q%d" % IQI, "q%d" % IQL)
+
+
+def forcing(c, fx, k):
+    """the fixture's drawn perturbation (fields, cfcn, four sources) and its adjoint forcing (fields, cfcn) as the fields of the case"""
+    pk, p00k = CC.pk_of(fx, lev(fx["delp"], k))
+    return host_fields(c, fx, k, pk, p00k, False), host_fields(c, fx, k, pk, p00k, True)[:2]
+
+
+def run_slot(c, slot, T, F, nonlinear=True):
+    """what a set slot returns and what its three runs leave on is..ie x js..je: the eight values, the fractions and the switch; the
+    tangent's fields and cfcn; the adjoint's fields, cfcn and the four source adjoints it leaves; the qi, ql the nonlinear run wrote back to
+    the trajectory and the CF_con it leaves in the slot"""
+    (P, cf, src), (PA, cfa) = F
+    D = TC.dom(c)
+    out, frac, pm = c.dy.cloud_get(slot)
+    TC.put_all(c, T, P)
+    c.dy.convection_sources(src)
+    c.dy.cloud_cfcn(cf)
+    c.dy.cloud(slot, TL)
+    r = [out[n] for n in OUT8] + [frac[n] for n in FRAC] + [pm.astype(np.float64)] + [c.dy.get(n, 1)[D] for n in FIELDS] + [c.dy.cloud_cfcn()]
+    TC.put_all(c, T, PA)
+    c.dy.cloud_cfcn(cfa)
+    c.dy.cloud(slot, AD)
+    r += [c.dy.get(n, 1)[D] for n in FIELDS] + [c.dy.cloud_cfcn()] + [v for v in c.dy.convection_sources().values()]
+    if nonlinear:
+        TC.put_all(c, T, P)
+        c.dy.cloud(slot, NL)
+        r += [c.dy.get(n, 0)[D] for n in FIELDS[2:]] + [c.dy.cloud_get(slot, frac=False, pertmod=False)[0]["CF_con"]]
+    return r
+
+
+def results(c, fx, T, sfc, cl, F):
+    ensure_created(c, fx)
+    TC.put_all(c, T, F[0][0])
+    c.dy.convection_set(0, *sfc)
+    c.dy.cloud_set(0, *cl)
+    return run_slot(c, 0, T, F)
+
+
+_small = {}
+
+
+def small_tile(make_small, tag, key):
+    """the results of the small tile, which checks 1 to 5 tie to the reference: computed once for a backend and left unchanged"""
+    if (key, tag) not in _small:
+        fx = fixture(tag)
+        small = make_small()
+        Ts, ss, cs, ks = placed(small, fx, dealt(small, 0))
+        assert set(np.unique(ks)) == set(range(fx["ncol"])), "every column of the fixture is on the small tile"
+        rs = results(small, fx, Ts, ss, cs, forcing(small, fx, ks))
+        first = np.zeros(fx["ncol"], dtype=np.int64)
+        first[ks.ravel()[::-1]] = np.arange(ks.size)[::-1]
+        for a in rs:
+            a.setflags(write=False)
+        _small[(key, tag)] = (rs, first)
+    return _small[(key, tag)]
+
+
+def check_position(make_small, make_cube, tag, layout=2, key=None):
+    """a column's set outputs and the results of its tangent, adjoint and nonlinear runs on the six faces, and on their sub-face layout,
+    equal those on the small tile: bitwise"""
     fx = fixture(tag)
     lm = fx["lm"]
-
-    def pert_of(c, k):
-        pk, p00k = CC.pk_of(fx, lev(fx["delp"], k))
-        return host_fields(c, fx, k, pk, p00k, False)
-
-    def results(c, T, sfc, cl, H):
-        P, cf, src = H
-        ensure_created(c, fx)
-        TC.put_all(c, T, P)
-        c.dy.convection_set(0, *sfc)
-        c.dy.cloud_set(0, *cl)
-        out, frac, pm = c.dy.cloud_get(0)
-        c.dy.convection_sources(src)
-        c.dy.cloud_cfcn(cf)
-        c.dy.cloud(0, TL)
-        D = TC.dom(c)
-        return [out[n] for n in OUT8] + [frac[n] for n in FRAC] + [pm.astype(np.float64)] + [c.dy.get(n, 1)[D] for n in ("pt", "q1", "q%d" % IQI, "q%d" % IQL)] + [c.dy.cloud_cfcn()]
-
-    small = make_small()
-    Ts, ss, cs, ks = placed(small, fx, dealt(small, 0))
-    rs = results(small, Ts, ss, cs, pert_of(small, ks))
-    first = np.zeros(fx["ncol"], dtype=np.int64)
-    first[ks.ravel()[::-1]] = np.arange(ks.size)[::-1]
+    rs, first = small_tile(make_small, tag, key)
     c1, c2 = make_cube(1), make_cube(layout)
     T1, s1, cl1, k1 = placed(c1, fx, dealt(c1, 5))
-    H1 = pert_of(c1, k1)
-    r1 = results(c1, T1, s1, cl1, H1)
+    F1 = forcing(c1, fx, k1)
+    r1 = results(c1, fx, T1, s1, cl1, F1)
     win = lambda a: np.ascontiguousarray(np.stack([a[f, ..., j0 - 1:j0 - 1 + c2.nt, i0 - 1:i0 - 1 + c2.nt] for (f, i0, j0) in c2.tiles]))
-    T2 = {n: pad(c2, win(TC.comp(c1, T1[n]))) for n in T1}
-    P2 = {n: pad(c2, win(TC.comp(c1, H1[0][n]))) for n in H1[0]}
-    r2 = results(c2, T2, [win(v) for v in s1], [win(v) for v in cl1], (P2, win(H1[1]), [win(v) for v in H1[2]]))
+    wpad = lambda P: {n: pad(c2, win(TC.comp(c1, P[n]))) for n in P}
+    (P1, cf1, src1), (PA1, cfa1) = F1
+    F2 = ((wpad(P1), win(cf1), [win(v) for v in src1]), (wpad(PA1), win(cfa1)))
+    r2 = results(c2, fx, wpad(T1), [win(v) for v in s1], [win(v) for v in cl1], F2)
+    assert len(r1) == len(rs) == 8 + 4 + 1 + 5 + 9 + 3
     for m, a in enumerate(r1):
-        want = np.moveaxis(np.moveaxis(rs[m], 1, -1).reshape(-1, lm)[first[k1]], -1, 1)
+        want = CC.as_on_small(rs, first, k1, lm, m)
         assert np.array_equal(a, want), (m, "a column's result depends on where it lies")
         g = np.zeros_like(a)
         for t, (f, i0, j0) in enumerate(c2.tiles):
             g[f, ..., j0 - 1:j0 - 1 + c2.nt, i0 - 1:i0 - 1 + c2.nt] = r2[m][t]
         assert np.array_equal(g, a), (m, "sub-face tiles gathered != six faces")
+    assert all(np.any(rs[m]) for m in range(23, 27)), "the adjoint leaves source adjoints"
     return k1.size
+
+
+# ---- 7b: columns beyond the first batch
+def check_batches(make_small, make_big, tag, read_err, shift=5, full=False, key=None):
+    """every column of a case of more columns than a batch holds -- read_err() returns what the library wrote under FV3LM_VERBOSE -- has
+    the results of the same fixture column on the small tile, bitwise, in every mode.  full: the case is whole batches exactly (the loop
+    bounds); otherwise its last batch is a partial one"""
+    fx = fixture(tag)
+    rs, first = small_tile(make_small, tag, key)
+    read_err()
+    c = make_big()
+    T, sfc, cl, k = placed(c, fx, dealt(c, shift))
+    r = results(c, fx, T, sfc, cl, forcing(c, fx, k))
+    nb = CC.batch_size(read_err(), "cloud")
+    print("%s %d columns, batch of %d" % (tag, k.size, nb))
+    if full:
+        assert k.size >= nb and k.size % nb == 0, (k.size, nb)
+    else:
+        assert nb < k.size and k.size % nb != 0, (k.size, nb)
+    for m, a in enumerate(r):
+        assert np.array_equal(a, CC.as_on_small(rs, first, k, fx["lm"], m)), (m, "a column's result depends on its batch")
+    return k.size, nb
+
+
+# ---- 7c: a slot set again, two slots in turn
+def check_reset_and_slots(make, tag):
+    """slot 0 from deal A, slot 1 from deal B (shift 5); run slot 1, then slot 0; the convection slot 0 set again from deal B: a cloud run
+    on it is refused until the cloud slot follows; then every result equals that of a fresh single-slot handle given the same deal,
+    bitwise, and slot 0 equals slot 1"""
+    import pytest
+    fx = fixture(tag)
+    c = make()
+    deals = {}
+    for name, shift in (("A", 0), ("B", 5)):
+        T, sfc, cl, k = placed(c, fx, dealt(c, shift))
+        deals[name] = (T, sfc, cl, forcing(c, fx, k))
+    fresh = {}
+    for name, (T, sfc, cl, F) in deals.items():
+        f = make()
+        ensure_created(f, fx, 1)
+        TC.put_all(f, T)
+        f.dy.convection_set(0, *sfc)
+        f.dy.cloud_set(0, *cl)
+        fresh[name] = (run_slot(f, 0, T, F, nonlinear=False), f.dy.convection_get(0)[1])
+    assert not np.array_equal(fresh["A"][1], fresh["B"][1]), "deal B has to change which columns are active"
+    assert not np.array_equal(fresh["A"][0][12], fresh["B"][0][12]), "deal B has to change the switch"
+
+    def same(got, name, what):
+        for m, (a, b) in enumerate(zip(got, fresh[name][0])):
+            assert np.array_equal(a, b), (what, m)
+
+    def run(slot, name):
+        return run_slot(c, slot, deals[name][0], deals[name][3], nonlinear=False)
+    ensure_created(c, fx, 2)
+    for slot, name in ((0, "A"), (1, "B")):
+        TC.put_all(c, deals[name][0])
+        c.dy.convection_set(slot, *deals[name][1])
+        c.dy.cloud_set(slot, *deals[name][2])
+    r1 = run(1, "B")
+    same(r1, "B", "slot 1, deal B")
+    same(run(0, "A"), "A", "slot 0, deal A, after slot 1 ran")
+    TC.put_all(c, deals["B"][0])
+    c.dy.convection_set(0, *deals["B"][1])
+    for mode in (TL, AD, NL):
+        with pytest.raises(Fv3LmError, match="never set"):
+            c.dy.cloud(0, mode)
+    same(run(1, "B"), "B", "slot 1 after the convection re-set of slot 0")
+    c.dy.cloud_set(0, *deals["B"][2])
+    assert np.array_equal(c.dy.convection_get(0)[1], fresh["B"][1]), "DOCONVEC of the slot set again"
+    r0 = run(0, "B")
+    same(r0, "B", "slot 0 set again from deal B")
+    for a, b in zip(r0, r1):
+        assert np.array_equal(a, b), "after the re-set, slot 0 equals slot 1"
 
 
 # ---- 8: nothing else moves; the slot keeps what set saw

@@ -233,50 +233,166 @@ def check_dot_product(c, lm, tol=1e-12):
 
 
 # ---- 5: position independence
-def check_position(make_small, make_cube, lm, layout=2):
-    """a column's set outputs and tangent results on the six faces, and on their sub-face layout, equal those on the small tile: bitwise"""
-    fx = fixture(lm)
+def forcing(c, fx, k):
+    """the fixture's drawn perturbation, its adjoint forcing and the four source adjoints (Y[4:8]) as the fields of the case"""
+    pk, p00k = pk_of(fx, lev(fx["delp"], k))
+    return perturbation(c, fx, k, pk, p00k, False), perturbation(c, fx, k, pk, p00k, True), [lev(fx["Y"][4 + m], k) for m in range(4)]
 
-    def run(c, shift):
-        T, sfc, k = placed(c, fx, dealt(c, shift))
-        return T, sfc, k
 
-    def results(c, T, sfc, P):
-        ensure_created(c, fx)
+def run_slot(c, slot, T, F, nonlinear=True):
+    """what a set slot returns and what its three runs leave on is..ie x js..je: the set outputs and the Jacobian column; the tangent's
+    fields and sources; the adjoint's fields and the consumed sources; the trajectory the nonlinear run wrote back.  -> (list, doconvec)"""
+    P, PA, YS = F
+    D = TC.dom(c)
+    out, dc, jac = c.dy.convection_get(slot)
+    TC.put_all(c, T, P)
+    c.dy.convection(slot, TL)
+    r = [out[n] for n in SETN] + [jac[0], jac[1]] + [c.dy.get(n, 1)[D] for n in FOUR] + [v for v in c.dy.convection_sources().values()]
+    TC.put_all(c, T, PA)
+    c.dy.convection_sources(YS)
+    c.dy.convection(slot, AD)
+    r += [c.dy.get(n, 1)[D] for n in FOUR] + [v for v in c.dy.convection_sources().values()]
+    if nonlinear:
         TC.put_all(c, T, P)
-        c.dy.convection_set(0, *sfc)
-        out, dc, jac = c.dy.convection_get(0)
-        c.dy.convection(0, TL)
-        D = TC.dom(c)
-        r = [out[n] for n in SETN] + [jac[0], jac[1]] + [c.dy.get(n, 1)[D] for n in FOUR] + [v for v in c.dy.convection_sources().values()]
-        return r, dc
+        c.dy.convection(slot, NL)
+        r += [c.dy.get(n, 0)[D] for n in FOUR]
+    return r, dc
 
-    def pert_of(c, k):
-        pk, p00k = pk_of(fx, lev(fx["delp"], k))
-        return perturbation(c, fx, k, pk, p00k, False)
 
-    small = make_small()
-    Ts, ss, ks = run(small, 0)
-    rs, ds = results(small, Ts, ss, pert_of(small, ks))
-    first = np.zeros(fx["ncol"], dtype=np.int64)
-    first[ks.ravel()[::-1]] = np.arange(ks.size)[::-1]
+def results(c, fx, T, sfc, F):
+    ensure_created(c, fx)
+    TC.put_all(c, T, F[0])
+    c.dy.convection_set(0, *sfc)
+    return run_slot(c, 0, T, F)
+
+
+_small = {}
+
+
+def small_tile(make_small, lm, key):
+    """the results of the small tile, which checks 1, 2 and 4 tie to the reference: computed once for a backend and left unchanged"""
+    if (key, lm) not in _small:
+        fx = fixture(lm)
+        small = make_small()
+        Ts, ss, ks = placed(small, fx, dealt(small, 0))
+        assert set(np.unique(ks)) == set(range(fx["ncol"])), "every column of the fixture is on the small tile"
+        rs, ds = results(small, fx, Ts, ss, forcing(small, fx, ks))
+        first = np.zeros(fx["ncol"], dtype=np.int64)
+        first[ks.ravel()[::-1]] = np.arange(ks.size)[::-1]
+        for a in rs:
+            a.setflags(write=False)
+        _small[(key, lm)] = (rs, ds, first)
+    return _small[(key, lm)]
+
+
+def as_on_small(rs, first, k, lm, m):
+    """result m of the small tile at the columns k of another case"""
+    return np.moveaxis(np.moveaxis(rs[m], 1, -1).reshape(-1, lm)[first[k]], -1, 1)
+
+
+def check_position(make_small, make_cube, lm, layout=2, key=None):
+    """a column's set outputs and the results of its tangent, adjoint and nonlinear runs on the six faces, and on their sub-face layout,
+    equal those on the small tile: bitwise"""
+    fx = fixture(lm)
+    rs, ds, first = small_tile(make_small, lm, key)
     c1, c2 = make_cube(1), make_cube(layout)
-    T1, s1, k1 = run(c1, 5)
-    P1 = pert_of(c1, k1)
-    r1, d1 = results(c1, T1, s1, P1)
+    T1, s1, k1 = placed(c1, fx, dealt(c1, 5))
+    F1 = forcing(c1, fx, k1)
+    r1, d1 = results(c1, fx, T1, s1, F1)
     win = lambda a: np.ascontiguousarray(np.stack([a[f, ..., j0 - 1:j0 - 1 + c2.nt, i0 - 1:i0 - 1 + c2.nt] for (f, i0, j0) in c2.tiles]))
     T2 = {n: pad(c2, win(TC.comp(c1, T1[n]))) for n in T1}
-    P2 = {n: pad(c2, win(TC.comp(c1, P1[n]))) for n in P1}
-    r2, d2 = results(c2, T2, [win(v) for v in s1], P2)
+    F2 = tuple({n: pad(c2, win(TC.comp(c1, P[n]))) for n in P} for P in F1[:2]) + ([win(v) for v in F1[2]],)
+    r2, d2 = results(c2, fx, T2, [win(v) for v in s1], F2)
+    assert len(r1) == len(rs) == 6 + 2 + 8 + 8 + 4
     for m, a in enumerate(r1):
-        want = np.moveaxis(np.moveaxis(rs[m], 1, -1).reshape(-1, lm)[first[k1]], -1, 1)
+        want = as_on_small(rs, first, k1, lm, m)
         assert np.array_equal(a, want), (m, "a column's result depends on where it lies")
         g = np.zeros_like(a)
         for t, (f, i0, j0) in enumerate(c2.tiles):
             g[f, ..., j0 - 1:j0 - 1 + c2.nt, i0 - 1:i0 - 1 + c2.nt] = r2[m][t]
         assert np.array_equal(g, a), (m, "sub-face tiles gathered != six faces")
     assert np.array_equal(d1, ds.ravel()[first[k1]])
+    assert not any(np.any(rs[m]) for m in range(20, 24)), "the adjoint consumes and clears its sources"
     return d1.size
+
+
+def batch_size(err, scheme):
+    """the columns of a batch as the library reports them at create under FV3LM_VERBOSE"""
+    import re
+    m = re.findall(r"fv3lm: %s arena .* batch of (\d+) columns" % scheme, err)
+    assert m, ("no 'batch of %d columns' line of the " + scheme + " arena: is FV3LM_VERBOSE set?", err[-500:])
+    return int(m[-1])
+
+
+# ---- 5b: columns beyond the first batch
+def check_batches(make_small, make_big, lm, read_err, shift=5, full=False, key=None):
+    """every column of a case of more columns than a batch holds -- read_err() returns what the library wrote under FV3LM_VERBOSE -- has
+    the results of the same fixture column on the small tile, bitwise, in every mode.  full: the case is whole batches exactly (the loop
+    bounds); otherwise the active list itself has to need a second, partial batch"""
+    fx = fixture(lm)
+    rs, ds, first = small_tile(make_small, lm, key)
+    read_err()
+    c = make_big()
+    T, sfc, k = placed(c, fx, dealt(c, shift))
+    r, dc = results(c, fx, T, sfc, forcing(c, fx, k))
+    nb = batch_size(read_err(), "convection")
+    nactive = int(dc.sum())
+    print("L%d %d columns, %d active, batch of %d" % (lm, dc.size, nactive, nb))
+    if full:
+        assert dc.size >= nb and dc.size % nb == 0, (dc.size, nb)
+    else:
+        assert nb < dc.size and dc.size % nb != 0, (dc.size, nb)
+        assert nactive > nb and nactive % nb != 0, (nactive, nb, "the active list fits one batch, or fills whole batches: the case tests no later batch")
+    for m, a in enumerate(r):
+        assert np.array_equal(a, as_on_small(rs, first, k, lm, m)), (m, "a column's result depends on its batch")
+    assert np.array_equal(dc, ds.ravel()[first[k]])
+    return dc.size, nactive, nb
+
+
+# ---- 5c: a slot set again, two slots in turn
+def check_reset_and_slots(make, lm):
+    """slot 0 from deal A, slot 1 from deal B (shift 5: other columns active, as many); run slot 1, then slot 0; slot 0 set again from deal
+    B and run, and once more from deal C (shift 24: one more active): every result -- the set outputs, DOCONVEC, the Jacobian column,
+    tangent and adjoint -- equals that of a fresh single-slot handle given the same deal, bitwise"""
+    fx = fixture(lm)
+    c = make()
+    deals = {}
+    for name, shift in (("A", 0), ("B", 5), ("C", 24)):
+        T, sfc, k = placed(c, fx, dealt(c, shift))
+        deals[name] = (T, sfc, forcing(c, fx, k))
+    fresh = {}
+    for name, (T, sfc, F) in deals.items():
+        f = make()
+        ensure_created(f, fx, 1)
+        TC.put_all(f, T)
+        f.dy.convection_set(0, *sfc)
+        fresh[name] = run_slot(f, 0, T, F, nonlinear=False)
+    dA, dB = fresh["A"][1], fresh["B"][1]
+    assert not np.array_equal(dA, dB) and 0 < dB.sum() < dB.size, "deal B has to change which columns are active"
+    assert fresh["C"][1].sum() != dB.sum(), "deal C has to change how many are"
+    assert np.any((fresh["A"][0][6] != 0) & (dB == 0)[:, None]), "deal A leaves a Jacobian column where deal B has none: what a re-set has to clear"
+
+    def same(got, name, what):
+        for m, (a, b) in enumerate(zip(got[0], fresh[name][0])):
+            assert np.array_equal(a, b), (what, m)
+        assert np.array_equal(got[1], fresh[name][1]), (what, "DOCONVEC")
+    ensure_created(c, fx, 2)
+    for slot, name in ((0, "A"), (1, "B")):
+        TC.put_all(c, deals[name][0])
+        c.dy.convection_set(slot, *deals[name][1])
+    r1 = run_slot(c, 1, deals["B"][0], deals["B"][2], nonlinear=False)
+    same(r1, "B", "slot 1, deal B")
+    same(run_slot(c, 0, deals["A"][0], deals["A"][2], nonlinear=False), "A", "slot 0, deal A, after slot 1 ran")
+    TC.put_all(c, deals["B"][0])
+    c.dy.convection_set(0, *deals["B"][1])
+    r0 = run_slot(c, 0, deals["B"][0], deals["B"][2], nonlinear=False)
+    same(r0, "B", "slot 0 set again from deal B")
+    same(run_slot(c, 1, deals["B"][0], deals["B"][2], nonlinear=False), "B", "slot 1 after the re-set of slot 0")
+    for a, b in zip(r0[0], r1[0]):
+        assert np.array_equal(a, b), "after the re-set, slot 0 equals slot 1"
+    TC.put_all(c, deals["C"][0])
+    c.dy.convection_set(0, *deals["C"][1])
+    same(run_slot(c, 0, deals["C"][0], deals["C"][2], nonlinear=False), "C", "slot 0 set a third time, from deal C with another count of active columns")
 
 
 # ---- 6: nothing else moves; the slot keeps what set saw

@@ -12,20 +12,20 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FDIR = os.path.join(ROOT, "fortran")
 
 
-def build_driver(libdir, libname, out):
-    """amdflang: shim module + driver -> executable linked against lib<libname>.so in libdir (rpath set)"""
-    srcs = [os.path.join(FDIR, "fv3lm_hip_mod.F90"), os.path.join(FDIR, "shim_driver.F90")]
+def build_driver(libdir, libname, out, driver="shim_driver.F90"):
+    """amdflang: shim module + driver (a program of fortran/) -> executable linked against lib<libname>.so in libdir (rpath set)"""
+    srcs = [os.path.join(FDIR, "fv3lm_hip_mod.F90"), os.path.join(FDIR, driver)]
     lib = os.path.join(libdir, "lib%s.so" % libname)
     if os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs + [lib]):
         return out
-    mod = os.path.join(os.path.dirname(out), "mod_" + libname)
+    mod = os.path.join(os.path.dirname(out), "mod_" + libname + ("" if driver == "shim_driver.F90" else "_" + driver[:-4]))
     os.makedirs(mod, exist_ok=True)
     # compiled from copies inside the build directory: a stale fv3lm_hip_mod.mod next to the sources must not be picked up
     import shutil
     for s_ in srcs:
         shutil.copy(s_, mod)
     subprocess.check_call(["amdflang", "-cpp", "-fPIC", "-c", "fv3lm_hip_mod.F90", "-o", "fv3lm_hip_mod.o"], cwd=mod)
-    subprocess.check_call(["amdflang", "-cpp", "shim_driver.F90", "fv3lm_hip_mod.o", "-o", out, "-L", libdir, "-l" + libname, "-Wl,-rpath," + libdir], cwd=mod)
+    subprocess.check_call(["amdflang", "-cpp", driver, "fv3lm_hip_mod.o", "-o", out, "-L", libdir, "-l" + libname, "-Wl,-rpath," + libdir], cwd=mod)
     return out
 
 

@@ -8,10 +8,10 @@ BACKEND = "emul"
 LMS = [40, 72, 20]
 
 
-def tile(lm, face=None, nq=2, **kw):
-    """the periodic tile 12 x 10, or one 12 x 12 face of a C12 cube, on the fixture's levels"""
+def tile(lm, face=None, nq=2, size=None, **kw):
+    """the periodic tile 12 x 10 (or size), or one 12 x 12 face of a C12 cube, on the fixture's levels"""
     from common import Case
-    nx, ny = (12, 10) if face is None else (12, 12)
+    nx, ny = (size or (12, 10)) if face is None else (12, 12)
     kw = kw or CC.case_kw(CC.fixture(lm))
     return Case(nx=nx, ny=ny, npz=lm, n_split=2, dt=1800.0, nq=nq, backend=BACKEND, oracle=False, face=face, **kw)
 
@@ -46,8 +46,26 @@ def test_dot_product(where, lm):
 
 def test_position_independence():
     """check 5: the L40 columns dealt over the six faces of a C16 cube and over its 2 x 2 sub-face layout (a tile needs 8 cells, so
-    C12 cannot be cut): every column's set outputs, Jacobian column, tangent fields and sources as on the small tile, bitwise"""
-    CC.check_position(lambda: tile(40, None, 1), lambda L: cube(40, L, 1, 16), 40, 2)
+    C12 cannot be cut): every column's set outputs, Jacobian column, tangent fields and sources, adjoint fields and consumed sources and
+    the trajectory the nonlinear run writes back as on the small tile, bitwise"""
+    CC.check_position(lambda: tile(40, None, 1), lambda L: cube(40, L, 1, 16), 40, 2, key=BACKEND)
+
+
+@pytest.mark.parametrize("where", ["six faces C24 L40", "tile 64 x 32 L20", "tile 64 x 40 L40"])
+def test_columns_beyond_one_batch(where, monkeypatch, capfd):
+    """check 5b: 3,456, 2,048 and 2,560 columns against a batch whose size the library reports: set runs two batches on the first and the
+    last case (on the cube the boundary falls inside a face) and exactly one full batch on the second; on the first and the last the
+    active list needs a second, partial batch too, which the test asserts.  Every column, every mode, as on the small tile: bitwise"""
+    monkeypatch.setenv("FV3LM_VERBOSE", "1")
+    lm = 20 if "L20" in where else 40
+    big = (lambda: cube(40, 1, 1, 24)) if "six" in where else (lambda: tile(lm, None, 1, (64, 32) if lm == 20 else (64, 40)))
+    CC.check_batches(lambda: tile(lm, None, 1), big, lm, lambda: capfd.readouterr().err, full=lm == 20, key=BACKEND)
+
+
+def test_reset_and_two_slots():
+    """check 5c: two slots with different trajectories run in turn, and a slot set again: results, DOCONVEC and the Jacobian column
+    as a fresh single-slot handle gives them for the same deal, bitwise"""
+    CC.check_reset_and_slots(lambda: tile(40, None, 1), 40)
 
 
 @pytest.mark.parametrize("where", ["tile", "six faces"])

@@ -10,10 +10,10 @@ BACKEND = "hip"
 TAGS = ["L40m2", "L72m2", "L72m1", "L20m1"]
 
 
-def tile(tag, face=None, nq=3, **kw):
-    """the periodic tile 12 x 10, or one 12 x 12 face of a C12 cube, on the fixture's levels"""
+def tile(tag, face=None, nq=3, size=None, **kw):
+    """the periodic tile 12 x 10 (or size), or one 12 x 12 face of a C12 cube, on the fixture's levels"""
     from common import Case
-    nx, ny = (12, 10) if face is None else (12, 12)
+    nx, ny = (size or (12, 10)) if face is None else (12, 12)
     fx = KC.fixture(tag)
     kw = kw or KC.case_kw(fx)
     return Case(nx=nx, ny=ny, npz=fx["lm"], n_split=2, dt=1800.0, nq=nq, backend=BACKEND, oracle=False, face=face, **kw)
@@ -57,8 +57,26 @@ def test_dot_product_of_the_chain(tag):
 
 def test_position_independence():
     """check 7: the L40 columns dealt over the six faces of a C16 cube and over its 2 x 2 sub-face layout: every column's set outputs,
-    fractions, switch and tangent results as on the small tile, bitwise"""
-    KC.check_position(lambda: tile("L40m2"), lambda L: cube("L40m2", L, 3, 16), "L40m2", 2)
+    fractions, switch and tangent results, adjoint results with cfcn and the source adjoints, and the qi, ql and CF_con of the nonlinear
+    run as on the small tile, bitwise"""
+    KC.check_position(lambda: tile("L40m2"), lambda L: cube("L40m2", L, 3, 16), "L40m2", 2, key=BACKEND)
+
+
+@pytest.mark.parametrize("where", ["six faces C24 L40", "tile 64 x 32 L20", "tile 64 x 40 L40"])
+def test_columns_beyond_one_batch(where, monkeypatch, capfd):
+    """check 7b: 3,456, 2,048 and 2,560 columns against a batch whose size the library reports: two batches, the second partial, on the
+    first and the last case (on the cube the boundary falls inside a face); exactly one full batch on the second.  Every column, every
+    mode, as on the small tile: bitwise"""
+    monkeypatch.setenv("FV3LM_VERBOSE", "1")
+    tag = "L20m1" if "L20" in where else "L40m2"
+    big = (lambda: cube(tag, 1, 3, 24)) if "six" in where else (lambda: tile(tag, None, 3, (64, 32) if tag == "L20m1" else (64, 40)))
+    KC.check_batches(lambda: tile(tag), big, tag, lambda: capfd.readouterr().err, full=tag == "L20m1", key=BACKEND)
+
+
+def test_reset_and_two_slots():
+    """check 7c: two slots with different trajectories run in turn; a convection slot set again refuses the cloud run until the cloud
+    slot is set again; then slot 0 equals slot 1 and a fresh single-slot handle, bitwise"""
+    KC.check_reset_and_slots(lambda: tile("L40m2"), "L40m2")
 
 
 @pytest.mark.parametrize("where", ["tile", "six faces"])
