@@ -30,13 +30,8 @@
 // + 9 w (+ 2 w with raw_out), the factorisation that follows 9 r + 6 w + delp r + pk w: about 52 words = 416 B, plus the upload of qa, qb.
 #pragma once
 #include "turbulence.h"
+#include "litcol.h"
 #include <vector>
-
-#if defined(__clang__)
-#define FV3LM_BL_LITERAL _Pragma("clang fp contract(off)")
-#else
-#define FV3LM_BL_LITERAL
-#endif
 
 namespace fv3 {
 
@@ -108,7 +103,7 @@ inline std::vector<double> bl_esinit() {
 // ---- device --------------------------------------------------------------------------------------------------------------------------
 // DQSAT_sub_sca (:1466-1518): piecewise-linear lookup, clamped at TMAXTBL - .001; the index is kept inside the table whatever TEMP is
 HD void bl_dqsat(double& dqsi, double& qssi, double temp, double plo, const double* tbl) {
-  FV3LM_BL_LITERAL
+  FV3LM_LITERAL
   const double ESFAC = blc::H2OMW / blc::AIRMW;
   const double pp = plo * 100.0;
   double ti = temp;
@@ -125,7 +120,7 @@ HD void bl_dqsat(double& dqsi, double& qssi, double temp, double plo, const doub
 }
 // IceFraction (utils/fv3jedi_lm_utils_mod.F90:295-319)
 HD double bl_icefraction(double temp) {
-  FV3LM_BL_LITERAL
+  FV3LM_LITERAL
   const double t_ice_all = 233.16, t_ice_max = 273.16;
   double f = 0.0;
   if (temp <= t_ice_all) f = 1.000; else if (temp <= t_ice_max) f = 1.00 - (temp - t_ice_all) / (t_ice_max - t_ice_all);
@@ -137,7 +132,7 @@ HD double bl_icefraction(double temp) {
 // LOUIS_DIFF (:444-498) at one interface: the layer above (zzu pvu uu vu), the layer below (zz pv u v), the interface height ze
 HD void bl_louis(const BlParams& p, double pbllocal, double zzu, double zz, double pvu, double pv, double uu, double vu, double u, double v,
                  double ze, double& kh, double& km) {
-  FV3LM_BL_LITERAL
+  FV3LM_LITERAL
   const double LOUIS = p.r[0], LAMBDAM2 = p.r[2], LAMBDAH2 = p.r[4], ZKMENV = p.r[5], ZKHENV = p.r[6], MINTHICK = p.r[7], MINSHEAR = p.r[8], AKHMMAX = p.r[11];
   const double almfac = 1.2, alhfac = 1.2;
   double dz = zzu - zz;
@@ -171,7 +166,7 @@ HD void bl_louis(const BlParams& p, double pbllocal, double zzu, double zz, doub
 struct BlDriverFn {
   BlArgs a;
   HD void operator()(int i, int j, int t) const {
-    FV3LM_BL_LITERAL
+    FV3LM_LITERAL
     using namespace blc;
     const TurbArgs& ta = a.t;
     const int lm = ta.g.npz; const size_t pl = ta.g.plane, o = ta.col(t, i, j), os = (size_t)t * pl + ta.g.idx(i, j);

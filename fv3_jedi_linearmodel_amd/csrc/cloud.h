@@ -3,7 +3,7 @@
 // Column-local; it follows the RAS convection of convection.h in every column and reads that feature's slot.
 //
 // The routine is written ONCE on a generic scalar T and run as values (double), tangent (RD) and adjoint (RV on the Tape of
-// coltape.h), the scalars and the contraction rule of convection.h.  cloud_tl.F90 is NOT everywhere the derivative of cloud.F90; where it
+// coltape.h), the scalars and the contraction rule of litcol.h.  cloud_tl.F90 is NOT everywhere the derivative of cloud.F90; where it
 // is not, cloud_tl.F90 rules and the place is marked "TL:" below (DESIGN.md section 3 lists them with their line numbers).  At MIN / MAX /
 // IF on a value the branch is taken on the value and the side is Tapenade's, read off cloud_tl.F90.
 //
@@ -47,11 +47,11 @@ constexpr double PI = 3.1415927410125732;      // MAPL_PI is a 4-byte real and f
 }
 
 // out with the perturbation c out' + (1 - c) in' (the sink and total filters, cloud_tl.F90:797-839): the value is out's
-HD double cld_blend(double o, double, double) { FV3LM_RAS_LITERAL return o; }
-HD RD cld_blend(const RD& o, const RD& i, double c) { FV3LM_RAS_LITERAL return RD(o.v, c * o.d + (1.0 - c) * i.d); }
-HD RV cld_blend(const RV& o, const RV& i, double c) { FV3LM_RAS_LITERAL return rv2(o, i, o.v, c, 1.0 - c); }
+HD double cld_blend(double o, double, double) { FV3LM_LITERAL return o; }
+HD RD cld_blend(const RD& o, const RD& i, double c) { FV3LM_LITERAL return RD(o.v, c * o.d + (1.0 - c) * i.d); }
+HD RV cld_blend(const RV& o, const RV& i, double c) { FV3LM_LITERAL return rv2(o, i, o.v, c, 1.0 - c); }
 // x ** p, p not an integer: Tapenade's derivative is 0 unless x > 0
-template <class T> HD T cld_pow(const T& x, double p) { FV3LM_RAS_LITERAL
+template <class T> HD T cld_pow(const T& x, double p) { FV3LM_LITERAL
   const double v = rval(x);
   return v > 0.0 ? run1(x, pow(v, p), p * pow(v, p - 1.)) : T(pow(v, p));
 }
@@ -60,11 +60,11 @@ struct CldCol {
   int lm, mst, khu, khl;
   ColWs g; const double* tbl; const double* r;
   double dt, frland;
-  HD double G(int v, int l) const { FV3LM_RAS_LITERAL return g.at(v, l); }
+  HD double G(int v, int l) const { FV3LM_LITERAL return g.at(v, l); }
 };
 
 // GET_ICE_FRACTION (cloud_tl.F90:2350-2393)
-template <class T> HD T cld_icefrac(const T& temp, double t_ice_all, double t_ice_max, int pwr) { FV3LM_RAS_LITERAL
+template <class T> HD T cld_icefrac(const T& temp, double t_ice_all, double t_ice_max, int pwr) { FV3LM_LITERAL
   const double t = rval(temp);
   T f(0.00);
   if (t <= t_ice_all) f = T(1.000);
@@ -77,7 +77,7 @@ template <class T> HD T cld_icefrac(const T& temp, double t_ice_all, double t_ic
   return x > 0.0 ? run1(f, v, pwr * v1) : T(v);
 }
 // MELTFREEZE (:991-1055)
-template <class T> HD void cld_meltfreeze(double dt, T& te, T& ql, T& qi, double t_ice_all, double t_ice_max, int pwr) { FV3LM_RAS_LITERAL
+template <class T> HD void cld_meltfreeze(double dt, T& te, T& ql, T& qi, double t_ice_all, double t_ice_max, int pwr) { FV3LM_LITERAL
   using namespace cldc;
   const double taufrz = 1000.;
   const T fqi = cld_icefrac(te, t_ice_all, t_ice_max, pwr);
@@ -97,7 +97,7 @@ template <class T> HD void cld_meltfreeze(double dt, T& te, T& ql, T& qi, double
   te = te + (ALHS - ALHL) * dqil / CP;
 }
 // CLOUD_TIDY (:897-986)
-template <class T> HD void cld_tidy(T& qv, T& te, T& qlc, T& qic, T& cf, T& qla, T& qia, T& af) { FV3LM_RAS_LITERAL
+template <class T> HD void cld_tidy(T& qv, T& te, T& qlc, T& qic, T& cf, T& qla, T& qia, T& af) { FV3LM_LITERAL
   using namespace cldc;
   if (rval(af) < 1.e-5) { qv = qv + qla + qia; te = te - ALHL / CP * qla - ALHS / CP * qia; af = T(0.); qla = T(0.); qia = T(0.); }
   if (rval(qlc) < 1.e-8) { qv = qv + qlc; te = te - ALHL / CP * qlc; qlc = T(0.); }
@@ -109,7 +109,7 @@ template <class T> HD void cld_tidy(T& qv, T& te, T& qlc, T& qic, T& cf, T& qla,
 }
 // CONVEC_SRC (:1060-1148)
 template <class T> HD void cld_convec_src(double dt, double imass, T& te, T& qv, const T& dcf, const T& dmf, T& qla, T& qia, T& af, const T& qs,
-                                          double t_ice_all, double t_ice_max, int pwr) { FV3LM_RAS_LITERAL
+                                          double t_ice_all, double t_ice_max, int pwr) { FV3LM_LITERAL
   using namespace cldc;
   const double minrhx = 0.001;
   T tend = dcf * imass;
@@ -131,7 +131,7 @@ template <class T> HD void cld_convec_src(double dt, double imass, T& te, T& qv,
   }
 }
 // the top-hat of PDFFRAC (flag 1, :1484-1502)
-template <class T> HD T cld_tophat(const T& qt, const T& s1, const T& qstar) { FV3LM_RAS_LITERAL
+template <class T> HD T cld_tophat(const T& qt, const T& s1, const T& qstar) { FV3LM_LITERAL
   if (rval(qt) + rval(s1) < rval(qstar)) return T(0.);
   if (rval(s1) > 0.) {
     T min1;
@@ -142,7 +142,7 @@ template <class T> HD T cld_tophat(const T& qt, const T& s1, const T& qstar) { F
 }
 // PDFFRAC (:1463-1600), flag 1 and flag 4.  TL: with flag 4 the value is the top-hat and the perturbation the linear ramp in RH between
 // 0.9335 and 1.0665 times 0.2 (:1564-1596)
-template <class T> HD T cld_pdffrac(int flag, const T& qt, const T& s1, const T& qstar) { FV3LM_RAS_LITERAL
+template <class T> HD T cld_pdffrac(int flag, const T& qt, const T& s1, const T& qstar) { FV3LM_LITERAL
   const T top = cld_tophat(qt, s1, qstar);
   if (flag == 1) return top;
   const T rh = qt / qstar;
@@ -151,7 +151,7 @@ template <class T> HD T cld_pdffrac(int flag, const T& qt, const T& s1, const T&
   return T(rval(top));
 }
 // PDFCONDENSATE (:1605-1750), flag 1
-template <class T> HD T cld_pdfcond(const T& qt, const T& s1, const T& qstar) { FV3LM_RAS_LITERAL
+template <class T> HD T cld_pdfcond(const T& qt, const T& s1, const T& qstar) { FV3LM_LITERAL
   if (rval(qt) + rval(s1) < rval(qstar)) return T(0.);
   if (rval(qstar) > rval(qt) - rval(s1)) {
     if (rval(s1) > 0.) {
@@ -165,7 +165,7 @@ template <class T> HD T cld_pdfcond(const T& qt, const T& s1, const T& qstar) { 
 }
 // LS_CLOUD (:1153-1457), PDFSHAPE = 1
 template <class T> HD void cld_ls_cloud(const CldCol& c, double alpha, double pl, T& te, T& qv, T& qcl, T& qal, T& qci, T& qai, T& cf, T& af,
-                                        double t_ice_all, double t_ice_max, int pwr, int pertmod, int dmp) { FV3LM_RAS_LITERAL
+                                        double t_ice_all, double t_ice_max, int pwr, int pertmod, int dmp) { FV3LM_LITERAL
   using namespace cldc;
   const T qc = qcl + qci, qa = qal + qai;
   T dqsx, qsx;
@@ -225,7 +225,7 @@ template <class T> HD void cld_ls_cloud(const CldCol& c, double alpha, double pl
   }
 }
 // EVAP_CNV (:1755-1835) and SUBL_CNV (:1840-1920): ice false / true.  TL: the in-cloud condensate QCm carries no perturbation (:1802, :1887)
-template <class T> HD void cld_evap_subl(bool ice, double dt, double rhcr, double pl, T& te, T& qv, T& ql, T& qi, T& f, const T& qs, double cld_evp_eff) { FV3LM_RAS_LITERAL
+template <class T> HD void cld_evap_subl(bool ice, double dt, double rhcr, double pl, T& te, T& qv, T& ql, T& qi, T& f, const T& qs, double cld_evp_eff) { FV3LM_LITERAL
   using namespace cldc;
   const double k_cond = 2.4e-2, diffu = 2.2e-5, nn = ice ? 5. * 1.0e6 : 50. * 1.0e6;
   const double epsilon = H2OMW / AIRMW, a_eff = cld_evp_eff;
@@ -252,7 +252,7 @@ template <class T> HD void cld_evap_subl(bool ice, double dt, double rhcr, doubl
 }
 // AUTOCONVERSION_LS (:1955-2150) and _CNV (:2155-2345).  TL: the perturbation of F2 is halved (:1992, :2192)
 template <class T> HD void cld_autoconv(bool ls, double dt, T& qc, T& qp, const T& te, double pl, T& f, double sundqv2, double sundqv3, double sundqt1,
-                                        double c_00, double lwcrit) { FV3LM_RAS_LITERAL
+                                        double c_00, double lwcrit) { FV3LM_LITERAL
   const double tv = rval(te);
   const T f2full = ras_sundq3(te, sundqv2, sundqv3, sundqt1);
   const T f2 = run1(f2full, rval(f2full), 0.5);
@@ -307,7 +307,7 @@ template <class T> HD void cld_autoconv(bool ls, double dt, T& qc, T& qp, const 
 }
 // ICE_SETTLEFALL_CNV (:2512-2592) and _LS (:2597-2692)
 template <class T> HD void cld_settlefall(bool ls, double wxr, T& qi, double pl, const T& te, T& f, int khu, int khl, int k, double dt, const T& dz, T& qp,
-                                          double icefall_c) { FV3LM_RAS_LITERAL
+                                          double icefall_c) { FV3LM_LITERAL
   using namespace cldc;
   const T rho = 1000. * 100. * pl / (RGAS * te);
   T xim(0.);
@@ -331,7 +331,7 @@ template <class T> HD void cld_settlefall(bool ls, double wxr, T& qi, double pl,
   if (ls && rval(qi) + rval(qixp) > 0.) f = qi * f / (qi + qixp);
 }
 // MARSHPALM (:3033-3134): diam3, w, ve
-template <class T> HD void cld_marshpalm(const T& rain, double pr, T& diam3, T& w, T& ve) { FV3LM_RAS_LITERAL
+template <class T> HD void cld_marshpalm(const T& rain, double pr, T& diam3, T& w, T& ve) { FV3LM_LITERAL
   const double rx[8] = {0., 5., 20., 80., 320., 1280., 5120., 20480.}, d3x[8] = {0.019, 0.032, 0.043, 0.057, 0.076, 0.102, 0.137, 0.183};
   const T rain_day = rain * 3600. * 24.;
   const double rd = rval(rain_day);
@@ -349,7 +349,7 @@ template <class T> HD void cld_marshpalm(const T& rain, double pr, T& diam3, T& 
 // PRECIPANDEVAP (:2700-3028).  above: PFL PFI EVAP_DD SUBL_DD, in: what the level above left, out: what this level leaves
 template <class T> HD void cld_precipandevap(const CldCol& c, int k, double rhcr3, T& qpl, T& qpi, T& qcl, T& te, T& qv, double mass, double imass, double pl,
                                              const T& dze, const T& qddf3, const T& aa, const T& bb, const T& area, T* above, double envfc, double ddrfc,
-                                             double revap_off_p, double c_acc, double c_ev_r, double c_ev_s) { FV3LM_RAS_LITERAL
+                                             double revap_off_p, double c_acc, double c_ev_r, double c_ev_s) { FV3LM_LITERAL
   using namespace cldc;
   const double b_sub = 1.00, envfrac = envfc, ddfract = ddrfc, landseaf = 1.00;
   T ifactor(1.00);
@@ -438,7 +438,7 @@ template <class T> HD void cld_precipandevap(const CldCol& c, int k, double rhcr
   above[0] = pfl; above[1] = pfi; above[2] = evap_dd; above[3] = subl_dd;
 }
 // PDF_WIDTH (cloud.F90:1045-1096)
-HD double cld_pdf_width(double pp, double frland, double maxrhcrit, double maxrhcritland, double turnrhcrit, double minrhcrit) { FV3LM_RAS_LITERAL
+HD double cld_pdf_width(double pp, double frland, double maxrhcrit, double maxrhcritland, double turnrhcrit, double minrhcrit) { FV3LM_LITERAL
   const double pi_0 = 4. * atan(1.);
   double tempmaxrh = maxrhcrit;
   if (frland > 0.05) tempmaxrh = maxrhcritland;
@@ -450,10 +450,8 @@ HD double cld_pdf_width(double pp, double frland, double maxrhcrit, double maxrh
   return alpha < 0.25 ? alpha : 0.25;
 }
 
-template <class T> using CldVecs = RasVecs<T>;
-
 // ---- real parts of the eigenvalues of an 8 x 8 matrix: balancing-free Hessenberg reduction and shifted QR (EISPACK elmhes / hqr) -----------
-HD double cld_max_abs_wr(double a[8][8]) { FV3LM_RAS_LITERAL
+HD double cld_max_abs_wr(double a[8][8]) { FV3LM_LITERAL
   const int n = 8;
   for (int m = 1; m < n - 1; ++m) {      // elmhes
     double x = 0.; int i = m;
@@ -547,7 +545,7 @@ HD double cld_max_abs_wr(double a[8][8]) { FV3LM_RAS_LITERAL
 
 // ---- pre (:246-302)
 template <class T>
-HD void cld_pre(const CldCol& c, const CldVecs<T>& V) { FV3LM_RAS_LITERAL
+HD void cld_pre(const CldCol& c, const LitVecs<T>& V) { FV3LM_LITERAL
   using namespace cldc;
   const int lm = c.lm;
   const RArr<T> TE = V(CE_T), QS = V(CE_QS), DZET = V(CE_DZET), QDDF3 = V(CE_QDDF3);
@@ -574,7 +572,7 @@ HD void cld_pre(const CldCol& c, const CldVecs<T>& V) { FV3LM_RAS_LITERAL
 // ---- one level (:328-841).  pertmod: the switch of this cell (do_moist_physics = 1: 1).  jac (values, do_moist_physics = 2): the cell
 // computes its own switch from the Jacobian of LS_CLOUD_D (:405-481) and returns it
 template <class T>
-HD int cld_level(const CldCol& c, const CldVecs<T>& V, int k, int pertmod, bool jac) { FV3LM_RAS_LITERAL
+HD int cld_level(const CldCol& c, const LitVecs<T>& V, int k, int pertmod, bool jac) { FV3LM_LITERAL
   using namespace cldc;
   const double* p = c.r;
   const double cnv_beta = p[0], anv_beta = p[1], ls_beta = p[2], rh00 = p[3], c_00 = p[4], lwcrit = p[5], c_acc = p[6], c_ev_r = p[7], c_ev_s = p[55],
@@ -692,7 +690,7 @@ HD int cld_level(const CldCol& c, const CldVecs<T>& V, int k, int pertmod, bool 
 
 // ---- post (:844-890)
 template <class T>
-HD void cld_post(const CldCol& c, const CldVecs<T>& V) { FV3LM_RAS_LITERAL
+HD void cld_post(const CldCol& c, const LitVecs<T>& V) { FV3LM_LITERAL
   using namespace cldc;
   const int lm = c.lm;
   const double rhexcess = 1.1;
@@ -715,24 +713,22 @@ HD void cld_post(const CldCol& c, const CldVecs<T>& V) { FV3LM_RAS_LITERAL
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------------
-struct CldArgs {
-  RasArgs r;                        // geometry, pt q1, the convection slot (PTT_C QVT_C, the four _C sources, PLE, PKZ, FRLAND), the sources' perturbation
+struct CldArgs : ColView, ColWork {      // the cloud slot's packed columns and the columns of this launch; the work spaces of the batch
+  double* rslot;                    // the convection slot of the same number: PTT_C QVT_C, the four _C sources, PLE, PKZ, FRLAND
   int mst;
-  Fld qi, ql;
-  double* slot;                     // the cloud slot, packed columns as the convection slot
+  Fld pt, delp, q1, qi, ql;
   double* cfcn;                     // perturbation of the convective cloud fraction, host-compact [ntile][lm][ty][tx]
-  double *gw, *tw, *ew, *ck; TapeMem tape; int nb;
-  CldParams p;
-  int* flag;
-  HD int kw() const { FV3LM_RAS_LITERAL return r.lm + 2 < CLD_NSV + 2 ? CLD_NSV + 2 : r.lm + 2; }
-  HD double& S(int v, int l, size_t col) const { FV3LM_RAS_LITERAL return slot[((size_t)v * (r.lm + 1) + l) * r.nc + col]; }
-  HD double& SC(int s, size_t col) const { FV3LM_RAS_LITERAL return slot[((size_t)CLD_NS * (r.lm + 1) + s) * r.nc + col]; }
-  HD CldCol column(int m, size_t col) const { FV3LM_RAS_LITERAL
-    CldCol c; c.lm = r.lm; c.mst = mst; c.khl = (int)SC(CSC_KHL, col); c.khu = (int)SC(CSC_KHU, col);
-    c.g = ColWs{gw + m, (size_t)nb, kw()}; c.tbl = r.tbl; c.r = p.r; c.dt = r.dt; c.frland = r.SC(SC_FRLAND, col);
+  double* src;                      // the four sources' perturbation (convection.h)
+  const double* tbl; CldParams p;
+  double dt, ptop, p00k;
+  HD ColView ras() const { FV3LM_LITERAL ColView r = *this; r.slot = rslot; r.ns = RAS_NS; return r; }
+  HD int kw() const { FV3LM_LITERAL return lm + 2 < CLD_NSV + 2 ? CLD_NSV + 2 : lm + 2; }
+  HD CldCol column(int m, size_t col) const { FV3LM_LITERAL
+    CldCol c; c.lm = lm; c.mst = mst; c.khl = (int)SC(CSC_KHL, col); c.khu = (int)SC(CSC_KHU, col);
+    c.g = ColWs{gw + m, (size_t)nb, kw()}; c.tbl = tbl; c.r = p.r; c.dt = dt; c.frland = ras().SC(SC_FRLAND, col);
     // p = ple 0.01, ph, pi = (p / 1000) ** (rgas / cp), pih, mass, dp, dm (:247-255, :267, :304-305)
     double p0 = S(CS_PLE, 0, col) * 0.01, pi0 = pow(p0 / 1000., cldc::RGAS / cldc::CP);
-    for (int l = 1; l <= r.lm; ++l) {
+    for (int l = 1; l <= lm; ++l) {
       const double p1 = S(CS_PLE, l, col) * 0.01, pi1 = pow(p1 / 1000., cldc::RGAS / cldc::CP);
       const double ph = 0.5 * (p0 + p1);
       c.g.at(CG_PH, l) = ph; c.g.at(CG_PIH, l) = pow(ph / 1000., cldc::RGAS / cldc::CP);
@@ -743,8 +739,9 @@ struct CldArgs {
     return c;
   }
   // the trajectory the driver starts from, as values of the state vectors
-  HD void load(const ColWs& w, size_t col) const { FV3LM_RAS_LITERAL
-    for (int l = 1; l <= r.lm; ++l) {
+  HD void load(const ColWs& w, size_t col) const { FV3LM_LITERAL
+    const ColView r = ras();
+    for (int l = 1; l <= lm; ++l) {
       w.at(CE_T, l) = r.S(S_OUT, l - 1, col); w.at(CE_Q, l) = r.S(S_OUT + 1, l - 1, col);
       w.at(CE_QILS, l) = S(CS_QILS, l - 1, col); w.at(CE_QLLS, l) = S(CS_QLLS, l - 1, col); w.at(CE_QICN, l) = S(CS_QICN, l - 1, col);
       w.at(CE_QLCN, l) = S(CS_QLCN, l - 1, col); w.at(CE_CFLS, l) = 0.; w.at(CE_CFCN, l) = S(CS_CFCN, l - 1, col);
@@ -757,15 +754,15 @@ struct CldArgs {
 // per-cell switch; what: 0 set, 1 nonlinear run (the same sweep; the trajectory tracers are written and the slot is left alone)
 struct CldSetFn {
   CldArgs a; int what;
-  HD void operator()(int m, int, int) const { FV3LM_RAS_LITERAL
-    const RasArgs& r = a.r;
+  HD void operator()(int m, int, int) const { FV3LM_LITERAL
+    const ColView r = a.ras();
     const size_t col = r.col_of(m); const int lm = r.lm;
     if (what == 0) {
-      double pe = r.ptop;
+      double pe = a.ptop;
       a.S(CS_PLE, 0, col) = pe;
       bool bad = false;
       for (int l = 0; l < lm; ++l) {
-        pe = pe + r.delp.t[r.fld(col, l)];
+        pe = pe + a.delp.t[r.fld(col, l)];
         a.S(CS_PLE, l + 1, col) = pe;
         const double plo = 0.5 * (r.S(S_PLE, l, col) + r.S(S_PLE, l + 1, col));
         const double temp = r.S(S_THO, l, col) * pow(plo / 1000.0, cldc::RGAS / cldc::CP);
@@ -783,7 +780,7 @@ struct CldSetFn {
     }
     const CldCol c = a.column(m, col);
     const ColWs tw{a.tw + m, (size_t)a.nb, a.kw()};
-    const CldVecs<double> V{tw, nullptr};
+    const LitVecs<double> V{tw, nullptr};
     a.load(tw, col);
     cld_pre<double>(c, V);
     for (int k = CLD_KTOP; k <= lm; ++k) {
@@ -807,19 +804,19 @@ struct CldSetFn {
 // tangent (:429-438 in, :495-501 out of fv3jedi_lm_moist_mod.F90 around CLOUD_DRIVER_D)
 struct CldTlFn {
   CldArgs a;
-  HD void operator()(int m, int, int) const { FV3LM_RAS_LITERAL
-    const RasArgs& r = a.r;
+  HD void operator()(int m, int, int) const { FV3LM_LITERAL
+    const ColView r = a.ras();
     const size_t col = r.col_of(m); const int lm = r.lm, kw = a.kw();
     const CldCol c = a.column(m, col);
     const ColWs ew{a.ew + m, (size_t)a.nb, kw}, tw{a.tw + m, (size_t)a.nb, kw};
-    const CldVecs<RD> V{tw, nullptr};
+    const LitVecs<RD> V{tw, nullptr};
     const size_t n3c = (size_t)r.ntile * lm * r.g.tx * r.g.ty;
     a.load(ew, col);
     for (int l = 1; l <= lm; ++l) {
       const size_t n = r.fld(col, l - 1), nc = r.cmp(col, l - 1);
       const double pk = r.S(S_PKZ, l - 1, col), qi = a.qi.p[n], ql = a.ql.p[n];
-      const double d[12] = {r.pt.p[n] * r.p00k / pk, r.q1.p[n], qi * a.S(CS_FRAC, l - 1, col), ql * a.S(CS_FRAC + 2, l - 1, col), qi * a.S(CS_FRAC + 1, l - 1, col),
-                            ql * a.S(CS_FRAC + 3, l - 1, col), 0., a.cfcn[nc], r.src[nc], r.src[n3c + nc], r.src[2 * n3c + nc], r.src[3 * n3c + nc]};
+      const double d[12] = {a.pt.p[n] * a.p00k / pk, a.q1.p[n], qi * a.S(CS_FRAC, l - 1, col), ql * a.S(CS_FRAC + 2, l - 1, col), qi * a.S(CS_FRAC + 1, l - 1, col),
+                            ql * a.S(CS_FRAC + 3, l - 1, col), 0., a.cfcn[nc], a.src[nc], a.src[n3c + nc], a.src[2 * n3c + nc], a.src[3 * n3c + nc]};
       for (int v = 0; v < 12; ++v) V(v).set(l, RD(ew.at(v, l), d[v]));
     }
     cld_pre<RD>(c, V);
@@ -828,7 +825,7 @@ struct CldTlFn {
     for (int l = 1; l <= lm; ++l) {
       const size_t n = r.fld(col, l - 1), nc = r.cmp(col, l - 1);
       const double pk = r.S(S_PKZ, l - 1, col);
-      r.pt.p[n] = V(CE_T)(l).d * pk / r.p00k; r.q1.p[n] = V(CE_Q)(l).d;
+      a.pt.p[n] = V(CE_T)(l).d * pk / a.p00k; a.q1.p[n] = V(CE_Q)(l).d;
       a.qi.p[n] = V(CE_QILS)(l).d + V(CE_QICN)(l).d; a.ql.p[n] = V(CE_QLLS)(l).d + V(CE_QLCN)(l).d;
       a.cfcn[nc] = V(CE_CFCN)(l).d;
     }
@@ -838,22 +835,22 @@ struct CldTlFn {
 // adjoint (:542-551 in, :607-616 out around CLOUD_DRIVER_B): values sweep with the checkpoints, then the segments last to first
 struct CldAdFn {
   CldArgs a;
-  HD void operator()(int m, int, int) const { FV3LM_RAS_LITERAL
-    const RasArgs& r = a.r;
+  HD void operator()(int m, int, int) const { FV3LM_LITERAL
+    const ColView r = a.ras();
     const size_t col = r.col_of(m); const int lm = r.lm, kw = a.kw();
     const CldCol c = a.column(m, col);
     const ColWs tw{a.tw + m, (size_t)a.nb, kw}, ew{a.ew + m, (size_t)a.nb, kw}, ck{a.ck + m, (size_t)a.nb, kw};
     const ColWs eb{a.ew + (size_t)CLD_NE * kw * a.nb + m, (size_t)a.nb, kw};
     Tape tape; tape.m = a.tape; tape.col = (size_t)m; tape.n = 0;
-    const CldVecs<double> EV{ew, nullptr};
-    const CldVecs<RV> TV_{tw, &tape};
+    const LitVecs<double> EV{ew, nullptr};
+    const LitVecs<RV> TV_{tw, &tape};
     const size_t n3c = (size_t)r.ntile * lm * r.g.tx * r.g.ty;
     for (int v = 0; v < CLD_NE; ++v) for (int l = 0; l < kw; ++l) { ew.at(v, l) = 0.; eb.at(v, l) = 0.; }
     a.load(ew, col);
     for (int l = 1; l <= lm; ++l) {
       const size_t n = r.fld(col, l - 1);
       const double pk = r.S(S_PKZ, l - 1, col), qi = a.qi.p[n], ql = a.ql.p[n];
-      eb.at(CE_T, l) = r.pt.p[n] * pk / r.p00k; eb.at(CE_Q, l) = r.q1.p[n];
+      eb.at(CE_T, l) = a.pt.p[n] * pk / a.p00k; eb.at(CE_Q, l) = a.q1.p[n];
       eb.at(CE_QILS, l) = qi; eb.at(CE_QICN, l) = qi; eb.at(CE_QLLS, l) = ql; eb.at(CE_QLCN, l) = ql;
       eb.at(CE_CFCN, l) = a.cfcn[r.cmp(col, l - 1)];
     }
@@ -869,13 +866,8 @@ struct CldAdFn {
     // one segment on the tape.  which 0 pre, 1 level k, 2 post.  Leaves are what the segment reads of E, and the incoming adjoints move
     // onto what it writes: pre reads theta and writes T QS DZET QDDF3 and the carried scalars; a level reads and writes its own cell of the
     // 15 vectors and the carried scalars; post reads and writes T and Q
-    auto leaf = [&](int v, int l) { RW<RV>::set(tw, v, l, RV(ew.at(v, l), 1., tape.push(-2 - (v * kw + l), -1, 0., 0.), &tape)); };
-    auto seed = [&](int v, int l) {
-      const double gb = eb.at(v, l);
-      eb.at(v, l) = 0.;
-      const int id = (int)tw.at(2 * v + 1, l);
-      if (id >= 0 && gb != 0.) tape.ad(id) += gb;
-    };
+    auto leaf = [&](int v, int l) { lit_leaf(tape, tw, ew, kw, v, l); };
+    auto seed = [&](int v, int l) { lit_seed(tape, tw, eb, v, l); };
     auto segment = [&](int which, int k) {
       tape.n = 0;
       if (which == 0) { for (int l = 1; l <= lm; ++l) leaf(CE_T, l); cld_pre<RV>(c, TV_); }
@@ -892,16 +884,7 @@ struct CldAdFn {
         for (int v = 0; v < CE_SV; ++v) seed(v, k);
         for (int n = 1; n <= CLD_NSV; ++n) seed(CE_SV, n);
       } else for (int l = 1; l <= lm; ++l) { seed(CE_T, l); seed(CE_Q, l); }
-      for (int id = tape.n - 1; id >= 0; --id) {
-        const size_t e = (size_t)id * tape.m.stride + tape.col;
-        const double ad = tape.m.adj[e];
-        if (ad == 0.) continue;
-        const TapeIdx ix = tape.m.idx[e];
-        if (ix.a <= -2) { const int q = -2 - ix.a; eb.at(q / kw, q % kw) += ad; continue; }
-        const TapePart pt = tape.m.part[e];
-        if (ix.a >= 0) tape.ad(ix.a) += pt.a * ad;
-        if (ix.b >= 0) tape.ad(ix.b) += pt.b * ad;
-      }
+      lit_walk_back(tape, eb, kw);
     };
     segment(2, 0);
     for (int k = lm; k >= CLD_KTOP; --k) {
@@ -915,18 +898,18 @@ struct CldAdFn {
     for (int l = 1; l <= lm; ++l) {
       const size_t n = r.fld(col, l - 1), nc = r.cmp(col, l - 1);
       const double pk = r.S(S_PKZ, l - 1, col);
-      r.pt.p[n] = eb.at(CE_T, l) * r.p00k / pk; r.q1.p[n] = eb.at(CE_Q, l);
+      a.pt.p[n] = eb.at(CE_T, l) * a.p00k / pk; a.q1.p[n] = eb.at(CE_Q, l);
       a.qi.p[n] = eb.at(CE_QILS, l) * a.S(CS_FRAC, l - 1, col) + eb.at(CE_QICN, l) * a.S(CS_FRAC + 1, l - 1, col);
       a.ql.p[n] = eb.at(CE_QLLS, l) * a.S(CS_FRAC + 2, l - 1, col) + eb.at(CE_QLCN, l) * a.S(CS_FRAC + 3, l - 1, col);
       a.cfcn[nc] = eb.at(CE_CFCN, l);
-      for (int v = 0; v < 4; ++v) r.src[(size_t)v * n3c + nc] = eb.at(CE_DQL + v, l);
+      for (int v = 0; v < 4; ++v) a.src[(size_t)v * n3c + nc] = eb.at(CE_DQL + v, l);
     }
   }
 };
 
 inline void run_cloud(Exec& ex, int what, const CldArgs& a) {      // what: -1 set, 0 nl, 1 tl, 2 ad
-  const Rect R{0, a.r.n - 1, 0, 0};
-  if (a.r.n <= 0) return;
+  const Rect R{0, a.n - 1, 0, 0};
+  if (a.n <= 0) return;
   if (what == -1) for_points(ex, R, 1, CldSetFn{a, 0}, "cloud_set");
   else if (what == MODE_NL) for_points(ex, R, 1, CldSetFn{a, 1}, "cloud.nl");
   else if (what == MODE_TL) for_points(ex, R, 1, CldTlFn{a}, "cloud.tl");

@@ -3,8 +3,8 @@
 // (fv3jedi_lm_moist_mod.F90:649-832, jacobian_filter_tlm :897-973) prepares around them.  Column-local.
 //
 // The routine is written ONCE on a generic scalar T and run as values (double), tangent (RD, a dual number) and adjoint (RV, a taped
-// scalar on the Tape of coltape.h).  Both scalars are this file's own because their operators must be compiled with contraction into fused multiply-adds off (the pragma acts
-// where an operator is defined, and Dual / TV of core.h / coltape.h serve kernels that are built with it on): the
+// scalar on the Tape of coltape.h): the scalars of litcol.h, compiled like every function of this file with contraction into fused
+// multiply-adds off (FV3LM_LITERAL), because the
 // fixture is the reference's double result in the routine's order of operations.  At every kink the branch is taken on the VALUE and
 // the side is Tapenade's (convection_tl.F90): MIN / MAX keep the first argument's derivative unless the second wins strictly as there,
 // a clipped value is a constant, SQRT has derivative 0 at 0, a cloud type that leaves by a CYCLE before its update is the identity.
@@ -26,15 +26,8 @@
 // Launch shape: one thread per column of a dense list (set: all columns; runs: the DOCONVEC columns, listed at set time), work vectors
 // [vector][level][column of the batch] so that the lanes of a wave touch contiguous rows.
 #pragma once
-#include "coltape.h"
+#include "litcol.h"
 #include "bldriver.h"
-
-// contraction off in every function of this file, scoped to the function as FV3LM_BL_LITERAL is: nothing outlives the header
-#if defined(__clang__)
-#define FV3LM_RAS_LITERAL _Pragma("clang fp contract(off)")
-#else
-#define FV3LM_RAS_LITERAL
-#endif
 
 namespace fv3 {
 
@@ -51,95 +44,6 @@ enum { G_PLE = 0, G_PKE, G_PF, G_PK, G_PRJ, G_PRS, G_PRH, G_PKI, G_DPT, G_DPB, G
 enum { S_THO = 0, S_QHO, S_UHO, S_VHO, S_PLE, S_PKZ, S_OUT /* 6 */, S_JAC = S_OUT + 6 /* 2 */, RAS_NS = S_JAC + 2 };
 enum { SC_TS = 0, SC_FRLAND, SC_KCBL, SC_SEED, SC_DOCONVEC, RAS_NSC };
 
-// ---- the two scalars ---------------------------------------------------------------------------------------------------------------
-struct RD {
-  double v, d;
-  HD RD() : v(0.), d(0.) {}
-  HD RD(double v_) : v(v_), d(0.) {}
-  HD RD(double v_, double d_) : v(v_), d(d_) {}
-};
-HD RD operator+(RD a, RD b) { FV3LM_RAS_LITERAL return RD(a.v + b.v, a.d + b.d); }
-HD RD operator-(RD a, RD b) { FV3LM_RAS_LITERAL return RD(a.v - b.v, a.d - b.d); }
-HD RD operator*(RD a, RD b) { FV3LM_RAS_LITERAL return RD(a.v * b.v, a.d * b.v + a.v * b.d); }
-HD RD operator/(RD a, RD b) { FV3LM_RAS_LITERAL const double q = a.v / b.v; return RD(q, (a.d - q * b.d) / b.v); }
-HD RD operator-(RD a) { FV3LM_RAS_LITERAL return RD(-a.v, -a.d); }
-HD RD operator+(RD a, double b) { FV3LM_RAS_LITERAL return RD(a.v + b, a.d); }
-HD RD operator+(double a, RD b) { FV3LM_RAS_LITERAL return RD(a + b.v, b.d); }
-HD RD operator-(RD a, double b) { FV3LM_RAS_LITERAL return RD(a.v - b, a.d); }
-HD RD operator-(double a, RD b) { FV3LM_RAS_LITERAL return RD(a - b.v, -b.d); }
-HD RD operator*(RD a, double b) { FV3LM_RAS_LITERAL return RD(a.v * b, a.d * b); }
-HD RD operator*(double a, RD b) { FV3LM_RAS_LITERAL return RD(a * b.v, a * b.d); }
-HD RD operator/(RD a, double b) { FV3LM_RAS_LITERAL return RD(a.v / b, a.d / b); }
-HD RD operator/(double a, RD b) { FV3LM_RAS_LITERAL const double q = a / b.v; return RD(q, -q * b.d / b.v); }
-
-// taped value (value, scale, id): its derivative with respect to tape variable id is scale (as TV of coltape.h)
-struct RV {
-  double v, s; int id; Tape* t;
-  HD RV() : v(0.), s(1.), id(-1), t(nullptr) {}
-  HD RV(double v_) : v(v_), s(1.), id(-1), t(nullptr) {}
-  HD RV(double v_, double s_, int id_, Tape* t_) : v(v_), s(s_), id(id_), t(t_) {}
-};
-HD RV rv2(const RV& a, const RV& b, double v, double pa, double pb) { FV3LM_RAS_LITERAL
-  if (a.id >= 0 && b.id >= 0) return RV(v, 1., a.t->push(a.id, b.id, pa * a.s, pb * b.s), a.t);
-  if (a.id >= 0) return RV(v, pa * a.s, a.id, a.t);
-  if (b.id >= 0) return RV(v, pb * b.s, b.id, b.t);
-  return RV(v);
-}
-HD RV rv1n(const RV& a, double v, double pa) { FV3LM_RAS_LITERAL return a.id < 0 ? RV(v) : RV(v, 1., a.t->push(a.id, -1, pa * a.s, 0.), a.t); }
-HD RV rv1l(const RV& a, double v, double pa) { FV3LM_RAS_LITERAL return a.id < 0 ? RV(v) : RV(v, pa * a.s, a.id, a.t); }
-HD RV operator+(const RV& a, const RV& b) { FV3LM_RAS_LITERAL return rv2(a, b, a.v + b.v, 1., 1.); }
-HD RV operator-(const RV& a, const RV& b) { FV3LM_RAS_LITERAL return rv2(a, b, a.v - b.v, 1., -1.); }
-HD RV operator*(const RV& a, const RV& b) { FV3LM_RAS_LITERAL return rv2(a, b, a.v * b.v, b.v, a.v); }
-HD RV operator/(const RV& a, const RV& b) { FV3LM_RAS_LITERAL
-  const double q = a.v / b.v;
-  if (b.id < 0) return rv1l(a, q, 1. / b.v);
-  if (a.id < 0) return rv1n(b, q, -q / b.v);
-  return rv2(a, b, q, 1. / b.v, -q / b.v);
-}
-HD RV operator-(const RV& a) { FV3LM_RAS_LITERAL return rv1l(a, -a.v, -1.); }
-HD RV operator+(const RV& a, double b) { FV3LM_RAS_LITERAL return rv1l(a, a.v + b, 1.); }
-HD RV operator+(double a, const RV& b) { FV3LM_RAS_LITERAL return rv1l(b, a + b.v, 1.); }
-HD RV operator-(const RV& a, double b) { FV3LM_RAS_LITERAL return rv1l(a, a.v - b, 1.); }
-HD RV operator-(double a, const RV& b) { FV3LM_RAS_LITERAL return rv1l(b, a - b.v, -1.); }
-HD RV operator*(const RV& a, double b) { FV3LM_RAS_LITERAL return rv1l(a, a.v * b, b); }
-HD RV operator*(double a, const RV& b) { FV3LM_RAS_LITERAL return rv1l(b, a * b.v, a); }
-HD RV operator/(const RV& a, double b) { FV3LM_RAS_LITERAL return rv1l(a, a.v / b, 1. / b); }
-HD RV operator/(double a, const RV& b) { FV3LM_RAS_LITERAL const double q = a / b.v; return rv1n(b, q, -q / b.v); }
-
-HD double rval(double a) { FV3LM_RAS_LITERAL return a; }
-HD double rval(const RD& a) { FV3LM_RAS_LITERAL return a.v; }
-HD double rval(const RV& a) { FV3LM_RAS_LITERAL return a.v; }
-// a nonlinear function of one argument: its value and its derivative at the argument
-HD double run1(double, double v, double) { FV3LM_RAS_LITERAL return v; }
-HD RD run1(const RD& a, double v, double p) { FV3LM_RAS_LITERAL return RD(v, p * a.d); }
-HD RV run1(const RV& a, double v, double p) { FV3LM_RAS_LITERAL return rv1n(a, v, p); }
-
-template <class T> struct RW;
-template <> struct RW<double> {
-  static constexpr int W = 1;
-  HD static double get(const ColWs& w, int s, int k, Tape*) { FV3LM_RAS_LITERAL return w.at(s, k); }
-  HD static void set(const ColWs& w, int s, int k, double x) { FV3LM_RAS_LITERAL w.at(s, k) = x; }
-};
-template <> struct RW<RD> {
-  static constexpr int W = 2;
-  HD static RD get(const ColWs& w, int s, int k, Tape*) { FV3LM_RAS_LITERAL return RD(w.at(2 * s, k), w.at(2 * s + 1, k)); }
-  HD static void set(const ColWs& w, int s, int k, const RD& x) { FV3LM_RAS_LITERAL w.at(2 * s, k) = x.v; w.at(2 * s + 1, k) = x.d; }
-};
-template <> struct RW<RV> {
-  static constexpr int W = 2;
-  HD static RV get(const ColWs& w, int s, int k, Tape* t) { FV3LM_RAS_LITERAL return RV(w.at(2 * s, k), 1., (int)w.at(2 * s + 1, k), t); }
-  HD static void set(const ColWs& w, int s, int k, const RV& x) { FV3LM_RAS_LITERAL
-    const int id = (x.id < 0 || x.s == 1.) ? x.id : x.t->push(x.id, -1, x.s, 0.);
-    w.at(2 * s, k) = x.v; w.at(2 * s + 1, k) = (double)id;
-  }
-};
-// vector s of the work space, level 1 .. lm + 1
-template <class T> struct RArr {
-  ColWs w; int s; Tape* t;
-  HD T operator()(int k) const { FV3LM_RAS_LITERAL return RW<T>::get(w, s, k, t); }
-  HD void set(int k, const T& x) const { FV3LM_RAS_LITERAL RW<T>::set(w, s, k, x); }
-};
-
 // ---- one column ------------------------------------------------------------------------------------------------------------------------
 struct RasParams { double r[25]; };
 struct RasCol {
@@ -147,7 +51,7 @@ struct RasCol {
   ColWs g;                      // geometry vectors
   const double* tbl; const double* sige; const double* r;
   double dt, ts, frland, mxdiam, co_auto;
-  HD double G(int v, int l) const { FV3LM_RAS_LITERAL return g.at(v, l); }
+  HD double G(int v, int l) const { FV3LM_LITERAL return g.at(v, l); }
 };
 namespace rasc {
 constexpr double GRAV = blc::GRAV, ALHL = blc::ALHL, CP = blc::CP, RGAS = blc::RGAS, H2OMW = blc::H2OMW, AIRMW = blc::AIRMW, VIREPS = blc::VIREPS;
@@ -155,7 +59,7 @@ constexpr double ONEPKAP = 1. + 2. / 7., DAYLEN = 86400.0, RHMAX = 0.9999;
 }
 
 // everything of the routine that depends on the pressures and KCBL only (:185-187, :212-243, :253-256, :595-604)
-HD void ras_geom(const RasCol& c) { FV3LM_RAS_LITERAL
+HD void ras_geom(const RasCol& c) { FV3LM_LITERAL
   using namespace rasc;
   const int lm = c.lm, K = c.k;
   const ColWs& g = c.g;
@@ -183,7 +87,7 @@ HD void ras_geom(const RasCol& c) { FV3LM_RAS_LITERAL
 
 // DQSAT_RAS / DQSATs_RAS (:705-832) and their tangents (convection_tl.F90:1049-1180)
 template <class T>
-HD void ras_dqsat(T& dqsi, T& qssi, const T& temp, double plo, const double* tbl) { FV3LM_RAS_LITERAL
+HD void ras_dqsat(T& dqsi, T& qssi, const T& temp, double plo, const double* tbl) { FV3LM_LITERAL
   const double ESFAC = rasc::H2OMW / rasc::AIRMW;
   const double pp = plo * 100.0, tl = rval(temp);
   T ti = temp;
@@ -200,7 +104,7 @@ HD void ras_dqsat(T& dqsi, T& qssi, const T& temp, double plo, const double* tbl
 }
 // SUNDQ3_ICE (:670-703), F3 = 1
 template <class T>
-HD T ras_sundq3(const T& temp, double rate2, double rate3, double te1) { FV3LM_RAS_LITERAL
+HD T ras_sundq3(const T& temp, double rate2, double rate3, double te1) { FV3LM_LITERAL
   const double te0 = 273., te2 = 200., t = rval(temp);
   const double jump1 = (rate2 - 1.0) / pow(te0 - te1, 0.333);
   T f2;
@@ -211,7 +115,7 @@ HD T ras_sundq3(const T& temp, double rate2, double rate3, double te1) { FV3LM_R
   return f2;
 }
 // ACRITN (:640-668)
-HD double ras_acritn(double pl, double plb, double acritfac) { FV3LM_RAS_LITERAL
+HD double ras_acritn(double pl, double plb, double acritfac) { FV3LM_LITERAL
   const double PH[15] = {150.0, 200.0, 250.0, 300.0, 350.0, 400.0, 450.0, 500.0, 550.0, 600.0, 650.0, 700.0, 750.0, 800.0, 850.0};
   const double A[15] = {1.6851, 1.1686, 0.7663, 0.5255, 0.4100, 0.3677, 0.3151, 0.2216, 0.1521, 0.1082, 0.0750, 0.0664, 0.0553, 0.0445, 0.0633};
   const int iwk = (int)(pl * 0.02 - 0.999999999);
@@ -222,14 +126,9 @@ HD double ras_acritn(double pl, double plb, double acritfac) { FV3LM_RAS_LITERAL
   return acritfac * acr * (plb - pl);
 }
 
-template <class T> struct RasVecs {
-  ColWs w; Tape* t;
-  HD RArr<T> operator()(int s) const { FV3LM_RAS_LITERAL return RArr<T>{w, s, t}; }
-};
-
 // ---- pre (:185-300 without the dead parts)
 template <class T>
-HD void ras_pre(const RasCol& c, const RasVecs<T>& V) { FV3LM_RAS_LITERAL
+HD void ras_pre(const RasCol& c, const LitVecs<T>& V) { FV3LM_LITERAL
   using namespace rasc;
   const int lm = c.lm, K = c.k, icmin = c.icmin;
   const double LBCP = ALHL * (1.0 / CP);
@@ -282,7 +181,7 @@ HD void ras_pre(const RasCol& c, const RasVecs<T>& V) { FV3LM_RAS_LITERAL
 
 // ---- one cloud type (:316-579).  false: it left by a CYCLE before the update, the state is untouched
 template <class T>
-HD bool ras_cloud(const RasCol& c, const RasVecs<T>& V, int IC) { FV3LM_RAS_LITERAL
+HD bool ras_cloud(const RasCol& c, const LitVecs<T>& V, int IC) { FV3LM_LITERAL
   using namespace rasc;
   const int K = c.k;
   const double* r = c.r;
@@ -474,7 +373,7 @@ HD bool ras_cloud(const RasCol& c, const RasVecs<T>& V, int IC) { FV3LM_RAS_LITE
 
 // ---- post (:581-636).  any: a cloud type fired (SUM(RMF) > 0: every contribution to RMF is positive)
 template <class T>
-HD void ras_post(const RasCol& c, const RasVecs<T>& V, bool any) { FV3LM_RAS_LITERAL
+HD void ras_post(const RasCol& c, const LitVecs<T>& V, bool any) { FV3LM_LITERAL
   using namespace rasc;
   const int lm = c.lm, K = c.k, icmin = c.icmin;
   const double DDT = DAYLEN / c.dt;
@@ -501,7 +400,7 @@ HD void ras_post(const RasCol& c, const RasVecs<T>& V, bool any) { FV3LM_RAS_LIT
 
 // the whole routine in one scalar (values, tangent)
 template <class T>
-HD bool ras_column(const RasCol& c, const RasVecs<T>& V) { FV3LM_RAS_LITERAL
+HD bool ras_column(const RasCol& c, const LitVecs<T>& V) { FV3LM_LITERAL
   ras_pre<T>(c, V);
   bool any = false;
   for (int ic = c.k; ic >= c.icmin + 1; --ic) any = ras_cloud<T>(c, V, ic) || any;
@@ -510,25 +409,14 @@ HD bool ras_column(const RasCol& c, const RasVecs<T>& V) { FV3LM_RAS_LITERAL
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------------
-struct RasArgs {
-  Geom g; int ntile, lm, icmin, mst;
+struct RasArgs : ColView, ColWork {      // the slot's packed columns and the columns of this launch; the work spaces of the batch
+  int icmin, mst;
   Fld u, v, pt, delp, q1;
-  double* slot; size_t nc;          // packed columns: col = (tile ty + j) tx + i
-  const int* list; int first, n;    // the columns of this launch: list[first + m] (list null: first + m)
-  double *gw, *tw, *ew, *ck; TapeMem tape; int nb;      // work spaces of the batch, stride nb
   double* src;                      // four sources of the perturbation, host-compact [4][ntile][lm][ty][tx]
   const double* tbl; const double* sige; RasParams p;
   double dt, ptop, akap, p00k;
-  int* flag;
-  HD int kw() const { FV3LM_RAS_LITERAL return lm + 2 < 7 ? 7 : lm + 2; }
-  HD double& S(int v, int l, size_t col) const { FV3LM_RAS_LITERAL return slot[((size_t)v * (lm + 1) + l) * nc + col]; }
-  HD double& SC(int s, size_t col) const { FV3LM_RAS_LITERAL return slot[((size_t)RAS_NS * (lm + 1) + s) * nc + col]; }
-  HD size_t fld(size_t col, int l) const { FV3LM_RAS_LITERAL      // level l (0-based) of the column in a padded field
-    const size_t pc = (size_t)g.tx * g.ty, t = col / pc, r = col % pc;
-    return (t * lm + l) * g.plane + g.idx(g.i0 + (int)(r % g.tx), g.j0 + (int)(r / g.tx));
-  }
-  HD size_t cmp(size_t col, int l) const { FV3LM_RAS_LITERAL const size_t pc = (size_t)g.tx * g.ty; return ((col / pc) * lm + l) * pc + col % pc; }
-  HD RasCol column(int m, size_t col, int momentum) const { FV3LM_RAS_LITERAL
+  HD int kw() const { FV3LM_LITERAL return lm + 2 < 7 ? 7 : lm + 2; }
+  HD RasCol column(int m, size_t col, int momentum) const { FV3LM_LITERAL
     RasCol c; c.lm = lm; c.icmin = icmin; c.momentum = momentum; c.k = (int)SC(SC_KCBL, col);
     c.g = ColWs{gw + m, (size_t)nb, kw()}; c.tbl = tbl; c.sige = sige; c.r = p.r;
     c.dt = dt; c.ts = SC(SC_TS, col); c.frland = SC(SC_FRLAND, col); c.co_auto = 2.5e-3;
@@ -539,13 +427,12 @@ struct RasArgs {
     ras_geom(c);
     return c;
   }
-  HD size_t col_of(int m) const { FV3LM_RAS_LITERAL return list ? (size_t)list[first + m] : (size_t)(first + m); }
 };
 
 // set, part A: the trajectory the slot keeps (set_ltraj :700-743), every column
 struct RasGatherFn {
   RasArgs a;
-  HD void operator()(int m, int, int) const { FV3LM_RAS_LITERAL
+  HD void operator()(int m, int, int) const { FV3LM_LITERAL
     const size_t col = a.col_of(m); const int lm = a.lm;
     double pe0 = a.ptop;
     a.S(S_PLE, 0, col) = 0.01 * pe0;
@@ -574,13 +461,13 @@ struct RasGatherFn {
 // set, part B: RASE0 on copies, the heating-rate filter (:796-823), the Jacobian filter (:897-973; only its first column exists)
 struct RasSetFn {
   RasArgs a;
-  HD void operator()(int m, int, int) const { FV3LM_RAS_LITERAL
+  HD void operator()(int m, int, int) const { FV3LM_LITERAL
     const size_t col = a.col_of(m); const int lm = a.lm;
     const RasCol c = a.column(m, col, 0);
     const int K = c.k;
     const ColWs tw{a.tw + m, (size_t)a.nb, a.kw()};
     {
-      const RasVecs<double> V{tw, nullptr};
+      const LitVecs<double> V{tw, nullptr};
       for (int l = 1; l <= lm; ++l) { V(E_THO).set(l, a.S(S_THO, l - 1, col)); V(E_QHO).set(l, a.S(S_QHO, l - 1, col)); V(E_UHO).set(l, 0.); V(E_VHO).set(l, 0.); }
       ras_column<double>(c, V);
       const int src[6] = {E_THO, E_QHO, E_CLW, E_FLXD, E_PRC3, E_UPDF};
@@ -609,7 +496,7 @@ struct RasSetFn {
       }
     }
     if (doconvec) {
-      const RasVecs<RD> V{tw, nullptr};
+      const LitVecs<RD> V{tw, nullptr};
       for (int l = 1; l <= lm; ++l) {
         V(E_THO).set(l, RD(a.S(S_THO, l - 1, col), l == K ? 1. : 0.)); V(E_QHO).set(l, RD(a.S(S_QHO, l - 1, col), 0.));
         V(E_UHO).set(l, RD(0.)); V(E_VHO).set(l, RD(0.));
@@ -631,11 +518,11 @@ struct RasSetFn {
 template <class T>
 struct RasRunFn {
   RasArgs a;
-  HD void operator()(int m, int, int) const { FV3LM_RAS_LITERAL
+  HD void operator()(int m, int, int) const { FV3LM_LITERAL
     const size_t col = a.col_of(m); const int lm = a.lm;
     const RasCol c = a.column(m, col, 1);
     const ColWs tw{a.tw + m, (size_t)a.nb, a.kw()};
-    const RasVecs<T> V{tw, nullptr};
+    const LitVecs<T> V{tw, nullptr};
     const Fld* f[4] = {&a.pt, &a.q1, &a.u, &a.v};
     for (int l = 1; l <= lm; ++l) {
       const size_t n = a.fld(col, l - 1);
@@ -664,15 +551,15 @@ struct RasRunFn {
 // adjoint run: forward sweep in values with the checkpoints, then the segments last to first on the tape
 struct RasAdFn {
   RasArgs a;
-  HD void operator()(int m, int, int) const { FV3LM_RAS_LITERAL
+  HD void operator()(int m, int, int) const { FV3LM_LITERAL
     const size_t col = a.col_of(m); const int lm = a.lm, kw = a.kw();
     const RasCol c = a.column(m, col, 1);
     const int K = c.k, icmin = c.icmin;
     const ColWs tw{a.tw + m, (size_t)a.nb, kw}, ew{a.ew + m, (size_t)a.nb, kw}, ck{a.ck + m, (size_t)a.nb, kw};
     const ColWs eb{a.ew + (size_t)RAS_NT * kw * a.nb + m, (size_t)a.nb, kw};      // after the values' state and work vectors
     Tape tape; tape.m = a.tape; tape.col = (size_t)m; tape.n = 0;
-    const RasVecs<double> EV{ew, nullptr};
-    const RasVecs<RV> TV_{tw, &tape};
+    const LitVecs<double> EV{ew, nullptr};
+    const LitVecs<RV> TV_{tw, &tape};
     const Fld* f[4] = {&a.pt, &a.q1, &a.u, &a.v};
     const size_t n3c = (size_t)a.ntile * lm * a.g.tx * a.g.ty;
     // values and incoming adjoints
@@ -697,25 +584,10 @@ struct RasAdFn {
       // one segment on the tape: every element of E a leaf, run, move the incoming adjoints onto the results, walk back
       auto segment = [&](int which, int ic) {
         tape.n = 0;
-        for (int v = 0; v < RAS_NE; ++v) for (int l = 1; l <= lm; ++l)
-          RW<RV>::set(tw, v, l, RV(ew.at(v, l), 1., tape.push(-2 - (v * kw + l), -1, 0., 0.), &tape));
+        for (int v = 0; v < RAS_NE; ++v) for (int l = 1; l <= lm; ++l) lit_leaf(tape, tw, ew, kw, v, l);
         if (which == 0) ras_pre<RV>(c, TV_); else if (which == 1) ras_cloud<RV>(c, TV_, ic); else ras_post<RV>(c, TV_, true);
-        for (int v = 0; v < RAS_NE; ++v) for (int l = 1; l <= lm; ++l) {
-          const double gb = eb.at(v, l);
-          eb.at(v, l) = 0.;
-          const int id = (int)tw.at(2 * v + 1, l);
-          if (id >= 0 && gb != 0.) tape.ad(id) += gb;
-        }
-        for (int id = tape.n - 1; id >= 0; --id) {
-          const size_t e = (size_t)id * tape.m.stride + tape.col;
-          const double ad = tape.m.adj[e];
-          if (ad == 0.) continue;
-          const TapeIdx ix = tape.m.idx[e];
-          if (ix.a <= -2) { const int q = -2 - ix.a; eb.at(q / kw, q % kw) += ad; continue; }
-          const TapePart pt = tape.m.part[e];
-          if (ix.a >= 0) tape.ad(ix.a) += pt.a * ad;
-          if (ix.b >= 0) tape.ad(ix.b) += pt.b * ad;
-        }
+        for (int v = 0; v < RAS_NE; ++v) for (int l = 1; l <= lm; ++l) lit_seed(tape, tw, eb, v, l);
+        lit_walk_back(tape, eb, kw);
       };
       segment(2, 0);
       for (int s = nfired - 1; s >= 0; --s) {

@@ -6,10 +6,6 @@
 #include "dycore.h"
 #include "remap.h"
 #include "rayleigh.h"
-#include "turbulence.h"
-#include "bldriver.h"
-#include "convection.h"
-#include "cloud.h"
 
 namespace fv3 {
 
@@ -152,56 +148,6 @@ struct Dynamics : Dycore {
   bool set_rayleigh(double tau, double rf_cutoff, const double* c2l);
   RfArgs rf_args();
   void rayleigh(int mode);
-  // Linearised boundary-layer turbulence (turbulence.h; fv3lm_turbulence_*): nothing allocated until turb_create
-  struct Turbulence {
-    int nslots = 0; std::vector<double*> slot; std::vector<char> set; double* fro = nullptr; int* flag = nullptr;
-    double *bl_sfc = nullptr, *bl_tbl = nullptr, *bl_raw = nullptr;      // BL_DRIVER (bldriver.h): surface planes and table at its first call, EKV FKV at the first raw_out
-  } turb;
-  bool turb_create(int nslots);
-  bool turb_slot_ok(const char* who, int slot);
-  TurbArgs turb_args(int slot);
-  bool turb_factorise(const char* who, int slot);
-  bool turb_set_diagonals(int slot, const double* const* diag);
-  bool turb_set_simple(int slot, const double* frocean);
-  bool turb_set_driver(int slot, const BlParams* p, double dt, const double* const* sfc, const double* qa, const double* qb, int cloud_mode, double* const* raw_out);
-  bool turb_run(int slot, int mode);
-  bool turb_get(int slot, double* const* out);
-  void turb_destroy();
-  // Linearised RAS convection (convection.h; fv3lm_convection_*): nothing allocated until conv_create
-  struct Convection {
-    int nslots = 0, mst = 0, icmin = 0, nb = 0; RasParams p;
-    double* slot_block = nullptr; int* list_block = nullptr;
-    std::vector<double*> slot; std::vector<char> set; std::vector<int*> list; std::vector<int> nactive;
-    double *gw = nullptr, *tw = nullptr, *ew = nullptr, *ck = nullptr, *src = nullptr, *tbl = nullptr, *sige = nullptr; int* flag = nullptr;
-    TapeMem tape;
-  } conv;
-  size_t conv_ncol() const { return (size_t)ntile_all * g.tx * g.ty; }
-  size_t conv_slot_doubles() const { return ((size_t)RAS_NS * (g.npz + 1) + RAS_NSC) * conv_ncol(); }
-  bool conv_create(int nslots, const RasParams* p, int do_phy_mst);
-  bool conv_slot_ok(const char* who, int slot, bool need_set);
-  RasArgs conv_args(int slot);
-  bool conv_set(int slot, const double* ts, const double* frland, const double* kcbl);
-  bool conv_get(int slot, double* const* out6, int* doconvec, double* jac2);
-  bool conv_sources(int put, double* const* src4);
-  bool conv_table(double* table, double* constants);
-  bool conv_run(int slot, int mode);
-  void conv_destroy();
-  // Linearised cloud scheme (cloud.h; fv3lm_cloud_*): nothing allocated until cloud_create; one slot per convection slot
-  struct Cloud {
-    int created = 0, iqi = 0, iql = 0, nb = 0; CldParams p;
-    double* slot_block = nullptr; std::vector<double*> slot; std::vector<char> set;
-    double *gw = nullptr, *tw = nullptr, *ew = nullptr, *ck = nullptr, *cfcn = nullptr; int* flag = nullptr;
-    TapeMem tape;
-  } cld;
-  size_t cloud_slot_doubles() const { return ((size_t)CLD_NS * (g.npz + 1) + CLD_NSC) * conv_ncol(); }
-  bool cloud_create(const CldParams* p, int iqi, int iql);
-  bool cloud_slot_ok(const char* who, int slot, bool need_set);
-  CldArgs cloud_args(int slot);
-  bool cloud_set(int slot, const double* qls, const double* qcn, const double* cfcn, const double* khl, const double* khu);
-  bool cloud_get(int slot, double* const* out8, double* const* frac4, int* pertmod);
-  bool cloud_cfcn(int put, double* cfcn);
-  bool cloud_run(int slot, int mode);
-  void cloud_destroy();
   // one field between the host's compact array and the device state.  which: 0 trajectory, 1 perturbation / adjoint
   void compact_in(const Fld& f, int which, const double* host) {
     const size_t n = (size_t)ntile_all * f.nk * g.tx * g.ty;
@@ -336,9 +282,6 @@ inline bool Dynamics::init2(const double* ak, const double* bk) {
 }
 inline void Dynamics::destroy2() {
   dev_free(stage_dev); stage_dev = nullptr;
-  turb_destroy();
-  cloud_destroy();
-  conv_destroy();
   dev_free(rf_lv); dev_free(rf_c2l); dev_free(rf_ck); dev_free(rf_pth.t); dev_free(rf_pth.p);
   dev_free(ak_dev); dev_free(bk_dev); if (remap_ws_own) dev_free(remap_ws); dev_free(cmax_dev);
   tshared.destroy(); twork.destroy();
@@ -692,466 +635,6 @@ inline void Dynamics::rayleigh(int mode) {
     for_points(ex, E, nz, RfHeatFn{a, mode}, mode == MODE_NL ? "rayleigh_heat.nl" : "rayleigh_heat.tl");
     for_points(ex, E, nz, RfDampFn{a, mode}, mode == MODE_NL ? "rayleigh_damp.nl" : "rayleigh_damp.tl");
   });
-}
-
-// ---- linearised boundary-layer turbulence (turbulence.h) -------------------------------------------------------------------------------
-// fv3lm_turbulence_create: nslots x (9 factor arrays + pk), padded planes
-inline bool Dynamics::turb_create(int nslots) {
-  if (turb.nslots > 0) { err = "fv3lm_turbulence_create: already created for this handle"; return false; }
-  if (nslots < 1) { err = "fv3lm_turbulence_create: nslots < 1"; return false; }
-  if (g.npz < 2) { err = "fv3lm_turbulence_create: npz < 2 (a tridiagonal system needs two levels)"; return false; }
-  const size_t bytes = (size_t)TURB_NARR * n3 * 8;
-  if (std::getenv("FV3LM_VERBOSE")) std::fprintf(stderr, "fv3lm: turbulence arena %d slot(s) x %d arrays x %zu doubles = %zu bytes\n", nslots, TURB_NARR, n3, (size_t)nslots * bytes);
-  const bool clean = sticky_error().empty();
-  for (int n = 0; n < nslots; ++n) turb.slot.push_back((double*)dev_alloc(bytes));
-  turb.fro = (double*)dev_alloc((size_t)ntile_all * g.plane * 8); turb.flag = (int*)dev_alloc(8);
-  bool ok = turb.fro && turb.flag;
-  for (double* p : turb.slot) ok = ok && p;
-  if (!ok) {      // a refusal: what was allocated goes back, the handle stays usable
-    err = "fv3lm_turbulence_create: allocation of " + std::to_string((size_t)nslots * bytes) + " bytes failed" + (sticky_error().empty() ? std::string() : ": " + sticky_error());
-    if (clean) sticky_error().clear();
-    turb_destroy();
-    return false;
-  }
-  turb.set.assign((size_t)nslots, 0); turb.nslots = nslots;
-  return true;
-}
-inline void Dynamics::turb_destroy() {
-  for (double* p : turb.slot) dev_free(p);
-  dev_free(turb.fro); dev_free(turb.flag); dev_free(turb.bl_sfc); dev_free(turb.bl_tbl); dev_free(turb.bl_raw);
-  turb = Turbulence{};
-}
-inline bool Dynamics::turb_slot_ok(const char* who, int slot) {
-  if (turb.nslots == 0) { err = std::string(who) + ": call fv3lm_turbulence_create first"; return false; }
-  if (slot < 0 || slot >= turb.nslots) { err = std::string(who) + ": slot " + std::to_string(slot) + " out of range (0.." + std::to_string(turb.nslots - 1) + ")"; return false; }
-  return true;
-}
-inline TurbArgs Dynamics::turb_args(int slot) {      // inside each_class
-  TurbArgs a; a.g = g;
-  a.u = ex.sh(f("u")); a.v = ex.sh(f("v")); a.pt = ex.sh(f("pt")); a.delp = ex.sh(f("delp"));
-  a.nq = nq;
-  for (int n = 0; n < nq; ++n) a.q[n] = ex.sh(q[(size_t)n]);
-  a.fac = turb.slot[(size_t)slot] + ex.cls_off * g.npz; a.fs = n3;
-  a.fro = turb.fro + ex.cls_off; a.flag = turb.flag;
-  a.ptop = opt.ptop; a.akap = opt.akap; a.p00k = std::pow(1.0e5, opt.akap);
-  a.dt = bdt; a.grav = opt.grav_jedi; a.cp = opt.cp; a.zvir = opt.zvir;
-  return a;
-}
-// VTRILUPERT of the slot's three systems and pk from the resident trajectory delp; a bad pivot is reported here, by one flag
-inline bool Dynamics::turb_factorise(const char* who, int slot) {
-  dev_zero(ex, turb.flag, 8);
-  each_class([&]() { run_turb_factorise(ex, turb_args(slot)); });
-  int flag = 0;
-  d2h(ex, &flag, turb.flag, sizeof flag);
-  turb.set[(size_t)slot] = flag ? 0 : 1;
-  if (flag) { err = std::string(who) + ": the factorisation of a main diagonal gave a zero or non-finite pivot (slot " + std::to_string(slot) + " is not set)"; return false; }
-  return true;
-}
-inline bool Dynamics::turb_set_diagonals(int slot, const double* const* diag) {
-  if (!turb_slot_ok("fv3lm_turbulence_set_diagonals", slot)) return false;
-  if (!diag) { err = "fv3lm_turbulence_set_diagonals: null array"; return false; }
-  for (int n = 0; n < 9; ++n) if (!diag[n]) { err = "fv3lm_turbulence_set_diagonals: null array"; return false; }      // before anything is touched
-  turb.set[(size_t)slot] = 0;
-  for (int n = 0; n < 9; ++n) { Fld d; d.t = turb.slot[(size_t)slot] + (size_t)n * n3; d.nk = g.npz; compact_in(d, 0, diag[n]); }
-  return turb_factorise("fv3lm_turbulence_set_diagonals", slot);
-}
-inline bool Dynamics::turb_set_simple(int slot, const double* frocean) {
-  if (!turb_slot_ok("fv3lm_turbulence_set_simple", slot)) return false;
-  if (nq < 3) { err = "fv3lm_turbulence_set_simple: nq < 3 (BL_simp reads qv, ql, qi = q1, q2, q3)"; return false; }
-  if (!frocean) { err = "fv3lm_turbulence_set_simple: null array"; return false; }
-  turb.set[(size_t)slot] = 0;
-  { Fld d; d.t = turb.fro; d.nk = 1; compact_in(d, 0, frocean); }
-  each_class([&]() { run_turb_simple(ex, turb_args(slot)); });
-  return turb_factorise("fv3lm_turbulence_set_simple", slot);
-}
-// BL_DRIVER on the resident trajectory (bldriver.h): the column's work vectors go through the slot's own planes, the nine diagonals
-// replace them, then the factorisation as after set_diagonals.  Every refusal stands before anything of the slot is touched, except
-// the parcel that never stops, which only the kernel can see: the slot is then left unset like after a zero pivot.
-inline bool Dynamics::turb_set_driver(int slot, const BlParams* p, double dt, const double* const* sfc, const double* qa, const double* qb, int cloud_mode,
-                                      double* const* raw_out) {
-  const char* who = "fv3lm_turbulence_set_driver";
-  auto no = [&](const std::string& m) { err = std::string(who) + ": " + m; return false; };
-  if (!turb_slot_ok(who, slot)) return false;
-  if (g.npz < 7) return no("npz < 7 (BL_DRIVER smooths the bottom six levels against the seventh)");
-  if (nq < 1) return no("nq < 1 (BL_DRIVER reads qv = q1)");
-  if (!p) return no("null parameters");
-  if (p->i[0] < 1 || p->i[0] > g.npz) return no("KPBLMIN = " + std::to_string(p->i[0]) + " outside 1.." + std::to_string(g.npz));
-  if (p->i[3] != 0) return no("RADLW_DEP != 0 (the reference reads an uninitialised RADLW there)");
-  if (turb_stored_nonfinite(&dt) || dt <= 0.) return no("dt <= 0 or not finite");
-  if (cloud_mode < 0 || cloud_mode > 1) return no("cloud_mode outside 0..1");
-  if (!sfc) return no("null array");
-  for (int n = 0; n < BL_NSFC; ++n) if (!sfc[n]) return no("null array");
-  if (raw_out) for (int n = 0; n < 13; ++n) if (!raw_out[n]) return no("null array in raw_out");
-  const size_t ss = (size_t)ntile_all * g.plane;
-  const bool clean = sticky_error().empty();
-  if (!turb.bl_tbl) {
-    turb.bl_tbl = (double*)dev_alloc((size_t)blc::TABLESIZE * 8);
-    if (turb.bl_tbl) { const std::vector<double> x = bl_esinit(); h2d(ex, turb.bl_tbl, x.data(), x.size() * 8); }
-  }
-  if (!turb.bl_sfc) turb.bl_sfc = (double*)dev_alloc(BL_NSFC * ss * 8);
-  if (raw_out && !turb.bl_raw) turb.bl_raw = (double*)dev_alloc(2 * n3 * 8);
-  if (!turb.bl_tbl || !turb.bl_sfc || (raw_out && !turb.bl_raw)) {
-    if (clean) sticky_error().clear();
-    return no("allocation failed");
-  }
-  turb.set[(size_t)slot] = 0;
-  double* S = turb.slot[(size_t)slot];
-  for (int n = 0; n < BL_NSFC; ++n) { Fld d; d.t = turb.bl_sfc + (size_t)n * ss; d.nk = 1; compact_in(d, 0, sfc[n]); }
-  const double* cl[2] = {qa, qb};
-  for (int n = 0; n < 2; ++n) {
-    double* dst = S + (size_t)(BLP_QI + n) * n3;
-    if (cl[n]) { Fld d; d.t = dst; d.nk = g.npz; compact_in(d, 0, cl[n]); } else dev_zero(ex, dst, n3 * 8);
-  }
-  dev_zero(ex, turb.flag, 8);
-  each_class([&]() {
-    BlArgs a; a.t = turb_args(slot); a.p = *p; a.dt = dt; a.tbl = turb.bl_tbl; a.sfc = turb.bl_sfc + ex.cls_off; a.ss = ss;
-    a.ekv = raw_out ? turb.bl_raw + ex.cls_off * g.npz : nullptr; a.fkv = raw_out ? a.ekv + n3 : nullptr;
-    a.cloud_mode = cloud_mode; a.flag = turb.flag + 1;
-    run_bl_driver(ex, a);
-  });
-  int flag[2] = {0, 0};
-  d2h(ex, flag, turb.flag, sizeof flag);
-  if (flag[1]) return no("a column's surface parcel never reaches its level of neutral buoyancy (mpbl_depth leaves ipbl unset; slot " + std::to_string(slot) + " is not set)");
-  if (raw_out) {
-    for (int n = 0; n < 11; ++n) { Fld d; d.t = n < 9 ? S + (size_t)n * n3 : turb.bl_raw + (size_t)(n - 9) * n3; d.nk = g.npz; compact_out(d, 0, raw_out[n]); }
-    { Fld d; d.t = turb.bl_sfc + (size_t)BL_ZPBL * ss; d.nk = 1; compact_out(d, 0, raw_out[11]); }
-    { Fld d; d.t = turb.bl_sfc + (size_t)BL_CT * ss; d.nk = 1; compact_out(d, 0, raw_out[12]); }
-  }
-  return turb_factorise(who, slot);
-}
-inline bool Dynamics::turb_run(int slot, int mode) {
-  if (!turb_slot_ok("fv3lm_turbulence", slot)) return false;
-  if (mode < 0 || mode > 2) { err = "fv3lm_turbulence: bad mode"; return false; }
-  if (!turb.set[(size_t)slot]) { err = "fv3lm_turbulence: slot " + std::to_string(slot) + " was never set (fv3lm_turbulence_set_diagonals / _set_simple)"; return false; }
-  each_class([&]() { run_turb_solve(ex, mode, turb_args(slot)); });
-  return true;
-}
-inline bool Dynamics::turb_get(int slot, double* const* out) {
-  if (!turb_slot_ok("fv3lm_turbulence_get", slot)) return false;
-  if (!turb.set[(size_t)slot]) { err = "fv3lm_turbulence_get: slot " + std::to_string(slot) + " was never set"; return false; }
-  if (!out) { err = "fv3lm_turbulence_get: null array"; return false; }
-  for (int n = 0; n < TURB_NARR; ++n) if (!out[n]) { err = "fv3lm_turbulence_get: null array"; return false; }
-  for (int n = 0; n < TURB_NARR; ++n) { Fld d; d.t = turb.slot[(size_t)slot] + (size_t)n * n3; d.nk = g.npz; compact_out(d, 0, out[n]); }
-  return true;
-}
-
-// ---- linearised RAS convection (convection.h) --------------------------------------------------------------------------------------------
-// fv3lm_convection_create: the slots (what set saw of the trajectory, packed columns), the table, SIGE, the four sources of the
-// perturbation and the work spaces, checkpoints and tape of one batch of columns.  All device memory of the feature is allocated here.
-inline bool Dynamics::conv_create(int nslots, const RasParams* p, int do_phy_mst) {
-  const char* who = "fv3lm_convection_create";
-  auto no = [&](const std::string& m) { err = std::string(who) + ": " + m; return false; };
-  if (conv.nslots > 0) return no("already created for this handle");
-  if (nslots < 1) return no("nslots < 1");
-  if (!p) return no("null parameters");
-  if (do_phy_mst < 1 || do_phy_mst > 2) return no("do_phy_mst outside 1..2");
-  if (ak_host.empty()) return no("the handle has no ak, bk (PREF = ak + bk p00 gives ICMIN and SIGE)");
-  if (nq < 1) return no("nq < 1 (convection reads and writes qv = q1)");
-  for (int n = 0; n < 25; ++n) if (turb_stored_nonfinite(&p->r[n])) return no("a value that is not finite in the parameters");
-  const int lm = g.npz; const size_t nc = conv_ncol();
-  std::vector<double> sige((size_t)lm + 1);
-  int cnt = 0;
-  for (int l = 0; l <= lm; ++l) { sige[(size_t)l] = ak_host[(size_t)l] + bk_host[(size_t)l] * 100000.0; if (sige[(size_t)l] < 3000.0) ++cnt; }
-  const double pb = sige[(size_t)lm];
-  for (double& x : sige) x = x / pb;
-  Convection& c = conv;
-  c.nb = (int)(nc < (size_t)RAS_BATCH ? nc : (size_t)RAS_BATCH);
-  const size_t kw = (size_t)(lm + 2 < 7 ? 7 : lm + 2), nb = (size_t)c.nb;
-  const size_t b_slot = conv_slot_doubles() * 8, b_gw = RAS_NG * kw * nb * 8, b_tw = 2 * (size_t)RAS_NT * kw * nb * 8, b_ew = ((size_t)RAS_NT + RAS_NE) * kw * nb * 8,
-               b_ck = (5 * (size_t)lm + 1) * kw * nb * 8, b_src = 4 * nc * lm * 8;
-  const int cap = RAS_TAPE_PER_LEVEL * (int)kw;
-  const size_t b_tape = (size_t)cap * nb * (sizeof(TapePart) + sizeof(TapeIdx) + 8);
-  const size_t total = (size_t)nslots * (b_slot + nc * 4) + b_gw + b_tw + b_ew + b_ck + b_src + b_tape + (size_t)blc::TABLESIZE * 8 + sige.size() * 8 + 8;
-  if (std::getenv("FV3LM_VERBOSE"))
-    std::fprintf(stderr, "fv3lm: convection arena %zu bytes: %d slot(s) x %zu, batch of %d columns: work %zu, checkpoints %zu, tape %zu (%d entries a column); sources %zu\n",
-                 total, nslots, b_slot + nc * 4, c.nb, b_gw + b_tw + b_ew, b_ck, b_tape, cap, b_src);
-  const bool clean = sticky_error().empty();
-  bool ok = true;
-  // the slots and their lists are one block each, so that a request that cannot fit fails in one allocation
-  const bool fits = (size_t)nslots <= ((size_t)1 << 62) / (b_slot + nc * 4);
-  double* sb = fits ? (double*)dev_alloc((size_t)nslots * b_slot) : nullptr; int* lb = fits ? (int*)dev_alloc((size_t)nslots * nc * 4) : nullptr;
-  ok = sb && lb;
-  c.slot_block = sb; c.list_block = lb;
-  if (ok) for (int n = 0; n < nslots; ++n) { c.slot.push_back(sb + (size_t)n * (b_slot / 8)); c.list.push_back(lb + (size_t)n * nc); }
-  c.gw = (double*)dev_alloc(b_gw); c.tw = (double*)dev_alloc(b_tw); c.ew = (double*)dev_alloc(b_ew); c.ck = (double*)dev_alloc(b_ck); c.src = (double*)dev_alloc(b_src);
-  c.tbl = (double*)dev_alloc((size_t)blc::TABLESIZE * 8); c.sige = (double*)dev_alloc(sige.size() * 8); c.flag = (int*)dev_alloc(8);
-  c.tape.part = (TapePart*)dev_alloc((size_t)cap * nb * sizeof(TapePart)); c.tape.idx = (TapeIdx*)dev_alloc((size_t)cap * nb * sizeof(TapeIdx));
-  c.tape.adj = (double*)dev_alloc((size_t)cap * nb * 8); c.tape.overflow = c.flag ? c.flag + 1 : nullptr; c.tape.stride = nb; c.tape.cap = cap;
-  ok = ok && c.gw && c.tw && c.ew && c.ck && c.src && c.tbl && c.sige && c.flag && c.tape.part && c.tape.idx && c.tape.adj;
-  if (!ok) {
-    err = std::string(who) + ": allocation of " + std::to_string(total) + " bytes failed" + (sticky_error().empty() ? std::string() : ": " + sticky_error());
-    if (clean) sticky_error().clear();
-    conv_destroy();
-    return false;
-  }
-  { const std::vector<double> x = bl_esinit(); h2d(ex, c.tbl, x.data(), x.size() * 8); }
-  h2d(ex, c.sige, sige.data(), sige.size() * 8);
-  c.p = *p; c.mst = do_phy_mst; c.icmin = cnt > 1 ? cnt : 1;
-  c.set.assign((size_t)nslots, 0); c.nactive.assign((size_t)nslots, 0); c.nslots = nslots;
-  return true;
-}
-inline void Dynamics::conv_destroy() {
-  dev_free(conv.slot_block); dev_free(conv.list_block);
-  dev_free(conv.gw); dev_free(conv.tw); dev_free(conv.ew); dev_free(conv.ck); dev_free(conv.src); dev_free(conv.tbl); dev_free(conv.sige); dev_free(conv.flag);
-  dev_free(conv.tape.part); dev_free(conv.tape.idx); dev_free(conv.tape.adj);
-  conv = Convection{};
-}
-inline bool Dynamics::conv_slot_ok(const char* who, int slot, bool need_set) {
-  if (conv.nslots == 0) { err = std::string(who) + ": call fv3lm_convection_create first"; return false; }
-  if (slot < 0 || slot >= conv.nslots) { err = std::string(who) + ": slot " + std::to_string(slot) + " out of range (0.." + std::to_string(conv.nslots - 1) + ")"; return false; }
-  if (need_set && !conv.set[(size_t)slot]) { err = std::string(who) + ": slot " + std::to_string(slot) + " was never set (fv3lm_convection_set)"; return false; }
-  return true;
-}
-inline RasArgs Dynamics::conv_args(int slot) {      // all resident tiles at once: a column does not know where it lies
-  RasArgs a; a.g = g; a.ntile = ntile_all; a.lm = g.npz; a.icmin = conv.icmin; a.mst = conv.mst;
-  a.u = ex.sh(f("u")); a.v = ex.sh(f("v")); a.pt = ex.sh(f("pt")); a.delp = ex.sh(f("delp")); a.q1 = ex.sh(q[0]);
-  a.slot = conv.slot[(size_t)slot]; a.nc = conv_ncol(); a.list = nullptr; a.first = 0; a.n = 0;
-  a.gw = conv.gw; a.tw = conv.tw; a.ew = conv.ew; a.ck = conv.ck; a.tape = conv.tape; a.nb = conv.nb; a.src = conv.src;
-  a.tbl = conv.tbl; a.sige = conv.sige; a.p = conv.p;
-  a.dt = bdt; a.ptop = opt.ptop; a.akap = opt.akap; a.p00k = std::pow(1.0e5, opt.akap);
-  a.flag = conv.flag;
-  return a;
-}
-// the slot takes the trajectory from the resident u v pt(= T) delp q1 at this call; RASE0, the two filters and the list of DOCONVEC columns
-inline bool Dynamics::conv_set(int slot, const double* ts, const double* frland, const double* kcbl) {
-  const char* who = "fv3lm_convection_set";
-  auto no = [&](const std::string& m) { err = std::string(who) + ": " + m; return false; };
-  if (!conv_slot_ok(who, slot, false)) return false;
-  if (!ts || !frland || !kcbl) return no("null array");
-  const size_t nc = conv_ncol(); const int lm = g.npz;
-  for (size_t n = 0; n < nc; ++n) {
-    if (turb_stored_nonfinite(ts + n) || turb_stored_nonfinite(frland + n) || turb_stored_nonfinite(kcbl + n)) return no("a value that is not finite in ts, frland or kcbl");
-    const long k = std::lround(kcbl[n]);
-    if (k < conv.icmin + 1 || k > lm) return no("kcbl = " + std::to_string(k) + " outside ICMIN+1 .. npz = " + std::to_string(conv.icmin + 1) + " .. " + std::to_string(lm));
-  }
-  conv.set[(size_t)slot] = 0;
-  if (cld.created) cld.set[(size_t)slot] = 0;      // the cloud slot reads this one: it has to be set again after it
-  std::vector<double> kc(nc);
-  for (size_t n = 0; n < nc; ++n) kc[n] = (double)std::lround(kcbl[n]);      // nint
-  RasArgs a = conv_args(slot);
-  h2d(ex, &a.SC(SC_TS, 0), ts, nc * 8); h2d(ex, &a.SC(SC_FRLAND, 0), frland, nc * 8); h2d(ex, &a.SC(SC_KCBL, 0), kc.data(), nc * 8);
-  dev_zero(ex, conv.flag, 8);
-  a.first = 0; a.n = (int)nc;
-  run_ras(ex, -2, a);
-  int flag[2] = {0, 0};
-  d2h(ex, flag, conv.flag, sizeof flag);
-  if (flag[0]) return no("a value that is not finite in the resident trajectory (slot " + std::to_string(slot) + " is not set)");
-  for (size_t first = 0; first < nc; first += (size_t)conv.nb) { a.first = (int)first; a.n = (int)(nc - first < (size_t)conv.nb ? nc - first : (size_t)conv.nb); run_ras(ex, -1, a); }
-  std::vector<double> dc(nc);
-  d2h(ex, dc.data(), &a.SC(SC_DOCONVEC, 0), nc * 8);
-  std::vector<int> list;
-  for (size_t n = 0; n < nc; ++n) if (dc[n] == 1.0) list.push_back((int)n);
-  if (!list.empty()) h2d(ex, conv.list[(size_t)slot], list.data(), list.size() * 4);
-  conv.nactive[(size_t)slot] = (int)list.size();
-  if (!sticky_error().empty()) { err = sticky_error(); return false; }
-  conv.set[(size_t)slot] = 1;
-  return true;
-}
-inline bool Dynamics::conv_get(int slot, double* const* out6, int* doconvec, double* jac2) {
-  const char* who = "fv3lm_convection_get";
-  if (!conv_slot_ok(who, slot, true)) return false;
-  if (!out6 || !doconvec) { err = std::string(who) + ": null array"; return false; }
-  for (int n = 0; n < 6; ++n) if (!out6[n]) { err = std::string(who) + ": null array"; return false; }
-  const size_t nc = conv_ncol(), pc = (size_t)g.tx * g.ty; const int lm = g.npz;
-  const RasArgs a = conv_args(slot);
-  std::vector<double> buf((size_t)(lm + 1) * nc);
-  auto unpack = [&](int v, double* dst) {      // [level][column] -> [tile][level][point]
-    d2h(ex, buf.data(), &a.S(v, 0, 0), buf.size() * 8);
-    for (size_t col = 0; col < nc; ++col) for (int l = 0; l < lm; ++l) dst[((col / pc) * lm + l) * pc + col % pc] = buf[(size_t)l * nc + col];
-  };
-  for (int n = 0; n < 6; ++n) unpack(S_OUT + n, out6[n]);
-  if (jac2) { unpack(S_JAC, jac2); unpack(S_JAC + 1, jac2 + (size_t)lm * nc); }
-  d2h(ex, buf.data(), &a.SC(SC_DOCONVEC, 0), nc * 8);
-  for (size_t n = 0; n < nc; ++n) doconvec[n] = (int)buf[n];
-  return true;
-}
-inline bool Dynamics::conv_sources(int put, double* const* src4) {
-  const char* who = "fv3lm_convection_sources";
-  if (conv.nslots == 0) { err = std::string(who) + ": call fv3lm_convection_create first"; return false; }
-  if (!src4) { err = std::string(who) + ": null array"; return false; }
-  for (int n = 0; n < 4; ++n) if (!src4[n]) { err = std::string(who) + ": null array"; return false; }
-  const size_t n3c = conv_ncol() * g.npz;
-  if (put) for (size_t n = 0; n < 4 * n3c; ++n) if (turb_stored_nonfinite(src4[n / n3c] + n % n3c)) { err = std::string(who) + ": a value that is not finite"; return false; }
-  for (int n = 0; n < 4; ++n) { if (put) h2d(ex, conv.src + (size_t)n * n3c, src4[n], n3c * 8); else d2h(ex, src4[n], conv.src + (size_t)n * n3c, n3c * 8); }
-  return true;
-}
-// the table the kernels look up (ESINIT) as it lies on the device, and the nine constants they use, in the order of the fixture
-inline bool Dynamics::conv_table(double* table, double* constants) {
-  const char* who = "fv3lm_convection_table";
-  if (conv.nslots == 0) { err = std::string(who) + ": call fv3lm_convection_create first"; return false; }
-  if (!table || !constants) { err = std::string(who) + ": null array"; return false; }
-  d2h(ex, table, conv.tbl, (size_t)blc::TABLESIZE * 8);
-  const double c[9] = {rasc::CP, rasc::ALHL, rasc::GRAV, rasc::RGAS, rasc::H2OMW, rasc::AIRMW, rasc::VIREPS, blc::P00, blc::KAPPA};
-  for (int n = 0; n < 9; ++n) constants[n] = c[n];
-  return true;
-}
-// DOCONVEC columns only, in dense batches over the slot's list.  Tangent: the sources are cleared, then written in the active columns;
-// adjoint: the sources are the incoming adjoints, consumed and cleared.  The slot is read only.
-inline bool Dynamics::conv_run(int slot, int mode) {
-  const char* who = "fv3lm_convection";
-  if (!conv_slot_ok(who, slot, false)) return false;
-  if (mode < 0 || mode > 2) { err = std::string(who) + ": bad mode"; return false; }
-  if (!conv_slot_ok(who, slot, true)) return false;
-  RasArgs a = conv_args(slot);
-  a.list = conv.list[(size_t)slot];
-  const size_t n3c = conv_ncol() * g.npz;
-  const int na = conv.nactive[(size_t)slot];
-  if (mode == MODE_TL) dev_zero(ex, conv.src, 4 * n3c * 8);
-  if (mode == MODE_AD) dev_zero(ex, conv.flag, 8);
-  for (int first = 0; first < na; first += conv.nb) { a.first = first; a.n = na - first < conv.nb ? na - first : conv.nb; run_ras(ex, mode, a); }
-  if (mode == MODE_AD) {
-    dev_zero(ex, conv.src, 4 * n3c * 8);
-    int flag[2] = {0, 0};
-    d2h(ex, flag, conv.flag, sizeof flag);
-    if (flag[1]) { err = std::string(who) + ": the tape of a cloud type overflowed (RAS_TAPE_PER_LEVEL); the adjoint fields are not valid"; return false; }
-  }
-  if (!sticky_error().empty()) { err = sticky_error(); return false; }
-  return true;
-}
-
-// ---- linearised cloud scheme (cloud.h) -----------------------------------------------------------------------------------------------------
-// fv3lm_cloud_create: one slot per convection slot, the perturbation's convective cloud fraction and the work spaces, checkpoints and tape
-// of one batch of columns.  All device memory of the feature is allocated here.
-inline bool Dynamics::cloud_create(const CldParams* p, int iqi, int iql) {
-  const char* who = "fv3lm_cloud_create";
-  auto no = [&](const std::string& m) { err = std::string(who) + ": " + m; return false; };
-  if (conv.nslots == 0) return no("call fv3lm_convection_create first");
-  if (cld.created) return no("already created for this handle");
-  if (!p) return no("null parameters");
-  for (int n = 0; n < 57; ++n) if (turb_stored_nonfinite(&p->r[n])) return no("a value that is not finite in the parameters");
-  if ((int)p->r[56] != 1) return no("CLOUDPARAMS(57) = PDFFLAG /= 1 (only the top-hat PDF is built)");
-  if ((int)(p->r[34] + .001) < 1) return no("CLOUDPARAMS(35) = ICEFRPWR < 1");
-  if (iqi < 2 || iqi > nq || iql < 2 || iql > nq) return no("iqi = " + std::to_string(iqi) + ", iql = " + std::to_string(iql) + " outside 2..nq = 2.." + std::to_string(nq));
-  if (iqi == iql) return no("iqi = iql = " + std::to_string(iqi) + " (cloud ice and cloud liquid are two tracers)");
-  const int lm = g.npz, nslots = conv.nslots; const size_t nc = conv_ncol();
-  Cloud& c = cld;
-  c.nb = (int)(nc < (size_t)CLD_BATCH ? nc : (size_t)CLD_BATCH);
-  const size_t kw = (size_t)(lm + 2 < CLD_NSV + 2 ? CLD_NSV + 2 : lm + 2), nb = (size_t)c.nb;
-  const size_t b_slot = cloud_slot_doubles() * 8, b_gw = CLD_NG * kw * nb * 8, b_tw = 2 * (size_t)CLD_NE * kw * nb * 8, b_ew = 2 * (size_t)CLD_NE * kw * nb * 8,
-               b_ck = ((size_t)CLD_NCK + 1) * kw * nb * 8, b_cf = nc * lm * 8;
-  const int cap = CLD_TAPE;
-  const size_t b_tape = (size_t)cap * nb * (sizeof(TapePart) + sizeof(TapeIdx) + 8);
-  const size_t total = (size_t)nslots * b_slot + b_gw + b_tw + b_ew + b_ck + b_cf + b_tape + 8;
-  if (std::getenv("FV3LM_VERBOSE"))
-    std::fprintf(stderr, "fv3lm: cloud arena %zu bytes: %d slot(s) x %zu, batch of %d columns: work %zu, checkpoints %zu, tape %zu (%d entries a column); cfcn %zu\n",
-                 total, nslots, b_slot, c.nb, b_gw + b_tw + b_ew, b_ck, b_tape, cap, b_cf);
-  const bool clean = sticky_error().empty();
-  c.slot_block = (double*)dev_alloc((size_t)nslots * b_slot);
-  c.gw = (double*)dev_alloc(b_gw); c.tw = (double*)dev_alloc(b_tw); c.ew = (double*)dev_alloc(b_ew); c.ck = (double*)dev_alloc(b_ck); c.cfcn = (double*)dev_alloc(b_cf);
-  c.flag = (int*)dev_alloc(8);
-  c.tape.part = (TapePart*)dev_alloc((size_t)cap * nb * sizeof(TapePart)); c.tape.idx = (TapeIdx*)dev_alloc((size_t)cap * nb * sizeof(TapeIdx));
-  c.tape.adj = (double*)dev_alloc((size_t)cap * nb * 8); c.tape.overflow = c.flag ? c.flag + 1 : nullptr; c.tape.stride = nb; c.tape.cap = cap;
-  if (!(c.slot_block && c.gw && c.tw && c.ew && c.ck && c.cfcn && c.flag && c.tape.part && c.tape.idx && c.tape.adj)) {
-    err = std::string(who) + ": allocation of " + std::to_string(total) + " bytes failed" + (sticky_error().empty() ? std::string() : ": " + sticky_error());
-    if (clean) sticky_error().clear();
-    cloud_destroy();
-    return false;
-  }
-  for (int n = 0; n < nslots; ++n) c.slot.push_back(c.slot_block + (size_t)n * (b_slot / 8));
-  dev_zero(ex, c.cfcn, b_cf);
-  c.p = *p; c.iqi = iqi; c.iql = iql; c.set.assign((size_t)nslots, 0); c.created = 1;
-  return true;
-}
-inline void Dynamics::cloud_destroy() {
-  dev_free(cld.slot_block); dev_free(cld.gw); dev_free(cld.tw); dev_free(cld.ew); dev_free(cld.ck); dev_free(cld.cfcn); dev_free(cld.flag);
-  dev_free(cld.tape.part); dev_free(cld.tape.idx); dev_free(cld.tape.adj);
-  cld = Cloud{};
-}
-inline bool Dynamics::cloud_slot_ok(const char* who, int slot, bool need_set) {
-  if (!cld.created) { err = std::string(who) + ": call fv3lm_cloud_create first"; return false; }
-  if (slot < 0 || slot >= conv.nslots) { err = std::string(who) + ": slot " + std::to_string(slot) + " out of range (0.." + std::to_string(conv.nslots - 1) + ")"; return false; }
-  if (!conv.set[(size_t)slot]) { err = std::string(who) + ": the convection slot " + std::to_string(slot) + " was never set (fv3lm_convection_set)"; return false; }
-  if (need_set && !cld.set[(size_t)slot]) { err = std::string(who) + ": slot " + std::to_string(slot) + " was never set (fv3lm_cloud_set)"; return false; }
-  return true;
-}
-inline CldArgs Dynamics::cloud_args(int slot) {
-  CldArgs a; a.r = conv_args(slot); a.mst = conv.mst;
-  a.qi = ex.sh(q[(size_t)cld.iqi - 1]); a.ql = ex.sh(q[(size_t)cld.iql - 1]);
-  a.slot = cld.slot[(size_t)slot]; a.cfcn = cld.cfcn;
-  a.gw = cld.gw; a.tw = cld.tw; a.ew = cld.ew; a.ck = cld.ck; a.tape = cld.tape; a.nb = cld.nb; a.p = cld.p; a.flag = cld.flag;
-  return a;
-}
-// the slot takes QLS QCN cfcn khl khu from the host, PLE from the resident delp and everything else from the convection slot of the same
-// number; the split, the fractions, CLOUD_DRIVER in values and (do_phy_mst = 2) the per-cell switch
-inline bool Dynamics::cloud_set(int slot, const double* qls, const double* qcn, const double* cfcn, const double* khl, const double* khu) {
-  const char* who = "fv3lm_cloud_set";
-  auto no = [&](const std::string& m) { err = std::string(who) + ": " + m; return false; };
-  if (!cloud_slot_ok(who, slot, false)) return false;
-  if (!qls || !qcn || !cfcn || !khl || !khu) return no("null array");
-  const size_t nc = conv_ncol(), pc = (size_t)g.tx * g.ty; const int lm = g.npz;
-  for (size_t n = 0; n < nc * lm; ++n)
-    if (turb_stored_nonfinite(qls + n) || turb_stored_nonfinite(qcn + n) || turb_stored_nonfinite(cfcn + n)) return no("a value that is not finite in QLS, QCN or cfcn");
-  for (size_t n = 0; n < nc; ++n) {
-    if (turb_stored_nonfinite(khl + n) || turb_stored_nonfinite(khu + n)) return no("a value that is not finite in khl or khu");
-    const long l = std::lround(khl[n]), u = std::lround(khu[n]);
-    if (l < 1 || l > lm || u < 1 || u > lm) return no("khl = " + std::to_string(l) + ", khu = " + std::to_string(u) + " outside 1..npz = 1.." + std::to_string(lm));
-  }
-  cld.set[(size_t)slot] = 0;
-  CldArgs a = cloud_args(slot);
-  std::vector<double> buf((size_t)(lm + 1) * nc, 0.);
-  auto pack = [&](int v, const double* src) {      // [tile][level][point] -> [level][column]
-    for (size_t col = 0; col < nc; ++col) for (int l = 0; l < lm; ++l) buf[(size_t)l * nc + col] = src[((col / pc) * lm + l) * pc + col % pc];
-    h2d(ex, &a.S(v, 0, 0), buf.data(), buf.size() * 8);
-  };
-  pack(CS_QILS, qls); pack(CS_QICN, qcn); pack(CS_CFCN, cfcn);
-  std::vector<double> kh(2 * nc);
-  for (size_t n = 0; n < nc; ++n) { kh[n] = (double)std::lround(khl[n]); kh[nc + n] = (double)std::lround(khu[n]); }      // nint
-  h2d(ex, &a.SC(CSC_KHL, 0), kh.data(), kh.size() * 8);
-  dev_zero(ex, cld.flag, 8);
-  for (size_t first = 0; first < nc; first += (size_t)cld.nb) { a.r.first = (int)first; a.r.n = (int)(nc - first < (size_t)cld.nb ? nc - first : (size_t)cld.nb); run_cloud(ex, -1, a); }
-  int flag[2] = {0, 0};
-  d2h(ex, flag, cld.flag, sizeof flag);
-  if (flag[0]) return no("a value that is not finite in the resident trajectory (slot " + std::to_string(slot) + " is not set)");
-  if (!sticky_error().empty()) { err = sticky_error(); return false; }
-  cld.set[(size_t)slot] = 1;
-  return true;
-}
-inline bool Dynamics::cloud_get(int slot, double* const* out8, double* const* frac4, int* pertmod) {
-  const char* who = "fv3lm_cloud_get";
-  if (!cloud_slot_ok(who, slot, true)) return false;
-  if (out8) for (int n = 0; n < 8; ++n) if (!out8[n]) { err = std::string(who) + ": null array"; return false; }
-  if (frac4) for (int n = 0; n < 4; ++n) if (!frac4[n]) { err = std::string(who) + ": null array"; return false; }
-  const size_t nc = conv_ncol(), pc = (size_t)g.tx * g.ty; const int lm = g.npz;
-  const CldArgs a = cloud_args(slot);
-  std::vector<double> buf((size_t)(lm + 1) * nc);
-  auto unpack = [&](int v, double* dst, int* idst) {      // [level][column] -> [tile][level][point]
-    d2h(ex, buf.data(), &a.S(v, 0, 0), buf.size() * 8);
-    for (size_t col = 0; col < nc; ++col) for (int l = 0; l < lm; ++l) {
-      const size_t n = ((col / pc) * lm + l) * pc + col % pc;
-      if (dst) dst[n] = buf[(size_t)l * nc + col]; else idst[n] = (int)buf[(size_t)l * nc + col];
-    }
-  };
-  if (out8) for (int n = 0; n < 8; ++n) unpack(CS_OUT + n, out8[n], nullptr);
-  if (frac4) for (int n = 0; n < 4; ++n) unpack(CS_FRAC + n, frac4[n], nullptr);
-  if (pertmod) unpack(CS_PMOD, nullptr, pertmod);
-  return true;
-}
-inline bool Dynamics::cloud_cfcn(int put, double* cfcn) {
-  const char* who = "fv3lm_cloud_cfcn";
-  if (!cld.created) { err = std::string(who) + ": call fv3lm_cloud_create first"; return false; }
-  if (!cfcn) { err = std::string(who) + ": null array"; return false; }
-  const size_t n3c = conv_ncol() * g.npz;
-  if (put) for (size_t n = 0; n < n3c; ++n) if (turb_stored_nonfinite(cfcn + n)) { err = std::string(who) + ": a value that is not finite"; return false; }
-  if (put) h2d(ex, cld.cfcn, cfcn, n3c * 8); else d2h(ex, cfcn, cld.cfcn, n3c * 8);
-  return true;
-}
-// every column, in dense batches.  The slot is read only; mode 0 writes the trajectory tracers iqi, iql
-inline bool Dynamics::cloud_run(int slot, int mode) {
-  const char* who = "fv3lm_cloud";
-  if (!cloud_slot_ok(who, slot, false)) return false;
-  if (mode < 0 || mode > 2) { err = std::string(who) + ": bad mode"; return false; }
-  if (!cloud_slot_ok(who, slot, true)) return false;
-  CldArgs a = cloud_args(slot);
-  const size_t nc = conv_ncol();
-  if (mode == MODE_AD) dev_zero(ex, cld.flag, 8);
-  for (size_t first = 0; first < nc; first += (size_t)cld.nb) { a.r.first = (int)first; a.r.n = (int)(nc - first < (size_t)cld.nb ? nc - first : (size_t)cld.nb); run_cloud(ex, mode, a); }
-  if (mode == MODE_AD) {
-    int flag[2] = {0, 0};
-    d2h(ex, flag, cld.flag, sizeof flag);
-    if (flag[1]) { err = std::string(who) + ": the tape of a segment overflowed (CLD_TAPE); the adjoint fields are not valid"; return false; }
-  }
-  if (!sticky_error().empty()) { err = sticky_error(); return false; }
-  return true;
 }
 
 }  // namespace fv3

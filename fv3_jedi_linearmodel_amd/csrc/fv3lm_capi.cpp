@@ -2,13 +2,13 @@
 // Built with `hipcc -x hip --offload-arch=gfx950` into libfv3lm_hip.so (the product), and with
 // `g++ -DFV3LM_HOST_EMUL` into tests/_emul/libfv3lm_emul.so (test-only host emulation, never
 // loaded by the package).
-#include "dynamics.h"
+#include "physics.h"
 #include <array>
 #include <string>
 
 using namespace fv3;
 
-struct fv3lm_handle { Dynamics d; };
+struct fv3lm_handle { Dynamics d; Physics p{d}; };
 
 static thread_local std::string g_err;
 static int fail(const std::string& m) { g_err = m; return 1; }
@@ -40,7 +40,7 @@ int fv3lm_create(fv3lm_handle** out, const fv3lm_dims* dm, const fv3lm_options* 
   }
   fv3lm_handle* h = new fv3lm_handle;
   // every failure path releases what was allocated so far (destroy2 / destroy accept a partly built object); the failure is reported here, once
-  auto bail = [&](std::string e) { h->d.destroy2(); h->d.destroy(); delete h; sticky_error().clear(); return fail("fv3lm_create: " + e); };   // e by value: it may live in *h
+  auto bail = [&](std::string e) { h->p.release(); h->d.destroy2(); h->d.destroy(); delete h; sticky_error().clear(); return fail("fv3lm_create: " + e); };   // e by value: it may live in *h
   if (!h->d.init(dm->nx, dm->ny, dm->npz, dm->ntile, dm->face, dm->nq, dm->dt, dm->n_split, dm->k_split, *opt, metrics, da_min,
                  da_min_c, phis, dm->nface, dm->tile_ij0)) return bail(h->d.err);
   if (!sticky_error().empty()) return bail(sticky_error());
@@ -53,7 +53,7 @@ int fv3lm_create(fv3lm_handle** out, const fv3lm_dims* dm, const fv3lm_options* 
 
 int fv3lm_destroy(fv3lm_handle* h) {
   if (!h) return 0;
-  h->d.destroy2(); h->d.destroy(); delete h;
+  h->p.release(); h->d.destroy2(); h->d.destroy(); delete h;
   if (--g_live <= 0) { g_live = 0; sticky_error().clear(); }      // the last handle takes its unreported failures with it
   return 0;
 }
@@ -193,21 +193,23 @@ int fv3lm_rayleigh(fv3lm_handle* h, int mode) {
   h->d.rayleigh(mode);
   return status(h);
 }
+// an entry point of the column physics (physics.h): the call's own refusal comes back through the handle's error string
+extern "C++" {
+template <class Fn> static int physics_call(fv3lm_handle* h, const char* name, const Fn& fn) {
+  if (!h) return fail(std::string(name) + ": null handle");
+  if (!fn(h->p)) return fail(h->d.err);
+  return status(h);
+}
+}
 // linearised boundary-layer turbulence (turbulence.h)
 int fv3lm_turbulence_create(fv3lm_handle* h, int nslots) {
-  if (!h) return fail("fv3lm_turbulence_create: null handle");
-  if (!h->d.turb_create(nslots)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_turbulence_create", [&](Physics& p_) { return p_.turb_create(nslots); });
 }
 int fv3lm_turbulence_set_diagonals(fv3lm_handle* h, int slot, const double* const* diag) {
-  if (!h) return fail("fv3lm_turbulence_set_diagonals: null handle");
-  if (!h->d.turb_set_diagonals(slot, diag)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_turbulence_set_diagonals", [&](Physics& p_) { return p_.turb_set_diagonals(slot, diag); });
 }
 int fv3lm_turbulence_set_simple(fv3lm_handle* h, int slot, const double* frocean) {
-  if (!h) return fail("fv3lm_turbulence_set_simple: null handle");
-  if (!h->d.turb_set_simple(slot, frocean)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_turbulence_set_simple", [&](Physics& p_) { return p_.turb_set_simple(slot, frocean); });
 }
 void fv3lm_bl_default_params(fv3lm_bl_params* p, int kpblmin) {      // bldriver.F90:100-127
   if (!p) return;
@@ -217,20 +219,14 @@ void fv3lm_bl_default_params(fv3lm_bl_params* p, int kpblmin) {      // bldriver
 }
 int fv3lm_turbulence_set_driver(fv3lm_handle* h, int slot, const fv3lm_bl_params* p, double dt, const double* const* sfc, const double* qa,
                                 const double* qb, int cloud_mode, double* const* raw_out) {
-  if (!h) return fail("fv3lm_turbulence_set_driver: null handle");
   static_assert(sizeof(fv3lm_bl_params) == sizeof(BlParams), "fv3lm_bl_params and BlParams must agree");
-  if (!h->d.turb_set_driver(slot, reinterpret_cast<const BlParams*>(p), dt, sfc, qa, qb, cloud_mode, raw_out)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_turbulence_set_driver", [&](Physics& p_) { return p_.turb_set_driver(slot, reinterpret_cast<const BlParams*>(p), dt, sfc, qa, qb, cloud_mode, raw_out); });
 }
 int fv3lm_turbulence(fv3lm_handle* h, int slot, int mode) {
-  if (!h) return fail("fv3lm_turbulence: null handle");
-  if (!h->d.turb_run(slot, mode)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_turbulence", [&](Physics& p_) { return p_.turb_run(slot, mode); });
 }
 int fv3lm_turbulence_get(fv3lm_handle* h, int slot, double* const* out) {
-  if (!h) return fail("fv3lm_turbulence_get: null handle");
-  if (!h->d.turb_get(slot, out)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_turbulence_get", [&](Physics& p_) { return p_.turb_get(slot, out); });
 }
 // linearised RAS convection (convection.h)
 void fv3lm_ras_default_params(fv3lm_ras_params* p, int im) {      // fv3jedi_lm_moist_mod.F90:120-148
@@ -241,35 +237,23 @@ void fv3lm_ras_default_params(fv3lm_ras_params* p, int im) {      // fv3jedi_lm_
   p->r[22] = imsize <= 200 ? 4000.0 : imsize <= 400 ? 2000.0 : imsize <= 800 ? 700.0 : 450.0;
 }
 int fv3lm_convection_create(fv3lm_handle* h, int nslots, const fv3lm_ras_params* p, int do_phy_mst) {
-  if (!h) return fail("fv3lm_convection_create: null handle");
   static_assert(sizeof(fv3lm_ras_params) == sizeof(RasParams), "fv3lm_ras_params and RasParams must agree");
-  if (!h->d.conv_create(nslots, reinterpret_cast<const RasParams*>(p), do_phy_mst)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_convection_create", [&](Physics& p_) { return p_.conv_create(nslots, reinterpret_cast<const RasParams*>(p), do_phy_mst); });
 }
 int fv3lm_convection_set(fv3lm_handle* h, int slot, const double* ts, const double* frland, const double* kcbl) {
-  if (!h) return fail("fv3lm_convection_set: null handle");
-  if (!h->d.conv_set(slot, ts, frland, kcbl)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_convection_set", [&](Physics& p_) { return p_.conv_set(slot, ts, frland, kcbl); });
 }
 int fv3lm_convection_get(fv3lm_handle* h, int slot, double* const* out6, int* doconvec, double* jac2) {
-  if (!h) return fail("fv3lm_convection_get: null handle");
-  if (!h->d.conv_get(slot, out6, doconvec, jac2)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_convection_get", [&](Physics& p_) { return p_.conv_get(slot, out6, doconvec, jac2); });
 }
 int fv3lm_convection_sources(fv3lm_handle* h, int put, double* const* src4) {
-  if (!h) return fail("fv3lm_convection_sources: null handle");
-  if (!h->d.conv_sources(put, src4)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_convection_sources", [&](Physics& p_) { return p_.conv_sources(put, src4); });
 }
 int fv3lm_convection_table(fv3lm_handle* h, double* table, double* constants) {
-  if (!h) return fail("fv3lm_convection_table: null handle");
-  if (!h->d.conv_table(table, constants)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_convection_table", [&](Physics& p_) { return p_.conv_table(table, constants); });
 }
 int fv3lm_convection(fv3lm_handle* h, int slot, int mode) {
-  if (!h) return fail("fv3lm_convection: null handle");
-  if (!h->d.conv_run(slot, mode)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_convection", [&](Physics& p_) { return p_.conv_run(slot, mode); });
 }
 // linearised cloud scheme (cloud.h)
 void fv3lm_cloud_default_params(fv3lm_cloud_params* p, int im) {      // fv3jedi_lm_moist_mod.F90:151-211
@@ -283,30 +267,20 @@ void fv3lm_cloud_default_params(fv3lm_cloud_params* p, int im) {      // fv3jedi
   p->r[45] = p->r[41] + 0.01;
 }
 int fv3lm_cloud_create(fv3lm_handle* h, const fv3lm_cloud_params* p, int iqi, int iql) {
-  if (!h) return fail("fv3lm_cloud_create: null handle");
   static_assert(sizeof(fv3lm_cloud_params) == sizeof(CldParams), "fv3lm_cloud_params and CldParams must agree");
-  if (!h->d.cloud_create(reinterpret_cast<const CldParams*>(p), iqi, iql)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_cloud_create", [&](Physics& p_) { return p_.cloud_create(reinterpret_cast<const CldParams*>(p), iqi, iql); });
 }
 int fv3lm_cloud_set(fv3lm_handle* h, int slot, const double* qls, const double* qcn, const double* cfcn, const double* khl, const double* khu) {
-  if (!h) return fail("fv3lm_cloud_set: null handle");
-  if (!h->d.cloud_set(slot, qls, qcn, cfcn, khl, khu)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_cloud_set", [&](Physics& p_) { return p_.cloud_set(slot, qls, qcn, cfcn, khl, khu); });
 }
 int fv3lm_cloud_get(fv3lm_handle* h, int slot, double* const* out8, double* const* frac4, int* pertmod) {
-  if (!h) return fail("fv3lm_cloud_get: null handle");
-  if (!h->d.cloud_get(slot, out8, frac4, pertmod)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_cloud_get", [&](Physics& p_) { return p_.cloud_get(slot, out8, frac4, pertmod); });
 }
 int fv3lm_cloud_cfcn(fv3lm_handle* h, int put, double* cfcn) {
-  if (!h) return fail("fv3lm_cloud_cfcn: null handle");
-  if (!h->d.cloud_cfcn(put, cfcn)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_cloud_cfcn", [&](Physics& p_) { return p_.cloud_cfcn(put, cfcn); });
 }
 int fv3lm_cloud(fv3lm_handle* h, int slot, int mode) {
-  if (!h) return fail("fv3lm_cloud: null handle");
-  if (!h->d.cloud_run(slot, mode)) return fail(h->d.err);
-  return status(h);
+  return physics_call(h, "fv3lm_cloud", [&](Physics& p_) { return p_.cloud_run(slot, mode); });
 }
 int fv3lm_step_tl(fv3lm_handle* h) { h->d.step_tl(); return status(h); }
 int fv3lm_step_nl(fv3lm_handle* h) { h->d.step_nl(); return status(h); }
