@@ -440,6 +440,29 @@ class Dycore:
         self.lib.L.fv3lm_cloud.argtypes = [C.c_void_p, C.c_int, C.c_int]
         self._chk(self.lib.L.fv3lm_cloud(self.h, int(slot), int(mode)))
 
+    # ---- the composed model step (src/fv3jedi_lm_mod.F90:161-187; csrc/model.h) over stored trajectory times ----
+    def lm_create(self, nslots, do_dyn=1, do_phy_trb=1, do_phy_mst=1):
+        """fv3lm_lm_create: nslots trajectory slots (u v pt delp q* (w delz) phis, whole padded planes) in one allocation; the flags are
+        conf%do_dyn, do_phy_trb and do_phy_mst /= 0, each 0 or 1, checked against the created features at the step"""
+        self.lib.L.fv3lm_lm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        self._chk(self.lib.L.fv3lm_lm_create(self.h, int(nslots), int(do_dyn), int(do_phy_trb), int(do_phy_mst)))
+
+    def lm_traj_save(self, slot):
+        """the resident trajectory, halos included, into the slot (after traj_to_fv3 and the physics sets of that time)"""
+        self.lib.L.fv3lm_lm_traj_save.argtypes = [C.c_void_p, C.c_int]
+        self._chk(self.lib.L.fv3lm_lm_traj_save(self.h, int(slot)))
+
+    def lm_traj_load(self, slot):
+        """the slot back: the handle is then as after traj_to_fv3 of the same host arrays; the perturbation is not touched"""
+        self.lib.L.fv3lm_lm_traj_load.argtypes = [C.c_void_p, C.c_int]
+        self._chk(self.lib.L.fv3lm_lm_traj_load(self.h, int(slot)))
+
+    def lm_step(self, slot, mode):
+        """one step of the whole linear model about the trajectory of the slot, on the resident perturbation.  TL: dynamics, convection,
+        cloud, turbulence; AD: turbulence, cloud, convection, dynamics (forward + backward sweep); cfcn cleared before and after"""
+        self.lib.L.fv3lm_lm_step.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        self._chk(self.lib.L.fv3lm_lm_step(self.h, int(slot), int(mode)))
+
     # ---- the host's boundary copies on the device (compact arrays [ntile, nk, ny, nx], no halo) ----
     def _cptrs(self, d, names, out=False):
         keep = []

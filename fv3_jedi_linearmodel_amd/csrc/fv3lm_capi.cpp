@@ -2,13 +2,13 @@
 // Built with `hipcc -x hip --offload-arch=gfx950` into libfv3lm_hip.so (the product), and with
 // `g++ -DFV3LM_HOST_EMUL` into tests/_emul/libfv3lm_emul.so (test-only host emulation, never
 // loaded by the package).
-#include "physics.h"
+#include "model.h"
 #include <array>
 #include <string>
 
 using namespace fv3;
 
-struct fv3lm_handle { Dynamics d; Physics p{d}; };
+struct fv3lm_handle { Dynamics d; Physics p{d}; Model m{d, p}; };
 
 static thread_local std::string g_err;
 static int fail(const std::string& m) { g_err = m; return 1; }
@@ -40,7 +40,7 @@ int fv3lm_create(fv3lm_handle** out, const fv3lm_dims* dm, const fv3lm_options* 
   }
   fv3lm_handle* h = new fv3lm_handle;
   // every failure path releases what was allocated so far (destroy2 / destroy accept a partly built object); the failure is reported here, once
-  auto bail = [&](std::string e) { h->p.release(); h->d.destroy2(); h->d.destroy(); delete h; sticky_error().clear(); return fail("fv3lm_create: " + e); };   // e by value: it may live in *h
+  auto bail = [&](std::string e) { h->m.release(); h->p.release(); h->d.destroy2(); h->d.destroy(); delete h; sticky_error().clear(); return fail("fv3lm_create: " + e); };   // e by value: it may live in *h
   if (!h->d.init(dm->nx, dm->ny, dm->npz, dm->ntile, dm->face, dm->nq, dm->dt, dm->n_split, dm->k_split, *opt, metrics, da_min,
                  da_min_c, phis, dm->nface, dm->tile_ij0)) return bail(h->d.err);
   if (!sticky_error().empty()) return bail(sticky_error());
@@ -53,7 +53,7 @@ int fv3lm_create(fv3lm_handle** out, const fv3lm_dims* dm, const fv3lm_options* 
 
 int fv3lm_destroy(fv3lm_handle* h) {
   if (!h) return 0;
-  h->p.release(); h->d.destroy2(); h->d.destroy(); delete h;
+  h->m.release(); h->p.release(); h->d.destroy2(); h->d.destroy(); delete h;
   if (--g_live <= 0) { g_live = 0; sticky_error().clear(); }      // the last handle takes its unreported failures with it
   return 0;
 }
@@ -85,12 +85,8 @@ static int status(fv3lm_handle* h) {
     if (e != hipSuccess) set_sticky(std::string("HIP stream failed: ") + hipGetErrorString(e));
   }
 #endif
-  if (!sticky_error().empty()) return fail(sticky_error());
-  if (!h->d.err.empty() && h->d.halo_missing) return fail(h->d.err);
-  if (h->d.halo_missing) return fail("halo exchange needed before fv3lm_set_exchange provided its table (face mode)");
-  if (h->d.tracer_subcycle_error) return fail("tracer_2d: accumulated Courant number > 60: trajectory is not usable");
-  if (h->d.nh_overflow()) return fail("non-hydrostatic column solver: reverse-mode tape overflow (internal sizing error)");
-  return 0;
+  const std::string e = pending_failure(h->d);
+  return e.empty() ? 0 : fail(e);
 }
 int fv3lm_set_face_data(fv3lm_handle* h, const double* edge, const double* ecorner) {
   if (!edge || !ecorner) return fail("fv3lm_set_face_data: null argument");
@@ -282,6 +278,20 @@ int fv3lm_cloud_cfcn(fv3lm_handle* h, int put, double* cfcn) {
 int fv3lm_cloud(fv3lm_handle* h, int slot, int mode) {
   return physics_call(h, "fv3lm_cloud", [&](Physics& p_) { return p_.cloud_run(slot, mode); });
 }
+// the composed model step (model.h): fv3jedi_lm_mod's step_tl / step_ad over stored trajectory times
+extern "C++" {
+template <class Fn> static int model_call(fv3lm_handle* h, const char* name, const Fn& fn) {
+  if (!h) return fail(std::string(name) + ": null handle");
+  if (!fn(h->m)) return fail(h->d.err);
+  return status(h);
+}
+}
+int fv3lm_lm_create(fv3lm_handle* h, int nslots, int do_dyn, int do_phy_trb, int do_phy_mst) {
+  return model_call(h, "fv3lm_lm_create", [&](Model& m_) { return m_.create(nslots, do_dyn, do_phy_trb, do_phy_mst); });
+}
+int fv3lm_lm_traj_save(fv3lm_handle* h, int slot) { return model_call(h, "fv3lm_lm_traj_save", [&](Model& m_) { return m_.traj_save(slot); }); }
+int fv3lm_lm_traj_load(fv3lm_handle* h, int slot) { return model_call(h, "fv3lm_lm_traj_load", [&](Model& m_) { return m_.traj_load(slot); }); }
+int fv3lm_lm_step(fv3lm_handle* h, int slot, int mode) { return model_call(h, "fv3lm_lm_step", [&](Model& m_) { return m_.step(slot, mode); }); }
 int fv3lm_step_tl(fv3lm_handle* h) { h->d.step_tl(); return status(h); }
 int fv3lm_step_nl(fv3lm_handle* h) { h->d.step_nl(); return status(h); }
 int fv3lm_step_ad(fv3lm_handle* h) { h->d.step_ad(); return status(h); }

@@ -257,8 +257,9 @@ int fv3lm_turbulence_set_driver(fv3lm_handle* h, int slot, const fv3lm_bl_params
  *   fv3lm_convection: DOCONVEC columns only.  mode 0: RASE on the trajectory, u v T q1 written back (step_nl); 1: RASE_D on the
  *       perturbation of u v pt q1, T -> theta by p00^kappa / pk in and back out, the sources cleared and then written in the active
  *       columns; 2: RASE_B, theta = T pk / p00^kappa in and its inverse out, the sources are consumed and cleared.  Host order, as
- *       fv3jedi_lm_mod.F90:161-187:  tangent  fv3lm_step_tl ; fv3lm_turbulence(1) ; fv3lm_convection(1)
- *                                    adjoint  fv3lm_convection(2) ; fv3lm_turbulence(2) ; fv3lm_step_ad.
+ *       fv3jedi_lm_mod.F90:161-187 and fv3jedi_lm_physics_mod.F90:121-122, :137-138 (the moist half before the turbulence in the
+ *       tangent, after it in the adjoint):  tangent  fv3lm_step_tl ; fv3lm_convection(1) ; fv3lm_turbulence(1)
+ *                                           adjoint  fv3lm_turbulence(2) ; fv3lm_convection(2) ; fv3lm_step_ad.
  *   fv3lm_convection_table: diagnostics -- the 18301 entries of the saturation table as they lie on the device (ESINIT, 150 K .. 333 K in
  *       steps of 0.01 K) and the nine constants of the kernels: CP ALHL GRAV RGAS H2OMW AIRMW VIREPS P00 KAPPA (MAPL_Constants in double).
  *   Refused with a message, the slot left unset: before create or a second create; nslots < 1; do_phy_mst outside 1..2; a handle without
@@ -296,8 +297,9 @@ int fv3lm_convection_table(fv3lm_handle* h, double* table, double* constants);
  *       the parts are summed, theta goes back to T, cfcn is updated.  2: theta = T pk / p00^kappa, both parts of qi and ql receive the
  *       full adjoint; after the driver they are combined with the fractions and the adjoints of the four sources are written where
  *       fv3lm_convection(2) consumes them.  Host order:
- *           tangent  fv3lm_step_tl ; fv3lm_turbulence(1) ; fv3lm_convection(1) ; fv3lm_cloud(1)
- *           adjoint  fv3lm_cloud(2) ; fv3lm_convection(2) ; fv3lm_turbulence(2) ; fv3lm_step_ad.
+ *           tangent  fv3lm_step_tl ; fv3lm_convection(1) ; fv3lm_cloud(1) ; fv3lm_turbulence(1)
+ *           adjoint  fv3lm_turbulence(2) ; fv3lm_cloud(2) ; fv3lm_convection(2) ; fv3lm_step_ad
+ *       (fv3jedi_lm_physics_mod.F90:121-122, :137-138); fv3lm_lm_step below runs exactly this.
  *   Refused with a message, the slot left unset: before fv3lm_convection_create or a second create; iqi / iql out of range or equal;
  *   CLOUDPARAMS(57) /= 1 (only the top-hat PDF is built); a slot whose convection slot was never set; a slot out of range or never set; a
  *   mode outside 0..2; a NULL array where one is required; khl / khu outside 1..npz; a value that is not finite; an allocation that
@@ -309,6 +311,34 @@ int fv3lm_cloud_set(fv3lm_handle* h, int slot, const double* qls, const double* 
 int fv3lm_cloud_get(fv3lm_handle* h, int slot, double* const* out8, double* const* frac4, int* pertmod);
 int fv3lm_cloud_cfcn(fv3lm_handle* h, int put, double* cfcn);
 int fv3lm_cloud(fv3lm_handle* h, int slot, int mode);
+/* The composed model step: fv3jedi_lm_mod's step_tl / step_ad (src/fv3jedi_lm_mod.F90:161-187), the dynamics and the column physics of
+ * one time step in the reference's order, about the trajectory of a stored time.
+ *   fv3lm_lm_create: nslots trajectory slots in one allocation, all or nothing (a refusal names FV3LM_TRAJ_SLOTS: fv3lm_create has by
+ *       then taken the acoustic-step slots from free memory).  A slot holds what fv3lm_traj_to_fv3 leaves resident of the trajectory:
+ *       u v pt delp q* (w delz on a non-hydrostatic handle) and phis, whole padded planes.  do_dyn, do_phy_trb, do_phy_mst: conf%do_dyn,
+ *       conf%do_phy_trb and whether conf%do_phy_mst /= 0, each 0 or 1 (its value 1 or 2 stays with fv3lm_convection_create); a flag may
+ *       be set before the feature it names is created, the check is made at the step.
+ *   fv3lm_lm_traj_save: the resident trajectory, halos included, into the slot by device-to-device copies; the slot is then set.  The
+ *       physics slots carry the same number: the host sets them (fv3lm_convection_set, fv3lm_cloud_set, fv3lm_turbulence_set_*) while
+ *       the trajectory of that time is resident, then saves it.
+ *   fv3lm_lm_traj_load: the slot back; the handle is then as after fv3lm_traj_to_fv3 of the same host arrays, bit for bit (halos, D-grid
+ *       edge rows, halo of phis; pe peln pk pkz computed again from delp as the upload does).  Neither call touches the perturbation.
+ *   fv3lm_lm_step: mode 1 tangent, 2 adjoint, on the resident perturbation.  ipert_to_zero (:167, :170, :182, :185, :242-253) clears the
+ *       device's cfcn perturbation before and after either (where the cloud feature exists).
+ *           tangent (:161-172; physics fv3jedi_lm_physics_mod.F90:121-122)
+ *               do_dyn: traj_load(slot) ; fv3lm_step_tl      do_phy_mst: convection(slot, 1) ; cloud(slot, 1)      do_phy_trb: turbulence(slot, 1)
+ *           adjoint (:176-187; physics :137-138)
+ *               do_phy_trb: turbulence(slot, 2)      do_phy_mst: cloud(slot, 2) ; convection(slot, 2)
+ *               do_dyn: traj_load(slot) ; fv3lm_step_nl ; fv3lm_step_ad (the dynamics' step_ad is forward sweep + backward sweep)
+ *       A part that fails (a tape overflow, a pending device failure) ends the step with its own message; nothing runs after it.
+ *   Refused with a message before anything is run or cleared: before create or a second create; nslots < 1; a flag outside 0..1 or all
+ *   three 0; a slot out of range; a load, or a step with do_dyn, of a slot never saved; a mode other than 1 or 2 (the nonlinear step is
+ *   composed from the parts: its physics must be set from the trajectory the dynamics has just advanced); a physics flag whose feature
+ *   was never created or whose slot was never set; do_phy_mst with the convection created and the cloud scheme not. */
+int fv3lm_lm_create(fv3lm_handle* h, int nslots, int do_dyn, int do_phy_trb, int do_phy_mst);
+int fv3lm_lm_traj_save(fv3lm_handle* h, int slot);   /* resident trajectory -> slot */
+int fv3lm_lm_traj_load(fv3lm_handle* h, int slot);   /* slot -> resident trajectory */
+int fv3lm_lm_step(fv3lm_handle* h, int slot, int mode);   /* mode 1 tangent, 2 adjoint */
 /* Per-kernel HIP-event profile of everything launched between begin and end, on the library's stream:
  * lines "kernel count total_ms algorithmic_bytes".  Returns the buffer length needed. */
 int fv3lm_profile_begin(fv3lm_handle* h);
