@@ -606,21 +606,24 @@ HD void remap_press_col_nh_ad(const NhColArgs& a, int tile, int i, int j) {
   a.f[9].p[F(9, km + 1)] = 0.;
   a.f[0].p[F(0, km + 1)] += ps_ad;
 }
-// adjoint of ring_col written out (a cumulative sum and, for pk3, one power per level): consumes f[1].p, accumulates into f[0].p
-HD void ring_col_ad(const NhColArgs& a, int tile, int i, int j) {
+// adjoint of ring_col written out (a cumulative sum and, for pk3, one power per level): consumes f[1].p, accumulates into f[0].p.
+// The interface pressures of the pk3 ring are kept in raw workspace slot 0 as the forward sums gave them: taking the layers off the
+// surface pressure again on the way up loses the thin top layers to cancellation (p = 1 Pa under a sum of 1e5 Pa).
+HD void ring_col_ad(const NhColArgs& a, const ColWs& ws, int tile, int i, int j) {
   const Geom& g = a.g; const int km = g.npz;
-  double p = a.ptop;
-  for (int k = 1; k <= km; ++k) p += a.f[0].t[fidx(g, a.f[0], tile, i, j, k)];
+  if (a.what != 1) {
+    double p = a.ptop;
+    for (int k = 1; k <= km; ++k) { p += a.f[0].t[fidx(g, a.f[0], tile, i, j, k)]; ws.at(0, k) = p; }
+  }
   if (a.what == 1) a.f[1].p[fidx(g, a.f[1], tile, i, j, 1)] = 0.;
   double sum = 0.;
   for (int k = km; k >= 1; --k) {
     const size_t n = fidx(g, a.f[1], tile, i, j, k + 1);
     const double oa = a.f[1].p[n];
     a.f[1].p[n] = 0.;
-    sum += (a.what == 1) ? oa : a.akap * exp(a.akap * log(p)) / p * oa;
-    const size_t m = fidx(g, a.f[0], tile, i, j, k);
-    a.f[0].p[m] += sum;
-    p -= a.f[0].t[m];
+    if (a.what == 1) sum += oa;
+    else { const double p = ws.at(0, k); sum += a.akap * exp(a.akap * log(p)) / p * oa; }
+    a.f[0].p[fidx(g, a.f[0], tile, i, j, k)] += sum;
   }
 }
 
@@ -651,7 +654,7 @@ struct NhColFn {
     const ColWs ws{a.ws + col, a.ws_stride, a.g.npz + 2};
     const double hs = a.hs ? a.hs[col] : 0.;
     if (KIND == NHC_EDGE && MODE == MODE_AD) { edge_col_ad(a, ws, z, i, j); return; }
-    if (KIND == NHC_RING && MODE == MODE_AD) { ring_col_ad(a, z, i, j); return; }
+    if (KIND == NHC_RING && MODE == MODE_AD) { ring_col_ad(a, ws, z, i, j); return; }
     if (KIND == NHC_ZH_INIT && MODE == MODE_AD && !a.use_tape) { zh_init_col_ad(a, z, i, j); return; }
     if (KIND == NHC_RM_PRESS && MODE == MODE_AD && !a.use_tape) { remap_press_col_nh_ad(a, z, i, j); return; }
     if ((KIND == NHC_RM_FIELD || KIND == NHC_RM_W) && MODE == MODE_AD && !(KIND == NHC_RM_W && a.use_tape)) { remap_field_col_nh_ad(a, ws, z, i, j); return; }

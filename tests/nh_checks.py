@@ -220,3 +220,90 @@ def nh_adjoint_fields(c):
     c.dy.put("ws", rng.standard_normal((1, 1, c.ny + 7, c.nx + 7)), 1)     # exercises the surface-w output of the last step too
     c.dy.dyn_core(AD)
     return {n: c.dy.get(n, 1)[0].copy() for n in INS}
+
+
+# ---- lifted levels inside whole acoustic steps: two adjacent layers of 15 .. 20 Pa near the surface, balanced thickness below dz_min = 2 m
+def thin_layer_levels(npz, ptop=1.0, p0=1.0e5):
+    """grid.hybrid_levels with layers npz-2 and npz-1 (1-based) cut to 20 Pa and 19 Pa at p0, the rest of their mass given to layer npz-3.
+    The three interfaces share one ak, so the two layers are bk differences alone and stay thin at every surface pressure"""
+    from fv3_jedi_linearmodel_amd.grid import hybrid_levels
+    ak, bk = hybrid_levels(npz, ptop, p0)
+    ak, bk = ak.copy(), bk.copy()
+    lo = ak[npz - 1] + bk[npz - 1] * p0          # the lower interface of layer npz-1 stays where it is
+    for k, p in ((npz - 2, lo - 19.0), (npz - 3, lo - 19.0 - 20.0)):
+        ak[k] = ak[npz - 1]
+        bk[k] = (p - ak[k]) / p0
+    return ak, bk
+
+
+def check_fix_fired(c):
+    """on the product's own advected heights after the run: inside the compute domain an interface lies below the one beneath + dz_min"""
+    zh_a = c.dy.get("zh_a", 0)[0]
+    A = c.rect(1, c.nx, 1, c.ny)
+    z = zh_a[A]
+    hit = 0
+    for k in range(c.npz - 1, -1, -1):       # replay the fix from the bottom, as the solver does
+        lim = z[k + 1] + 2.0
+        low = z[k] < lim
+        hit += int(np.sum(low))
+        z[k] = np.where(low, lim, z[k])
+    assert hit >= c.nx * c.ny, ("the dz_min fix fired at", hit, "points")
+    return hit
+
+
+def oracle_movement(c, mode, T, P=None, seeds=None, n=2):
+    """how far one ulp on the inputs moves the oracle's own double-precision result (relative L-inf per output field, largest of n jitters): with
+    layers of 20 Pa the pressure-gradient and the solver divide by masses 500 times smaller than elsewhere in the column, and 1e-11 is no longer
+    reachable by any double-precision code; the bound of the lifted case is max(1e-11, 8 x this), as for the column checks (nh_column_checks.py)"""
+    rng = np.random.default_rng(97)
+    A = c.rect(1, c.nx, 1, c.ny)
+    run = lambda TT: c.oracle.dyn_core_nh(mode, c.dims.dt, c.dims.n_split, TT, P, *([seeds] if seeds is not None else []))
+    base = run(T)
+    mv = np.zeros((2, len(base[1])))          # [0] trajectory outputs (TL run), [1] tangent outputs / adjoint inputs
+    for _ in range(n):
+        Tj = [t * (1.0 + rng.integers(-1, 2, t.shape) * 2.0 ** -53) for t in T]
+        out = run(Tj)
+        for w in ((0, 1) if mode == TL else (1,)):
+            for m, (a, b) in enumerate(zip(out[w], base[w])):
+                r = (slice(None),) if mode == AD else A
+                mv[w, m] = max(mv[w, m], relerr(a[r], b[r]))
+    return mv
+
+
+def check_nh_lifted(c):
+    """tangent, adjoint and dot product of two acoustic steps with the dz_min fix firing, against oracle/nh.hpp; prints every figure"""
+    T, P = nh_state(c)
+    A = c.rect(1, c.nx, 1, c.ny)
+    mv = oracle_movement(c, TL, T, P)
+    ot, op = c.oracle.dyn_core_nh(TL, c.dims.dt, c.dims.n_split, T, P)
+    put(c, T, P)
+    c.dy.dyn_core(TL)
+    hit = check_fix_fired(c)
+    for m, (n, a, b) in enumerate(zip(OUTS, ot, op)):
+        e1, e2 = relerr(c.dy.get(n, 0)[0][A], a[A]), relerr(c.dy.get(n, 1)[0][A], b[A])
+        tol0, tol = max(1e-11, 8.0 * mv[0, m]), max(1e-11, 8.0 * mv[1, m])
+        print("lifted %-5s traj %.2e (oracle movement %.2e, tol %.2e)  tl %.2e (%.2e, %.2e)" % (n, e1, mv[0, m], tol0, e2, mv[1, m], tol))
+        assert e1 < tol0, (n, "traj", e1, tol0)
+        assert e2 < tol, (n, "tl", e2, tol)
+    rng = np.random.default_rng(11)
+    seeds = []
+    for n in OUTS:
+        s = np.zeros((c.dy.levels(n), c.ny + 7, c.nx + 7))
+        if n != "zh":
+            s[A] = rng.standard_normal(s[A].shape)
+        seeds.append(s)
+    mva = oracle_movement(c, AD, T, None, seeds)
+    _, iad = c.oracle.dyn_core_nh(AD, c.dims.dt, c.dims.n_split, T, None, seeds)
+    put(c, T)
+    c.dy.dyn_core(NL)
+    for n, s in zip(OUTS, seeds):
+        c.dy.put(n, s[None], 1)
+    c.dy.dyn_core(AD)
+    for m, (n, a) in enumerate(zip(INS, iad)):
+        e = relerr(c.dy.get(n, 1)[0], a)
+        tol = max(1e-11, 8.0 * mva[1, m])
+        print("lifted ad %-5s %.2e  oracle movement %.2e  tol %.2e" % (n, e, mva[1, m], tol))
+        assert e < tol, (n, "ad", e, tol)
+    check_nh_dot_product(c, tol=max(1e-11, 8.0 * float(np.max(mv[1]))))
+    check_fix_fired(c)                      # and in the trajectory the backward sweep ran on
+    return hit

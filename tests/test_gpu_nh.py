@@ -122,3 +122,11 @@ def test_nh_sim1_adjoint_matches_oracle(nhc_sim1):
 
 def test_nh_sim1_dot_product(nhc_sim1):
     N.check_nh_dot_product(nhc_sim1)
+
+
+def test_nh_lifted_levels_inside_the_acoustic_steps():
+    """two adjacent layers of 20 and 19 Pa near the surface: their balanced thickness is below dz_min = 2 m and the fix lifts them in every step;
+    the first-write adjoint plan, the trajectory slots and the checkpoints carry the lifted solver inputs through the backward sweep"""
+    from common import Case
+    c = Case(nx=10, ny=8, npz=12, n_split=2, dt=40.0, backend="hip", hydrostatic=0, levels=N.thin_layer_levels(12))
+    N.check_nh_lifted(c)
