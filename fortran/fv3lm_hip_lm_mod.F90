@@ -8,7 +8,7 @@ module fv3lm_hip_lm_mod
   use fv3lm_hip_mod
   implicit none
   private
-  public :: fv3lm_hip_lm_create, fv3lm_hip_lm_traj_save, fv3lm_hip_lm_traj_load, fv3lm_hip_lm_step
+  public :: fv3lm_hip_lm_create, fv3lm_hip_lm_traj_save, fv3lm_hip_lm_traj_load, fv3lm_hip_lm_step, fv3lm_hip_cloud_bind_cfcn
 
   interface
     function c_lm_create(h, nslots, do_dyn, do_phy_trb, do_phy_mst) bind(C, name="fv3lm_lm_create") result(rc)
@@ -35,6 +35,12 @@ module fv3lm_hip_lm_mod
       integer(c_int), value :: slot, mode
       integer(c_int) :: rc
     end function c_lm_step
+    function c_cloud_bind_cfcn(h, iqc) bind(C, name="fv3lm_cloud_bind_cfcn") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), value :: iqc
+      integer(c_int) :: rc
+    end function c_cloud_bind_cfcn
     function c_lm_last_error() bind(C, name="fv3lm_last_error") result(p)
       import :: c_ptr
       type(c_ptr) :: p
@@ -87,4 +93,13 @@ contains
     integer, intent(in) :: slot, mode
     call check(c_lm_step(self%handle, int(slot - 1, c_int), int(mode, c_int)), 'lm_step')
   end subroutine fv3lm_hip_lm_step
+
+  !> once, after fv3lm_hip_cloud_create and before the first fv3lm_hip_cloud_set: the convective cloud fraction is tracer iqc (1-based,
+  !! the reference's q(:,:,:,5) with do_phy_mst /= 0, fv3jedi_lm_dynamics_mod.F90:159-163), trajectory and perturbation, and the dynamics
+  !! of fv3lm_hip_lm_step carries it between ipert_to_zero and the cloud scheme as FV_DYNAMICS_TLM / _BWD do
+  subroutine fv3lm_hip_cloud_bind_cfcn(self, iqc)
+    type(fv3lm_hip_type), intent(inout) :: self
+    integer, intent(in) :: iqc
+    call check(c_cloud_bind_cfcn(self%handle, int(iqc, c_int)), 'cloud_bind_cfcn')
+  end subroutine fv3lm_hip_cloud_bind_cfcn
 end module fv3lm_hip_lm_mod

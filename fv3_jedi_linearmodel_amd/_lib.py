@@ -405,6 +405,12 @@ class Dycore:
         self.lib.L.fv3lm_cloud_create.argtypes = [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int]
         self._chk(self.lib.L.fv3lm_cloud_create(self.h, None if params is None else C.byref(params), int(iqi), int(iql)))
 
+    def cloud_bind_cfcn(self, iqc):
+        """fv3lm_cloud_bind_cfcn: after cloud_create, before the first cloud_set: cfcn is tracer iqc of the dycore (trajectory and
+        perturbation), carried by the dynamics as the reference's fifth tracer; cloud_set then accepts cfcn=None"""
+        self.lib.L.fv3lm_cloud_bind_cfcn.argtypes = [C.c_void_p, C.c_int]
+        self._chk(self.lib.L.fv3lm_cloud_bind_cfcn(self.h, int(iqc)))
+
     def cloud_set(self, slot, qls, qcn, cfcn, khl, khu):
         """after convection_set of the same slot: QLS QCN cfcn [ntile, npz, ny, nx], khl khu [ntile, ny, nx] (None: NULL)"""
         a = [None if x is None else self._compact(x, self.dims.npz) for x in (qls, qcn, cfcn)] + [None if x is None else self._compact(x) for x in (khl, khu)]

@@ -717,12 +717,16 @@ struct CldArgs : ColView, ColWork {      // the cloud slot's packed columns and 
   double* rslot;                    // the convection slot of the same number: PTT_C QVT_C, the four _C sources, PLE, PKZ, FRLAND
   int mst;
   Fld pt, delp, q1, qi, ql;
-  double* cfcn;                     // perturbation of the convective cloud fraction, host-compact [ntile][lm][ty][tx]
+  double* cfcn;                     // perturbation of the convective cloud fraction: the feature's own array, host-compact
+                                    // [ntile][lm][ty][tx], or (cf_fld) the perturbation half of the bound tracer, padded planes like pt q1 qi ql
+  double* cfcn_t;                   // bound: the trajectory half of that tracer (null otherwise)
+  int cf_fld;
   double* src;                      // the four sources' perturbation (convection.h)
   const double* tbl; CldParams p;
   double dt, ptop, p00k;
   HD ColView ras() const { FV3LM_LITERAL ColView r = *this; r.slot = rslot; r.ns = RAS_NS; return r; }
   HD int kw() const { FV3LM_LITERAL return lm + 2 < CLD_NSV + 2 ? CLD_NSV + 2 : lm + 2; }
+  HD double& cf(size_t col, int l) const { FV3LM_LITERAL return cfcn[cf_fld ? fld(col, l) : cmp(col, l)]; }      // level l (0-based) of the column's cfcn
   HD CldCol column(int m, size_t col) const { FV3LM_LITERAL
     CldCol c; c.lm = lm; c.mst = mst; c.khl = (int)SC(CSC_KHL, col); c.khu = (int)SC(CSC_KHU, col);
     c.g = ColWs{gw + m, (size_t)nb, kw()}; c.tbl = tbl; c.r = p.r; c.dt = dt; c.frland = ras().SC(SC_FRLAND, col);
@@ -816,18 +820,18 @@ struct CldTlFn {
       const size_t n = r.fld(col, l - 1), nc = r.cmp(col, l - 1);
       const double pk = r.S(S_PKZ, l - 1, col), qi = a.qi.p[n], ql = a.ql.p[n];
       const double d[12] = {a.pt.p[n] * a.p00k / pk, a.q1.p[n], qi * a.S(CS_FRAC, l - 1, col), ql * a.S(CS_FRAC + 2, l - 1, col), qi * a.S(CS_FRAC + 1, l - 1, col),
-                            ql * a.S(CS_FRAC + 3, l - 1, col), 0., a.cfcn[nc], a.src[nc], a.src[n3c + nc], a.src[2 * n3c + nc], a.src[3 * n3c + nc]};
+                            ql * a.S(CS_FRAC + 3, l - 1, col), 0., a.cf(col, l - 1), a.src[nc], a.src[n3c + nc], a.src[2 * n3c + nc], a.src[3 * n3c + nc]};
       for (int v = 0; v < 12; ++v) V(v).set(l, RD(ew.at(v, l), d[v]));
     }
     cld_pre<RD>(c, V);
     for (int k = CLD_KTOP; k <= lm; ++k) cld_level<RD>(c, V, k, (int)a.S(CS_PMOD, k - 1, col), false);
     cld_post<RD>(c, V);
     for (int l = 1; l <= lm; ++l) {
-      const size_t n = r.fld(col, l - 1), nc = r.cmp(col, l - 1);
+      const size_t n = r.fld(col, l - 1);
       const double pk = r.S(S_PKZ, l - 1, col);
       a.pt.p[n] = V(CE_T)(l).d * pk / a.p00k; a.q1.p[n] = V(CE_Q)(l).d;
       a.qi.p[n] = V(CE_QILS)(l).d + V(CE_QICN)(l).d; a.ql.p[n] = V(CE_QLLS)(l).d + V(CE_QLCN)(l).d;
-      a.cfcn[nc] = V(CE_CFCN)(l).d;
+      a.cf(col, l - 1) = V(CE_CFCN)(l).d;
     }
   }
 };
@@ -852,7 +856,7 @@ struct CldAdFn {
       const double pk = r.S(S_PKZ, l - 1, col), qi = a.qi.p[n], ql = a.ql.p[n];
       eb.at(CE_T, l) = a.pt.p[n] * pk / a.p00k; eb.at(CE_Q, l) = a.q1.p[n];
       eb.at(CE_QILS, l) = qi; eb.at(CE_QICN, l) = qi; eb.at(CE_QLLS, l) = ql; eb.at(CE_QLCN, l) = ql;
-      eb.at(CE_CFCN, l) = a.cfcn[r.cmp(col, l - 1)];
+      eb.at(CE_CFCN, l) = a.cf(col, l - 1);
     }
     // the trajectory before pre is needed again: kept in the checkpoint store's last vectors
     const int T0 = CLD_NCK;
@@ -901,16 +905,34 @@ struct CldAdFn {
       a.pt.p[n] = eb.at(CE_T, l) * a.p00k / pk; a.q1.p[n] = eb.at(CE_Q, l);
       a.qi.p[n] = eb.at(CE_QILS, l) * a.S(CS_FRAC, l - 1, col) + eb.at(CE_QICN, l) * a.S(CS_FRAC + 1, l - 1, col);
       a.ql.p[n] = eb.at(CE_QLLS, l) * a.S(CS_FRAC + 2, l - 1, col) + eb.at(CE_QLCN, l) * a.S(CS_FRAC + 3, l - 1, col);
-      a.cfcn[nc] = eb.at(CE_CFCN, l);
+      a.cf(col, l - 1) = eb.at(CE_CFCN, l);
       for (int v = 0; v < 4; ++v) a.src[(size_t)v * n3c + nc] = eb.at(CE_DQL + v, l);
     }
   }
 };
 
-inline void run_cloud(Exec& ex, int what, const CldArgs& a) {      // what: -1 set, 0 nl, 1 tl, 2 ad
+// a bound tracer's trajectory half and the slot.  what 0: the trajectory cfcn into the slot (set_ltraj :720), gathered as convection_set
+// gathers its fields; 1: CF_con as CLOUD_DRIVER in values left it into the trajectory (step_nl :388)
+struct CldCfcnFn {
+  CldArgs a; int what;
+  HD void operator()(int m, int, int) const { FV3LM_LITERAL
+    const size_t col = a.col_of(m);
+    bool bad = false;
+    for (int l = 0; l < a.lm; ++l) {
+      const size_t n = a.fld(col, l);
+      if (what == 0) { a.S(CS_CFCN, l, col) = a.cfcn_t[n]; bad = bad || turb_stored_nonfinite(&a.S(CS_CFCN, l, col)); }
+      else a.cfcn_t[n] = a.S(CS_OUT + 7, l, col);
+    }
+    if (bad) *a.flag = 1;
+  }
+};
+
+inline void run_cloud(Exec& ex, int what, const CldArgs& a) {      // what: -3 cfcn scatter, -2 cfcn gather, -1 set, 0 nl, 1 tl, 2 ad
   const Rect R{0, a.n - 1, 0, 0};
   if (a.n <= 0) return;
-  if (what == -1) for_points(ex, R, 1, CldSetFn{a, 0}, "cloud_set");
+  if (what == -3) for_points(ex, R, 1, CldCfcnFn{a, 1}, "cloud_cfcn_scatter");
+  else if (what == -2) for_points(ex, R, 1, CldCfcnFn{a, 0}, "cloud_cfcn_gather");
+  else if (what == -1) for_points(ex, R, 1, CldSetFn{a, 0}, "cloud_set");
   else if (what == MODE_NL) for_points(ex, R, 1, CldSetFn{a, 1}, "cloud.nl");
   else if (what == MODE_TL) for_points(ex, R, 1, CldTlFn{a}, "cloud.tl");
   else for_points(ex, R, 1, CldAdFn{a}, "cloud.ad");

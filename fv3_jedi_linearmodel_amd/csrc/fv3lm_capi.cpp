@@ -266,6 +266,9 @@ int fv3lm_cloud_create(fv3lm_handle* h, const fv3lm_cloud_params* p, int iqi, in
   static_assert(sizeof(fv3lm_cloud_params) == sizeof(CldParams), "fv3lm_cloud_params and CldParams must agree");
   return physics_call(h, "fv3lm_cloud_create", [&](Physics& p_) { return p_.cloud_create(reinterpret_cast<const CldParams*>(p), iqi, iql); });
 }
+int fv3lm_cloud_bind_cfcn(fv3lm_handle* h, int iqc) {
+  return physics_call(h, "fv3lm_cloud_bind_cfcn", [&](Physics& p_) { return p_.cloud_bind_cfcn(iqc); });
+}
 int fv3lm_cloud_set(fv3lm_handle* h, int slot, const double* qls, const double* qcn, const double* cfcn, const double* khl, const double* khu) {
   return physics_call(h, "fv3lm_cloud_set", [&](Physics& p_) { return p_.cloud_set(slot, qls, qcn, cfcn, khl, khu); });
 }

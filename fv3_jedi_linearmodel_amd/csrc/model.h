@@ -78,8 +78,16 @@ struct Model {
     return p.sticky_clean();
   }
 
-  // ipert_to_zero (fv3jedi_lm_mod.F90:242-253): of ua, va, cfcn only cfcn lives on the device, with the cloud feature
-  void clear_cfcn() { if (!p.cld.mem.empty()) dev_zero(ex, p.cld.cfcn, p.ncol() * d.g.npz * 8); }
+  // ipert_to_zero (fv3jedi_lm_mod.F90:242-253): of ua, va, cfcn only cfcn lives on the device, with the cloud feature.  Bound to a tracer
+  // (fv3lm_cloud_bind_cfcn) it is that tracer's perturbation, cleared on its whole padded planes: the adjoint's halo enters step_ad as
+  // zeros, as pert_to_fv3 leaves it (fv3jedi_lm_dynamics_mod.F90:878).  Nothing clears it between the dynamics and the moist half, so the
+  // tangent the transport leaves in it reaches CLOUD_DRIVER_D (fv3jedi_lm_moist_mod.F90:438) and the adjoint CLOUD_DRIVER_B leaves in it
+  // (:616) reaches FV_DYNAMICS_BWD
+  void clear_cfcn() {
+    if (p.cld.mem.empty()) return;
+    if (p.cld.iqc) dev_zero(ex, d.q[(size_t)p.cld.iqc - 1].p, d.n3 * 8);
+    else dev_zero(ex, p.cld.cfcn, p.ncol() * d.g.npz * 8);
+  }
   bool dynamics_ok() { const std::string e = pending_failure(d); if (e.empty()) return true; d.err = e; return false; }
 
   // fv3lm_lm_step: step_tl (fv3jedi_lm_mod.F90:161-172) or step_ad (:176-187) on the resident perturbation.  The physics halves in the

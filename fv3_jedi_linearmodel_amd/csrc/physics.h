@@ -44,6 +44,8 @@ struct Physics {
   } conv;
   struct Cloud {      // one slot per convection slot
     DevList mem; int iqi = 0, iql = 0; CldParams p;
+    int iqc = 0;                    // fv3lm_cloud_bind_cfcn: cfcn is tracer iqc of the dycore (0: the feature's own array below)
+    bool was_set = false;           // a slot has been set: too late to bind
     std::vector<double*> slot; std::vector<char> set;
     ColWork w{}; double* cfcn = nullptr;
   } cld;
@@ -408,24 +410,41 @@ struct Physics {
     if (!slot_set(who, "the convection slot", conv.set, slot, "fv3lm_convection_set")) return false;
     return !need_set || slot_set(who, "slot", cld.set, slot, "fv3lm_cloud_set");
   }
+  // fv3lm_cloud_bind_cfcn: from here on the convective cloud fraction is tracer iqc of the dycore, as the reference's fifth tracer
+  // (fv3jedi_lm_dynamics_mod.F90:159-163, :769, :831, :878, :912): the trajectory half is the trajectory cfcn, the perturbation half is
+  // cfcn' or its adjoint, and the dynamics carries both.  The feature's own array stays allocated and is no longer read.
+  bool cloud_bind_cfcn(int iqc) {
+    const char* who = "fv3lm_cloud_bind_cfcn";
+    if (cld.mem.empty()) return no(who, "call fv3lm_cloud_create first");
+    if (cld.iqc) return no(who, "already bound to tracer " + std::to_string(cld.iqc));
+    if (iqc < 2 || iqc > d.nq) return no(who, "iqc = " + std::to_string(iqc) + " outside 2..nq = 2.." + std::to_string(d.nq));
+    if (iqc == cld.iqi || iqc == cld.iql)
+      return no(who, "iqc = " + std::to_string(iqc) + " is the tracer of cloud " + (iqc == cld.iqi ? "ice (iqi)" : "liquid (iql)") + ": cfcn is a tracer of its own");
+    if (cld.was_set) return no(who, "a cloud slot has been set: bind after fv3lm_cloud_create, before the first fv3lm_cloud_set");
+    cld.iqc = iqc;
+    return true;
+  }
   CldArgs cloud_args(int slot) {
     CldArgs a;
     static_cast<ColView&>(a) = col_view(cld.slot[(size_t)slot], CLD_NS); static_cast<ColWork&>(a) = cld.w;
     a.rslot = conv.slot[(size_t)slot]; a.mst = conv.mst;
     a.pt = ex.sh(d.f("pt")); a.delp = ex.sh(d.f("delp")); a.q1 = ex.sh(d.q[0]);
     a.qi = ex.sh(d.q[(size_t)cld.iqi - 1]); a.ql = ex.sh(d.q[(size_t)cld.iql - 1]);
-    a.cfcn = cld.cfcn; a.src = conv.src; a.tbl = conv.tbl; a.p = cld.p;
+    a.cfcn = cld.cfcn; a.cfcn_t = nullptr; a.cf_fld = 0;
+    if (cld.iqc) { const Fld qc = ex.sh(d.q[(size_t)cld.iqc - 1]); a.cfcn = qc.p; a.cfcn_t = qc.t; a.cf_fld = 1; }
+    a.src = conv.src; a.tbl = conv.tbl; a.p = cld.p;
     a.dt = d.bdt; a.ptop = d.opt.ptop; a.p00k = std::pow(1.0e5, d.opt.akap);
     return a;
   }
   // the slot takes QLS QCN cfcn khl khu from the host, PLE from the resident delp and everything else from the convection slot of the same
-  // number; the split, the fractions, CLOUD_DRIVER in values and (do_phy_mst = 2) the per-cell switch
+  // number; the split, the fractions, CLOUD_DRIVER in values and (do_phy_mst = 2) the per-cell switch.  With a bound tracer a null cfcn
+  // takes the resident trajectory of that tracer (set_ltraj :720)
   bool cloud_set(int slot, const double* qls, const double* qcn, const double* cfcn, const double* khl, const double* khu) {
     const char* who = "fv3lm_cloud_set";
     if (!cloud_slot_ok(who, slot, false)) return false;
-    if (!qls || !qcn || !cfcn || !khl || !khu) return no(who, "null array");
+    if (!qls || !qcn || (!cfcn && !cld.iqc) || !khl || !khu) return no(who, "null array");
     const size_t nc = ncol(); const int lm = g.npz;
-    if (!all_finite(qls, nc * lm) || !all_finite(qcn, nc * lm) || !all_finite(cfcn, nc * lm)) return no(who, "a value that is not finite in QLS, QCN or cfcn");
+    if (!all_finite(qls, nc * lm) || !all_finite(qcn, nc * lm) || (cfcn && !all_finite(cfcn, nc * lm))) return no(who, "a value that is not finite in QLS, QCN or cfcn");
     for (size_t n = 0; n < nc; ++n) {
       if (!all_finite(khl + n, 1) || !all_finite(khu + n, 1)) return no(who, "a value that is not finite in khl or khu");
       const long l = std::lround(khl[n]), u = std::lround(khu[n]);
@@ -434,11 +453,14 @@ struct Physics {
     cld.set[(size_t)slot] = 0;
     CldArgs a = cloud_args(slot);
     std::vector<double> buf((size_t)(lm + 1) * nc, 0.);
-    pack_columns(&a.S(CS_QILS, 0, 0), qls, buf); pack_columns(&a.S(CS_QICN, 0, 0), qcn, buf); pack_columns(&a.S(CS_CFCN, 0, 0), cfcn, buf);
+    pack_columns(&a.S(CS_QILS, 0, 0), qls, buf); pack_columns(&a.S(CS_QICN, 0, 0), qcn, buf);
+    if (cfcn) pack_columns(&a.S(CS_CFCN, 0, 0), cfcn, buf);
     std::vector<double> kh(2 * nc);
     for (size_t n = 0; n < nc; ++n) { kh[n] = (double)std::lround(khl[n]); kh[nc + n] = (double)std::lround(khu[n]); }      // nint
     h2d(ex, &a.SC(CSC_KHL, 0), kh.data(), kh.size() * 8);
     clear_flags(cld.w.flag);
+    cld.was_set = true;
+    if (!cfcn) for_batches(nc, (size_t)cld.w.nb, [&](int first, int n) { a.first = first; a.n = n; run_cloud(ex, -2, a); });
     for_batches(nc, (size_t)cld.w.nb, [&](int first, int n) { a.first = first; a.n = n; run_cloud(ex, -1, a); });
     if (read_flags(cld.w.flag)[0]) return no(who, "a value that is not finite in the resident trajectory (slot " + std::to_string(slot) + " is not set)");
     if (!sticky_clean()) return false;
@@ -463,10 +485,15 @@ struct Physics {
     if (!cfcn) return no(who, "null array");
     const size_t n3c = ncol() * g.npz;
     if (put && !all_finite(cfcn, n3c)) return no(who, "a value that is not finite");
+    if (cld.iqc) {      // bound: is..ie x js..je of the tracer's perturbation; a put leaves zeros outside, as pert_to_fv3 does
+      const Fld& qc = d.q[(size_t)cld.iqc - 1];
+      if (put) d.compact_in(qc, 1, cfcn); else d.compact_out(qc, 1, cfcn);
+      return sticky_clean();
+    }
     if (put) h2d(ex, cld.cfcn, cfcn, n3c * 8); else d2h(ex, cfcn, cld.cfcn, n3c * 8);
     return true;
   }
-  // every column, in dense batches.  The slot is read only; mode 0 writes the trajectory tracers iqi, iql
+  // every column, in dense batches.  The slot is read only; mode 0 writes the trajectory tracers iqi, iql and, bound, CF_con to iqc
   bool cloud_run(int slot, int mode) {
     const char* who = "fv3lm_cloud";
     if (!cloud_slot_ok(who, slot, false)) return false;
@@ -475,6 +502,7 @@ struct Physics {
     CldArgs a = cloud_args(slot);
     if (mode == MODE_AD) clear_flags(cld.w.flag);
     for_batches(ncol(), (size_t)cld.w.nb, [&](int first, int n) { a.first = first; a.n = n; run_cloud(ex, mode, a); });
+    if (mode == MODE_NL && cld.iqc) for_batches(ncol(), (size_t)cld.w.nb, [&](int first, int n) { a.first = first; a.n = n; run_cloud(ex, -3, a); });
     if (mode == MODE_AD && read_flags(cld.w.flag)[1]) return no(who, "the tape of a segment overflowed (CLD_TAPE); the adjoint fields are not valid");
     return sticky_clean();
   }

@@ -291,6 +291,19 @@ int fv3lm_convection_table(fv3lm_handle* h, double* table, double* constants);
  *   fv3lm_cloud_get: out8 = theta, q, QI_ls, QL_ls, QI_con, QL_con, CF_ls, CF_con after CLOUD_DRIVER in values; frac4 = ILSF ICNF LLSF
  *       LCNF; pertmod = the switch, one int a cell (all 1 for do_phy_mst = 1).  NULL is allowed for each.
  *   fv3lm_cloud_cfcn: the perturbation's convective cloud fraction (npz deep), which the feature owns on the device: put = 0 reads, 1 writes.
+ *   fv3lm_cloud_bind_cfcn: opt-in, after fv3lm_cloud_create and before the first fv3lm_cloud_set.  From then on the convective cloud
+ *       fraction of this handle IS tracer iqc of the dycore (1-based, 2..nq, neither iqi nor iql), as the reference's fifth tracer with
+ *       do_phy_mst /= 0 (fv3jedi_lm_dynamics_mod.F90:159-163, :769, :831, :878, :912): the trajectory half is the trajectory cfcn, the
+ *       perturbation half is cfcn' or its adjoint, and the dynamics transports both.  The tangent and adjoint kernels then read and write
+ *       that tracer's perturbation in place of the feature's array.  fv3lm_cloud_set accepts cfcn = NULL and takes the resident trajectory
+ *       of tracer iqc (set_ltraj :720; a non-NULL array is used as before); fv3lm_cloud(slot, 0) also writes CF_con to the trajectory of
+ *       tracer iqc on is..ie x js..je (step_nl :388); fv3lm_cloud_cfcn moves is..ie x js..je of the tracer's perturbation (a put leaves
+ *       zeros outside, as fv3lm_pert_to_fv3 does); fv3lm_lm_step clears the tracer's perturbation, whole padded planes, before and after
+ *       a step and nothing clears it in between, so the tangent the transport of the trajectory's cfcn leaves there reaches
+ *       CLOUD_DRIVER_D (fv3jedi_lm_moist_mod.F90:438) and the adjoint CLOUD_DRIVER_B leaves there (:616) reaches FV_DYNAMICS_BWD.  A
+ *       handle that never binds keeps cfcn out of the dynamics (a host that owns cfcn routes it itself).  Refused with a message, the
+ *       handle left as it was: before fv3lm_cloud_create; a second bind; iqc outside 2..nq or equal to iqi or iql; after a cloud slot
+ *       has been set.
  *   fv3lm_cloud: every column.  mode 0: CLOUD_DRIVER in values on copies of the slot; qi = QI_ls + QI_con and ql = QL_ls + QL_con go to
  *       the resident trajectory tracers iqi, iql (CF_con is what get returns); T and qv are not touched.  1: T -> theta by p00^kappa / pk,
  *       qi and ql split by the fractions, cflsp = 0, cfcn as put, the four sources as fv3lm_convection(1) left them; after the driver
@@ -307,6 +320,7 @@ int fv3lm_convection_table(fv3lm_handle* h, double* table, double* constants);
 typedef struct { double r[57]; } fv3lm_cloud_params;
 void fv3lm_cloud_default_params(fv3lm_cloud_params* p, int im);
 int fv3lm_cloud_create(fv3lm_handle* h, const fv3lm_cloud_params* p, int iqi, int iql);
+int fv3lm_cloud_bind_cfcn(fv3lm_handle* h, int iqc);
 int fv3lm_cloud_set(fv3lm_handle* h, int slot, const double* qls, const double* qcn, const double* cfcn, const double* khl, const double* khu);
 int fv3lm_cloud_get(fv3lm_handle* h, int slot, double* const* out8, double* const* frac4, int* pertmod);
 int fv3lm_cloud_cfcn(fv3lm_handle* h, int put, double* cfcn);
@@ -324,7 +338,9 @@ int fv3lm_cloud(fv3lm_handle* h, int slot, int mode);
  *   fv3lm_lm_traj_load: the slot back; the handle is then as after fv3lm_traj_to_fv3 of the same host arrays, bit for bit (halos, D-grid
  *       edge rows, halo of phis; pe peln pk pkz computed again from delp as the upload does).  Neither call touches the perturbation.
  *   fv3lm_lm_step: mode 1 tangent, 2 adjoint, on the resident perturbation.  ipert_to_zero (:167, :170, :182, :185, :242-253) clears the
- *       device's cfcn perturbation before and after either (where the cloud feature exists).
+ *       device's cfcn perturbation before and after either (where the cloud feature exists).  Without fv3lm_cloud_bind_cfcn that array is
+ *       the cloud feature's own and the dynamics never sees it: the cloud tangent starts from cfcn' = 0 and the cfcn adjoint it leaves is
+ *       dropped, which the reference does not do; with it, cfcn is a tracer and the coupling is the reference's.
  *           tangent (:161-172; physics fv3jedi_lm_physics_mod.F90:121-122)
  *               do_dyn: traj_load(slot) ; fv3lm_step_tl      do_phy_mst: convection(slot, 1) ; cloud(slot, 1)      do_phy_trb: turbulence(slot, 1)
  *           adjoint (:176-187; physics :137-138)
