@@ -271,6 +271,86 @@ def tiled_tables(n, layout):
 
 
 # --------------------------------------------------------------------------------------------- grid
+_TABLE_CACHE = {}
+
+
+def _cached_table(n, kind):
+    if (n, kind) not in _TABLE_CACHE:
+        _TABLE_CACHE[(n, kind)] = exchange_table(n, EXCHANGE_FIELDS[kind])
+    return _TABLE_CACHE[(n, kind)]
+
+
+def _exchange_scalars(n, kind, f0, f1=None):
+    """mpp_update_domains of one metric plane or of a SCALAR_PAIR of them [6, pj, pj] (tools/fv_grid_tools_nlm.F90:686, :863, :898,
+    model/fv_grid_utils_nlm.F90:743-746): the data motion of the table of that kind without its signs -- every halo element outside the
+    corner squares takes the neighbour's own value, the pair swapped where the contact is rotated."""
+    tab = _cached_table(n, kind)
+    fl = [f0.reshape(6, -1)] + ([f1.reshape(6, -1)] if f1 is not None else [])
+    vals = np.empty(len(tab))
+    for sf in range(len(fl)):
+        k = tab[:, 3] == sf
+        vals[k] = fl[sf][tab[k, 4], tab[k, 5]]
+    for df in range(len(fl)):
+        k = tab[:, 0] == df
+        fl[df][tab[k, 1], tab[k, 2]] = vals[k]
+
+
+def _P(i, j):
+    """element (i, j) (Fortran indices) of every face of a padded plane"""
+    return (slice(None), j + NG - 1, i + NG - 1)
+
+
+def _fill_corner_squares(kind, n, x, y=None):
+    """fill_corners (tools/fv_mp_nlm_mod.F90) as grid_init applies it to the metric planes: the corner squares take the values the
+    rows of the face would meet if they went on across the west / east neighbour ("B": one corner-point plane, FILL=XDir, :1057-1064;
+    "D": dx on x with dy on y, :1278-1301; "A": dxa with dya, :1454-1469; "C": dxc with dyc, :1390-1405)."""
+    npx = n + 1
+    rng = [(i, j) for j in range(1, NG + 1) for i in range(1, NG + 1)]
+    if kind == "B":
+        for i, j in rng:
+            x[_P(1 - i, 1 - j)] = x[_P(1 - j, i + 1)]; x[_P(1 - i, npx + j)] = x[_P(1 - j, npx - i)]
+            x[_P(npx + i, 1 - j)] = x[_P(npx + j, i + 1)]; x[_P(npx + i, npx + j)] = x[_P(npx + j, npx - i)]
+        return
+    # offsets of the staggered targets: (east shift of x, north shift of x, east shift of y, north shift of y, source shifts)
+    if kind == "D":
+        for i, j in rng:
+            x[_P(1 - i, 1 - j)] = y[_P(1 - j, i)]; x[_P(1 - i, npx + j)] = y[_P(1 - j, npx - i)]
+            x[_P(n + i, 1 - j)] = y[_P(npx + j, i)]; x[_P(n + i, npx + j)] = y[_P(npx + j, npx - i)]
+        for i, j in rng:
+            y[_P(1 - i, 1 - j)] = x[_P(j, 1 - i)]; y[_P(1 - i, n + j)] = x[_P(j, npx + i)]
+            y[_P(npx + i, 1 - j)] = x[_P(npx - j, 1 - i)]; y[_P(npx + i, n + j)] = x[_P(npx - j, npx + i)]
+    elif kind == "A":
+        for i, j in rng:
+            x[_P(1 - i, 1 - j)] = y[_P(1 - j, i)]; x[_P(1 - i, n + j)] = y[_P(1 - j, npx - i)]
+            x[_P(n + i, 1 - j)] = y[_P(n + j, i)]; x[_P(n + i, n + j)] = y[_P(n + j, npx - i)]
+        for i, j in rng:
+            y[_P(1 - j, 1 - i)] = x[_P(i, 1 - j)]; y[_P(1 - j, n + i)] = x[_P(i, n + j)]
+            y[_P(n + j, 1 - i)] = x[_P(npx - i, 1 - j)]; y[_P(n + j, n + i)] = x[_P(npx - i, n + j)]
+    elif kind == "C":
+        for i, j in rng:
+            x[_P(1 - i, 1 - j)] = y[_P(j, 1 - i)]; x[_P(1 - i, n + j)] = y[_P(j, npx + i)]
+            x[_P(npx + i, 1 - j)] = y[_P(npx - j, 1 - i)]; x[_P(npx + i, n + j)] = y[_P(npx - j, npx + i)]
+        for i, j in rng:
+            y[_P(1 - i, 1 - j)] = x[_P(1 - j, i)]; y[_P(1 - i, npx + j)] = x[_P(1 - j, npx - i)]
+            y[_P(n + i, 1 - j)] = x[_P(npx + j, i)]; y[_P(n + i, npx + j)] = x[_P(npx + j, npx - i)]
+
+
+def _transport_sines(m, n, names):
+    """The sin_sg / cos_sg entries of corner-halo cells that transport reads (model/fv_grid_utils_nlm.F90:363-391 for the sines, before
+    the edge sines are formed, and :571-627 for both, after the corner halo has been poisoned): the outward edge of the halo cells
+    along each face edge takes the angle the neighbour across the corner sees there.  names: ("sin_sg",) or ("sin_sg", "cos_sg")."""
+    npx = n + 1
+    first = names == ("sin_sg",)
+    for nm in names:
+        q = {k: m["%s%d" % (nm, k)] for k in (1, 2, 3, 4)}
+        for k in (0, 1, 2):
+            q[3][_P(0, -k)] = q[2][_P(-k, 1)]; q[4][_P(-k, 0)] = q[1][_P(1, -k)]                    # sw
+            q[3][_P(0, npx + k)] = q[4][_P(-k, n)]                                                  # nw
+            q[2][_P(-k, npx)] = q[1][_P(1, npx - k if first else npx + k)]                          # (:374 reads npx + i, :593 npy - i)
+            q[1][_P(npx, -k)] = q[2][_P(npx + k, 1)]; q[4][_P(npx + k, 0)] = q[3][_P(n, -k)]        # se
+            q[1][_P(npx, npx + k)] = q[4][_P(npx + k, n)]; q[2][_P(npx + k, npx)] = q[3][_P(n, npx + k)]    # ne
+
+
 def _norm(v):
     return v / np.linalg.norm(v, axis=-1, keepdims=True)
 
@@ -307,7 +387,7 @@ def cube_corner_points(n):
     for tile, (nrm, e1, e2) in FRAMES.items():
         pts = nrm[None, None, :] + t[None, :, None] * e1[None, None, :] + t[:, None, None] * e2[None, None, :]
         P[tile - 1, NG:NG + n + 1, NG:NG + n + 1] = _norm(pts)
-    tab = exchange_table(n, [("corner", "s")])
+    tab = _cached_table(n, "corner")
     flat = P.reshape(6, pj * pj, 3)
     flat[tab[:, 1], tab[:, 2]] = flat[tab[:, 4], tab[:, 5]]
     # corner regions: x-direction view (see _fold) — real points of the third face at that vertex
@@ -319,10 +399,25 @@ def cube_corner_points(n):
     return P
 
 
-def cubed_sphere_metrics(n, radius=6371.0e3, omega=7.292e-5):
+EDGE_FORMS = ("extended", "reference")
+
+
+def cubed_sphere_metrics(n, radius=6371.0e3, omega=7.292e-5, edge_forms="extended"):
     """All metric planes of include/fv3lm.h for the six faces, [6, pj, pi] each, plus da_min, da_min_c,
     the a2b edge weights edge_w/e/s/n [6, pj] and the extrap_corner coefficients [6, 4, 3]
-    (definitions: NLM/fv_grid_utils_nlm.F90:455-745, a2b_edge_tlm.F90:1478-1487)."""
+    (definitions: NLM/fv_grid_utils_nlm.F90:455-745, a2b_edge_tlm.F90:1478-1487).
+
+    edge_forms: how the planes are completed along the face edges, in the halo and in the corner squares.
+    "extended" (the default, and what the benchmark has always run on): every plane is the geometry of the face's own rows and columns
+    continued across the cube edge -- dxc, dyc, area_c measured across the bend, the a2b edge weights taken between the mid-points of
+    the edge segments, corner squares in the x-direction view for both directions.
+    "reference": what grid_init / grid_utils_init hold there (tools/fv_grid_tools_nlm.F90:648-937, model/fv_grid_utils_nlm.F90:359-627,
+    :700-746, :1105-1214): halo = the neighbour's own value, corner squares by fill_corners, dxc / dyc / area_c along an edge twice (at
+    a vertex three times) the part inside the face, sin_sg / cos_sg of the corner-halo cells as transport reads them, edge weights
+    between the points where the lines joining the cell centres cross the edge.  tests/test_face_metrics.py holds this form to a
+    restatement of the Fortran entry by entry; the tests run on it (tests/common.py)."""
+    assert edge_forms in EDGE_FORMS, edge_forms
+    ref = edge_forms == "reference"
     from .grid import METRIC_NAMES
     pj = n + 2 * NG + 1
     P = cube_corner_points(n)                                   # corners (i,j) -> index [j+2, i+2]
@@ -364,6 +459,32 @@ def cubed_sphere_metrics(n, radius=6371.0e3, omega=7.292e-5):
     for nm in ("dx", "dy", "dxa", "dya", "dxc", "dyc", "area"):
         a = m[nm]; a[a == 0.0] = a[a > 0].mean()
     area_c[area_c == 0.0] = area_c[area_c > 0].mean()
+    # What grid_init does along the face edges and in the corner squares (tools/fv_grid_tools_nlm.F90): the halo of every plane holds
+    # the neighbour's own value, the corner squares what fill_corners puts there, and along a face edge dxc, dyc and area_c are twice
+    # (at a vertex three times) the part inside the face (:767-859) -- not the distance / area across the bend of the cube edge.
+    e1i, eni = NG, NG + n                                        # plane indices of i = 1 and i = npx
+    if ref:
+        Jc, Jm, Jn = slice(NG, NG + n + 1), slice(NG - 1, NG + n), slice(NG, NG + n)       # j = 1..npy, the same - 1, 1..npy-1
+        _fill_corner_squares("D", n, m["dx"], m["dy"]); _fill_corner_squares("A", n, m["dxa"], m["dya"])
+        dxc, dyc = m["dxc"], m["dyc"]
+        dxc[:, :, 0] = dxc[:, :, 1]; dxc[:, :, -1] = dxc[:, :, -2]; dyc[:, 0, :] = dyc[:, 1, :]; dyc[:, -1, :] = dyc[:, -2, :]       # :738-751
+        dxc[:, Jn, e1i] = 2.0 * radius * _dist(mw[:, Jn, e1i], ctr[:, Jn, e1i]); dxc[:, Jn, eni] = 2.0 * radius * _dist(ctr[:, Jn, eni - 1], mw[:, Jn, eni])
+        dyc[:, e1i, Jn] = 2.0 * radius * _dist(ms[:, e1i, Jn], ctr[:, e1i, Jn]); dyc[:, eni, Jn] = 2.0 * radius * _dist(ctr[:, eni - 1, Jn], ms[:, eni, Jn])
+        _exchange_scalars(n, "cvec", dxc, dyc); _fill_corner_squares("C", n, dxc, dyc)
+        r2 = radius ** 2
+        area_c[:, Jc, e1i] = 2.0 * r2 * _quad_area(mw[:, Jm, e1i], ctr[:, Jm, e1i], ctr[:, Jc, e1i], mw[:, Jc, e1i])
+        area_c[:, Jc, eni] = 2.0 * r2 * _quad_area(ctr[:, Jm, eni - 1], mw[:, Jm, eni], mw[:, Jc, eni], ctr[:, Jc, eni - 1])
+        area_c[:, e1i, Jc] = 2.0 * r2 * _quad_area(ms[:, e1i, Jm], ms[:, e1i, Jc], ctr[:, e1i, Jc], ctr[:, e1i, Jm])
+        area_c[:, eni, Jc] = 2.0 * r2 * _quad_area(ctr[:, eni - 1, Jm], ctr[:, eni - 1, Jc], ms[:, eni, Jc], ms[:, eni, Jm])
+        # the four vertices: the kite between the vertex, the two edge mid-points next to it and the centre of the cell inside the face.
+        # (:841 closes the south-east one with the centre of the neighbour's cell, agrid(npx, 1), which gives a negative area; the four
+        # are taken alike here.)
+        for (vi, vj, ci, cj) in ((e1i, e1i, e1i, e1i), (eni, e1i, eni - 1, e1i), (eni, eni, eni - 1, eni - 1), (e1i, eni, e1i, eni - 1)):
+            mi, mj = (vi if vi == e1i else vi - 1), (vj if vj == e1i else vj - 1)       # the edge mid-points on the face's side of the vertex
+            area_c[:, vj, vi] = 3.0 * r2 * _quad_area(P[:, vj, vi], ms[:, vj, mi], ctr[:, cj, ci], mw[:, mj, vi])
+        _exchange_scalars(n, "corner", area_c); _fill_corner_squares("B", n, area_c)
+        _exchange_scalars(n, "cell", m["area"])
+        _transport_sines(m, n, ("sin_sg",))
     for nm in ("dx", "dy", "dxa", "dya", "dxc", "dyc"):
         m["r" + nm] = 1.0 / m[nm]
     m["rarea"] = 1.0 / m["area"]; m["rarea_c"] = 1.0 / area_c
@@ -383,11 +504,12 @@ def cubed_sphere_metrics(n, radius=6371.0e3, omega=7.292e-5):
     m["rsin_v"] = 1.0 / np.maximum(tiny, m["sina_v"] ** 2)
     m["rsin2"] = 1.0 / np.maximum(tiny, m["sin_sg5"] ** 2)
     m["rsina"] = 1.0 / np.maximum(tiny, m["sina"] ** 2)
-    e1i, eni = NG, NG + n                                        # plane indices of i=1 and i=npx
     big = 1.0e30
     m["rsina"][:, [e1i, eni], :] = big; m["rsina"][:, :, [e1i, eni]] = big            # :527-538 (face edges)
     m["rsin_u"][:, :, [e1i, eni]] = 1.0 / m["sina_u"][:, :, [e1i, eni]]                 # :540-547
     m["rsin_v"][:, [e1i, eni], :] = 1.0 / m["sina_v"][:, [e1i, eni], :]                 # :549-556
+    if ref:
+        _transport_sines(m, n, ("sin_sg", "cos_sg"))
     # divergence / del-n damping metrics (:700-725)
     m["divg_u"] = m["sina_v"] * m["dyc"] / m["dx"]; m["del6_u"] = m["sina_v"] * m["dx"] / m["dyc"]
     m["divg_v"] = m["sina_u"] * m["dxc"] / m["dy"]; m["del6_v"] = m["sina_u"] * m["dy"] / m["dxc"]
@@ -399,25 +521,35 @@ def cubed_sphere_metrics(n, radius=6371.0e3, omega=7.292e-5):
         f = 0.5 * (m["sin_sg1"][:, :, col] + m["sin_sg3"][:, :, col - 1])
         m["divg_v"][:, :, col] = f * m["dxc"][:, :, col] / m["dy"][:, :, col]
         m["del6_v"][:, :, col] = f * m["dy"][:, :, col] / m["dxc"][:, :, col]
+    if ref:
+        _exchange_scalars(n, "cvec", m["divg_v"], m["divg_u"]); _exchange_scalars(n, "cvec", m["del6_v"], m["del6_u"])       # :743-746
     # Coriolis
     latc = np.arcsin(np.clip(ctr[..., 2], -1, 1)); latk = np.arcsin(np.clip(P[..., 2], -1, 1))
     m["f0"][sl] = 2.0 * omega * np.sin(latc); m["fC"] = 2.0 * omega * np.sin(latk)
     inner = (slice(None), slice(NG, NG + n), slice(NG, NG + n))
     da_min = float(m["area"][inner].min())
     da_min_c = float(area_c[:, NG:NG + n + 1, NG:NG + n + 1].min())
-    # a2b_ord4 edge weights (fv_grid_utils_nlm.F90 edge_w/e/s/n: linear interpolation weights of the edge
-    # mid-points to the corner) and extrap_corner coefficients x1/(x2-x1)
+    # a2b_ord4 edge weights (fv_grid_utils_nlm.F90 edge_factors, :1145-1211): the value a2b_ord4 forms on the edge between the cell
+    # centres (i-1, j) and (i, j) sits where the line joining them crosses the edge -- mid_pt_sphere of the two centres, which on the
+    # skewed cells near a vertex is not the mid-point of the edge segment -- and edge_w(j) is the linear weight of the (j-1)-th of
+    # those points at the corner point between them.  Also the extrap_corner coefficients x1/(x2-x1).
     edge = np.zeros((6, 4, pj))                                  # order w, e, s, n; index by plane position
-    def ew(pa, pb, pc):                                          # corner pb between mid-points pa, pc: weight of pa
+    def ew(pa, pb, pc):                                          # corner pb between the crossing points pa, pc: weight of pa
         d1, d2 = _dist(pa, pb), _dist(pb, pc)
         return d2 / (d1 + d2)
+    # ("extended": between the mid-points of the edge segments instead.)
+    if ref:
+        xw, xe = _norm(ctr[:, :, e1i - 1] + ctr[:, :, e1i]), _norm(ctr[:, :, eni - 1] + ctr[:, :, eni])      # [6, pj-1, 3] along j
+        xs, xn = _norm(ctr[:, e1i - 1, :] + ctr[:, e1i, :]), _norm(ctr[:, eni - 1, :] + ctr[:, eni, :])      # along i
+    else:
+        xw, xe, xs, xn = mw[:, :, e1i], mw[:, :, eni], ms[:, e1i, :], ms[:, eni, :]
     for t in range(6):
         for j in range(2, n + 1):                                # qout(1,j) = edge_w(j)*q2(j-1) + (1-edge_w(j))*q2(j)
             jj = j + NG - 1
-            edge[t, 0, jj] = ew(mw[t, jj - 1, e1i], P[t, jj, e1i], mw[t, jj, e1i])
-            edge[t, 1, jj] = ew(mw[t, jj - 1, eni], P[t, jj, eni], mw[t, jj, eni])
-            edge[t, 2, jj] = ew(ms[t, e1i, jj - 1], P[t, e1i, jj], ms[t, e1i, jj])
-            edge[t, 3, jj] = ew(ms[t, eni, jj - 1], P[t, eni, jj], ms[t, eni, jj])
+            edge[t, 0, jj] = ew(xw[t, jj - 1], P[t, jj, e1i], xw[t, jj])
+            edge[t, 1, jj] = ew(xe[t, jj - 1], P[t, jj, eni], xe[t, jj])
+            edge[t, 2, jj] = ew(xs[t, jj - 1], P[t, e1i, jj], xs[t, jj])
+            edge[t, 3, jj] = ew(xn[t, jj - 1], P[t, eni, jj], xn[t, jj])
     ecorner = np.zeros((6, 4, 3))
     def ec(p0, p1, p2):
         x1, x2 = _dist(p1, p0), _dist(p2, p0)

@@ -12,13 +12,24 @@ def relerr(a, b):
     return float(np.max(np.abs(a - b)) / (s if s > 0 else 1.0))
 
 
+def _apply_metrics_hook(hook, metrics, edge, ecorner):
+    if hook is None:
+        return metrics, edge, ecorner
+    out = hook(metrics, edge, ecorner)
+    metrics, edge, ecorner = out if out is not None else (metrics, edge, ecorner)
+    return {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in metrics.items()}, np.ascontiguousarray(edge), np.ascontiguousarray(ecorner)
+
+
 class Case:
     def __init__(self, nx=12, ny=12, npz=8, n_split=2, k_split=1, dt=1800.0, backend="hip", seed=20250114, oracle=False, nq=0,
-                 face=None, **optkw):
+                 face=None, metrics_hook=None, edge_forms="extended", **optkw):
         """face=None: the doubly-periodic tile with no cube edge.  face=t (0..5): one whole face of a C<nx> cube with
         the real gnomonic metrics of that face and arbitrary smooth halo data (kernel-group tests).
         tau=, rf_cutoff=: Rayleigh damping of the upper layers (fv3lm_set_rayleigh; off by default).
-        levels=(ak, bk): hybrid coefficients [npz+1] in place of grid.hybrid_levels; the state's delp follows them at the same ps."""
+        levels=(ak, bk): hybrid coefficients [npz+1] in place of grid.hybrid_levels; the state's delp follows them at the same ps.
+        metrics_hook (face cases): callable(metrics, edge, ecorner) applied to the metric dict [1, pj, pi] and the a2b edge data of the
+        face before the library instance (and the oracle) are created; it changes them in place or returns the three to use instead.
+        edge_forms: cube.cubed_sphere_metrics(edge_forms=...), "extended" or "reference"."""
         self.nx, self.ny, self.npz = nx, ny, npz
         self.tau, self.rf_cutoff = optkw.pop("tau", 0.0), optkw.pop("rf_cutoff", 0.0)
         levels = optkw.pop("levels", None)
@@ -30,10 +41,11 @@ class Case:
         else:
             from . import cube
             assert nx == ny
-            m6, self.da_min, self.da_min_c, edge, ecorner, geo = cube.cubed_sphere_metrics(nx)
+            m6, self.da_min, self.da_min_c, edge, ecorner, geo = cube.cubed_sphere_metrics(nx, edge_forms=edge_forms)
             self.metrics = {k: np.ascontiguousarray(v[face:face + 1]) for k, v in m6.items()}
             self.edge, self.ecorner = np.ascontiguousarray(edge[face:face + 1]), np.ascontiguousarray(ecorner[face:face + 1])
             self.c2l = np.ascontiguousarray(geo["c2l"][face:face + 1])
+            self.metrics, self.edge, self.ecorner = _apply_metrics_hook(metrics_hook, self.metrics, self.edge, self.ecorner)
         self.traj, self.phis, self.ak, self.bk = G.synthetic_state(nx, ny, npz, self.opt, seed=seed)
         if levels is not None:
             ak, bk = (np.array(x, dtype=np.float64) for x in levels)
@@ -101,12 +113,16 @@ class CubeCase:
     case are then the tiles' windows [ntile, nk, n/L+7, n/L+7] of the same global fields (gather() puts results back on faces)."""
 
     def __init__(self, n=12, npz=6, n_split=2, k_split=1, dt=1800.0, backend="hip", seed=20250114, nq=0, oracle=False, rank=0, world=1,
-                 layout=1, loopback=False, **optkw):
+                 layout=1, loopback=False, metrics_hook=None, edge_forms="extended", **optkw):
         """rank/world: this process holds only cube.faces_of(rank, world, ntiles) (one process per GPU); state and metrics are the
         corresponding slices of the same global fields, so results can be compared with a single-process run.
         loopback: the rows between this rank's own tiles go through the message path too (cube.split_table).
         levels=(ak, bk): hybrid coefficients [npz+1] handed to the library in place of the state's own (column physics that reads
-        PREF = ak + bk p00; the synthetic state is left as it is)."""
+        PREF = ak + bk p00; the synthetic state is left as it is).
+        metrics_hook: callable(metrics, edge, ecorner) applied to the metric dict [6, pj, pj] and the a2b edge data of the six whole
+        faces (before they are cut into tiles or dealt over ranks) and before the library instance is created; it changes them in
+        place or returns the three to use instead.
+        edge_forms: cube.cubed_sphere_metrics(edge_forms=...), "extended" or "reference"."""
         from . import cube
         self.n = n
         self.layout = layout
@@ -115,8 +131,9 @@ class CubeCase:
         self.tau, self.rf_cutoff = optkw.pop("tau", 0.0), optkw.pop("rf_cutoff", 0.0)
         levels = optkw.pop("levels", None)
         self.opt = default_options(**optkw)
-        self.metrics, self.da_min, self.da_min_c, self.edge, self.ecorner, self.geo = cube.cubed_sphere_metrics(n)
+        self.metrics, self.da_min, self.da_min_c, self.edge, self.ecorner, self.geo = cube.cubed_sphere_metrics(n, edge_forms=edge_forms)
         self.c2l = self.geo["c2l"]
+        self.metrics, self.edge, self.ecorner = _apply_metrics_hook(metrics_hook, self.metrics, self.edge, self.ecorner)
         self.traj, self.phis, self.ak, self.bk = cube.cube_fields(n, npz, self.geo, seed, "traj", self.opt)
         if levels is not None:
             self.ak, self.bk = (np.array(x, dtype=np.float64) for x in levels)

@@ -1,5 +1,6 @@
 """Shared case builder for the parity tests: the package's synthetic cases (fv3_jedi_linearmodel_amd/harness.py) + the oracle as checker and
-a second backend, the test-only host-emulation build of the product's stage code."""
+a second backend, the test-only host-emulation build of the product's stage code.  The cube cases of the tests run on the metric form
+the reference holds along the face edges (cube.cubed_sphere_metrics edge_forms="reference", pinned by tests/test_face_metrics.py)."""
 import os
 import subprocess
 import numpy as np
@@ -46,8 +47,8 @@ class _TestHooks:
 
 
 class Case(_TestHooks, H.Case):
-    def __init__(self, *a, backend="emul", oracle=True, **kw):
-        super().__init__(*a, backend=backend, oracle=oracle, **kw)
+    def __init__(self, *a, backend="emul", oracle=True, edge_forms="reference", **kw):
+        super().__init__(*a, backend=backend, oracle=oracle, edge_forms=edge_forms, **kw)
 
     def _make_oracle(self):
         o = Oracle(self.nx, self.ny, self.npz, self.nq, self.metrics, self.opt, self.da_min, self.da_min_c, self.phis, self.ak, self.bk)
@@ -57,8 +58,8 @@ class Case(_TestHooks, H.Case):
 
 
 class CubeCase(_TestHooks, H.CubeCase):
-    def __init__(self, *a, backend="emul", oracle=False, **kw):
-        super().__init__(*a, backend=backend, oracle=oracle, **kw)
+    def __init__(self, *a, backend="emul", oracle=False, edge_forms="reference", **kw):
+        super().__init__(*a, backend=backend, oracle=oracle, edge_forms=edge_forms, **kw)
 
     def _make_oracle(self):
         from oracle import CubeOracle

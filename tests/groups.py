@@ -55,12 +55,56 @@ def drop_face_corners(c, name, arr):
             for isl in (slice(0, 3), slice(c.nx + 3, None)):
                 out[..., js, isl] = 0.0
         return out
-    if name not in ("ua", "va"):
+    # c_sw at the four corner-halo cells: the reference forms delpc, ptc there with rarea = -1 / big_number (fill_ghost,
+    # fv_grid_tools_nlm.F90:902; sw_core_nlm.F90:246-256) and the area fluxes ut, vt around them with sin_sg = tiny_number and the
+    # corner-halo cosa_u/v, rsin_u/v (:157-174): by its own account they hold no value, though the rects Ah, UTF, VTF include them
+    cells = [(0, 0), (c.nx + 1, 0), (0, c.ny + 1), (c.nx + 1, c.ny + 1)]
+    pts = {"ua": cells, "va": cells, "delpc": cells, "ptc": cells, "utf": [(0, 0), (c.nx + 2, 0), (0, c.ny + 1), (c.nx + 2, c.ny + 1)],
+           "vtf": [(0, 0), (c.nx + 1, 0), (0, c.ny + 2), (c.nx + 1, c.ny + 2)]}
+    if name not in pts:
         return arr
     out = arr.copy()
-    for (i, j) in ((0, 0), (c.nx + 1, 0), (0, c.ny + 1), (c.nx + 1, c.ny + 1)):
+    for (i, j) in pts[name]:
         out[..., j + 2, i + 2] = 0.0
     return out
+
+
+# ---- per-region error measure: an edge error is never divided by a bulk maximum
+REGION_WIDTH = 3
+
+
+def regions(n, rect, width=REGION_WIDTH):
+    """Per-region error measure (square faces).  {name: boolean [pj, pj]} partition of the rect (i0, i1, j0, j1) into bulk, four edge strips and four corner blocks"""
+    pj = n + 7
+    J, I = np.meshgrid(np.arange(pj) - 2, np.arange(pj) - 2, indexing="ij")
+    i0, i1, j0, j1 = rect
+    inside = (I >= i0) & (I <= i1) & (J >= j0) & (J <= j1)
+    w, e, s, nn = I <= width, I >= n + 1 - width, J <= width, J >= n + 1 - width
+    out = dict(sw=w & s, se=e & s & ~w, ne=e & nn & ~w & ~s, nw=w & nn & ~s)
+    corner = out["sw"] | out["se"] | out["ne"] | out["nw"]
+    out.update(west=w & ~corner, east=e & ~corner & ~w, south=s & ~corner, north=nn & ~corner & ~s)
+    out["bulk"] = ~(w | e | s | nn)
+    return {k: v & inside for k, v in out.items() if (v & inside).any()}
+
+
+def region_errors(got, ref, mask, n, rect):
+    """{region: worst over levels of max |got - ref| / max |ref| over the points of mask in that region}; every masked point is in one"""
+    res = {}
+    covered = np.zeros_like(mask)
+    for name, reg in regions(n, rect).items():
+        sel = reg & mask
+        covered |= sel
+        if not sel.any():
+            continue
+        worst = 0.0
+        for k in range(ref.shape[0]):
+            r = ref[k][sel]
+            assert np.all(np.isfinite(r.astype(np.float64))), ("the restatement read an undefined entry", name, k)
+            scale = np.max(np.abs(r))
+            worst = max(worst, float(np.max(np.abs(got[k][sel] - r)) / (scale if scale > 0 else 1)))
+        res[name] = worst
+    assert np.array_equal(covered, mask)
+    return res
 
 
 def make_inputs(c, group, seed=7):
@@ -102,7 +146,9 @@ def make_inputs(c, group, seed=7):
     return T, P
 
 
-def check_group(c, group, mode, tol):
+def check_group(c, group, mode, tol, region_tol=None):
+    """region_tol: additionally hold every output of the tangent run to region_tol per region (regions / region_errors above: relative to the
+    largest reference value of the same output, level and region); the global norm and its assertions stay as they are."""
     meth, scal, ins, outs = table(c)[group]
     T, P = make_inputs(c, group)
     fn = getattr(c.oracle, meth)
@@ -122,6 +168,11 @@ def check_group(c, group, mode, tol):
             assert e1 < tol, (group, n, "traj", e1)
             assert e2 < tol, (group, n, "tl", e2)
             worst = max(worst, e1, e2)
+            if region_tol is not None:
+                mask = D(masked(c, np.ones_like(a), rk))[0] != 0
+                for which, ref_ in ((0, a), (1, b)):
+                    for reg, e in region_errors(c.dy.get(n, which)[0], ref_, mask, c.nx, rects(c)[rk]).items():
+                        assert e < region_tol, (group, n, reg, which, e)
         return worst
     # adjoint: random output adjoints on the defined ranges
     rng = np.random.default_rng(11)
