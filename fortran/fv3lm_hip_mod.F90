@@ -18,6 +18,7 @@ module fv3lm_hip_mod
   public :: fv3lm_hip_create, fv3lm_hip_destroy, fv3lm_hip_put, fv3lm_hip_get
   public :: fv3lm_hip_step_tl, fv3lm_hip_step_ad
   public :: fv3lm_hip_traj_to_fv3, fv3lm_hip_pert_to_fv3, fv3lm_hip_fv3_to_pert
+  public :: fv3lm_hip_set_tracer_damping, fv3lm_hip_tracer_damping
   public :: fv3lm_hip_set_rayleigh, fv3lm_hip_rayleigh_profile
   public :: fv3lm_hip_turbulence_create, fv3lm_hip_turbulence_set_diagonals, fv3lm_hip_turbulence_set_simple
   public :: fv3lm_hip_turbulence, fv3lm_hip_turbulence_get
@@ -107,6 +108,21 @@ module fv3lm_hip_mod
       type(c_ptr), value :: h
       real(c_double), intent(out) :: rf(*)
       integer(c_int), intent(out) :: kmax
+      integer(c_int) :: rc
+    end function
+    function c_set_tracer_damping(h, nord_tr, trdm2, nord_tr_pert, trdm2_pert, split_damp_tr) &
+        bind(C, name="fv3lm_set_tracer_damping") result(rc)
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      integer(c_int), value :: nord_tr, nord_tr_pert, split_damp_tr
+      real(c_double), value :: trdm2, trdm2_pert
+      integer(c_int) :: rc
+    end function
+    function c_tracer_damping(h, nord2, trdm2) bind(C, name="fv3lm_tracer_damping") result(rc)
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      integer(c_int), intent(out) :: nord2(2)
+      real(c_double), intent(out) :: trdm2(2)
       integer(c_int) :: rc
     end function
     function c_set_exchange(h, kind, rows, nrows) bind(C, name="fv3lm_set_exchange") result(rc)
@@ -379,6 +395,25 @@ contains
     integer(c_int), intent(out) :: kmax
     call check(c_rayleigh_profile(self%handle, rf, kmax), 'rayleigh_profile')
   end subroutine fv3lm_hip_rayleigh_profile
+
+  !> Tracer damping of tracer_2d: FV_Atm(1)%flagstruct%nord_tr, %trdm2 and FV_AtmP(1)%flagstruct%nord_tr_pert, %trdm2_pert,
+  !! %split_damp_tr (include/fv3lm.h).  Call after fv3lm_hip_create, before the first step or between complete steps.
+  subroutine fv3lm_hip_set_tracer_damping(self, nord_tr, trdm2, nord_tr_pert, trdm2_pert, split_damp_tr)
+    type(fv3lm_hip_type), intent(inout) :: self
+    integer(c_int), intent(in) :: nord_tr, nord_tr_pert
+    real(c_double), intent(in) :: trdm2, trdm2_pert
+    logical, intent(in) :: split_damp_tr
+    call check(c_set_tracer_damping(self%handle, nord_tr, trdm2, nord_tr_pert, trdm2_pert, merge(1_c_int, 0_c_int, split_damp_tr)), &
+               'set_tracer_damping')
+  end subroutine fv3lm_hip_set_tracer_damping
+
+  !> the effective pairs: nord2 = (nord_tr, nord_tr_pert), trdm2 = (trdm2, trdm2_pert)
+  subroutine fv3lm_hip_tracer_damping(self, nord2, trdm2)
+    type(fv3lm_hip_type), intent(inout) :: self
+    integer(c_int), intent(out) :: nord2(2)
+    real(c_double), intent(out) :: trdm2(2)
+    call check(c_tracer_damping(self%handle, nord2, trdm2), 'tracer_damping')
+  end subroutine fv3lm_hip_tracer_damping
 
   !> One halo-exchange table (kind 0..4, include/fv3lm.h): rows(7, n) for the faces resident on this GPU, and the
   !! per-peer send/receive lists for faces held by other ranks (replaces mpp_update_domains / mpp_get_boundary).

@@ -22,6 +22,8 @@ program shim_driver
   real(c_double), allocatable :: u(:, :, :), v(:, :, :), pt(:, :, :), delp(:, :, :), q(:, :, :, :)
   real(c_double), allocatable :: up(:, :, :), vp(:, :, :), ptp(:, :, :), delpp(:, :, :), qp(:, :, :, :)
   character(len=8) :: qn
+  integer(c_int) :: nord2(2)
+  real(c_double) :: trdm2(2)
 
   call get_command_argument(1, fin); call get_command_argument(2, fout)
   open(11, file=trim(fin), access='stream', form='unformatted', status='old')
@@ -42,6 +44,10 @@ program shim_driver
   end do
   if (bad == 1) opt%nord = 7        ! an option the library refuses: exercises status -> fv3lm_last_error -> fatal exit
   call fv3lm_hip_create(dyn, dims, opt, mptr, da_min, da_min_c, phis, ak, bk)
+  ! tracer damping, set where a host sets it (INTEGRATION.md): a coefficient of zero, so the steps below are the undamped ones
+  call fv3lm_hip_set_tracer_damping(dyn, 1, 0.0_c_double, 0, 0.0_c_double, .true.)
+  call fv3lm_hip_tracer_damping(dyn, nord2, trdm2)
+  if (nord2(1) /= 1 .or. nord2(2) /= 0 .or. trdm2(1) /= 0.0_c_double .or. trdm2(2) /= 0.0_c_double) error stop 'fv3lm_hip_tracer_damping'
   open(12, file=trim(fout), access='stream', form='unformatted', status='replace')
   ! ---- step_tl: trajectory and perturbation in, both advanced
   call put_all(0, u, v, pt, delp, q); call put_all(1, up, vp, ptp, delpp, qp)

@@ -252,6 +252,19 @@ class Dycore:
         self.lib.L.fv3lm_rayleigh.argtypes = [C.c_void_p, C.c_int]
         self._chk(self.lib.L.fv3lm_rayleigh(self.h, mode))
 
+    # ---- tracer damping of tracer_2d (nord_tr, trdm2 and their *_pert; fv_tracer2d_tlm.F90:1045-1111) ----
+    def set_tracer_damping(self, nord_tr=0, trdm2=0.0, nord_tr_pert=0, trdm2_pert=0.0, split_damp_tr=1):
+        """fv3lm_set_tracer_damping: after create, before a step or between complete steps; rebuilds the tracer program."""
+        self.lib.L.fv3lm_set_tracer_damping.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int]
+        self._chk(self.lib.L.fv3lm_set_tracer_damping(self.h, int(nord_tr), float(trdm2), int(nord_tr_pert), float(trdm2_pert), int(split_damp_tr)))
+
+    def tracer_damping(self):
+        """-> ((nord_tr, trdm2), (nord_tr_pert, trdm2_pert)): the effective trajectory and perturbation pairs"""
+        n = (C.c_int * 2)(); d = (C.c_double * 2)()
+        self.lib.L.fv3lm_tracer_damping.argtypes = [C.c_void_p, C.POINTER(C.c_int), _dp]
+        self._chk(self.lib.L.fv3lm_tracer_damping(self.h, n, d))
+        return (n[0], d[0]), (n[1], d[1])
+
     # ---- linearised boundary-layer turbulence (fv3jedi_lm_turbulence_mod.F90; csrc/turbulence.h), compact arrays [ntile, npz, ny, nx] ----
     def _compact(self, a, nk=None):
         a = np.ascontiguousarray(a, dtype=np.float64)

@@ -173,6 +173,9 @@ struct LevelParams {
   double d2_divg_p = 0., damp_t_pert = 0., dddmp = 0., d4_bg = 0., dddmp_p = 0., d4_bg_p = 0.;
   // tracer_2d sub-cycling of the current call (fv_tracer2d_tlm.F90:1306-1345): sub-steps this level takes and 1/that
   int tr_ksplt = 1; double tr_frac = 1.0;
+  // tracer damping (fv3lm_set_tracer_damping): the trajectory's nord_tr / trdm2 and the perturbation's nord_tr_pert / trdm2_pert, after
+  // run_setup_pert has overwritten the former by the latter where split_damp_tr is off (fv_control_tlmadm.F90:232-234)
+  int nord_tr = 0, nord_tr_p = 0; double trdm2 = 0., trdm2_p = 0.;
   double dp_ref = 0.;       // ak(k+1)-ak(k) + (bk(k+1)-bk(k))*1e5 (dyn_core_tlm.F90:1704-1706), non-hydrostatic interface weights
 };
 

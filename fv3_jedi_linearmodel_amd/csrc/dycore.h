@@ -541,10 +541,29 @@ struct Dycore {
     ppm_y(q_j, fyo, R(is, ie, js, je + 1), 0);
     const size_t o2b = P.size();
     Fld d2b{};
-    if (dsel != DAMP_NONE) {
+    // the tracers' damping (DAMP_TR) acts in the first sub-step of tracer_2d only: its stages launch nothing in the later ones, and a
+    // damping Laplacian exists only where some level's order asks for one (need_d2: the chain the tangent / adjoint is taken of,
+    // need_d2t: the trajectory pass of split levels)
+    bool need_d2 = dsel != DAMP_NONE, need_d2t = need_d2;
+    if (dsel == DAMP_TR) {
+      need_d2 = need_d2t = false;
+      for (int k = 0; k < npz && k < (int)lev_host.size(); ++k) {
+        const bool sp = level_split(lev_host[k], hsel, dsel);
+        int n_; double d_; damp_of(lev_host[k], dsel, n_, d_, sp); need_d2 = need_d2 || (n_ >= 1 && d_ > 1.e-4);
+        if (sp) { damp_of(lev_host[k], dsel, n_, d_, false); need_d2t = need_d2t || (n_ >= 1 && d_ > 1.e-4); }
+      }
+    }
+    Ctx* gate_ctx = &ctx;
+    auto first_substep_only = [&](size_t n0) {
+      if (dsel != DAMP_TR) return;
+      for (size_t n = n0; n < P.size(); ++n) { auto f = P[n].fn; P[n].fn = [f, gate_ctx](Exec& e, int m) { if (gate_ctx->tr_it == 1) f(e, m); }; }
+    };
+    if (need_d2) {
+      const size_t n0 = P.size();
       d2b = W((pre + "_d2b").c_str(), npz);
       TpD2D h; h.in[0] = q; h.out[0] = d2b; h.orect[0] = R(is - 1, ie + 1, js - 1, je + 1); h.k1 = npz; h.dsel = dsel; h.use_mass = use_mass; h.hsel = hsel;
       add_face(P, grp, h, 1);
+      first_substep_only(n0);
     }
     // split_hord: some level runs this transport with a trajectory scheme other than the scheme the tangent / adjoint is taken of
     bool any_split = false;
@@ -577,7 +596,7 @@ struct Dycore {
       for (const Fld* f_ : {&a.fx, &a.fy, &a.fy2, &a.q_i, &a.fxo, &a.fx2, &a.q_j, &a.fyo, &a.acx, &a.acy, &a.amfx, &a.amfy}) if (f_->p) op.ad_out.push_back(f_->p);
       P.push_back(op);
       if (any_split) {       // the trajectory pass of the split levels: its own damping Laplacian (run as a nonlinear launch in the tangent mode too), then the chain
-        if (dsel != DAMP_NONE) {
+        if (need_d2t) {
           Fld d2t = W((pre + "_d2t").c_str(), npz);
           // a trajectory nord of 2 (split_damp, nord >= 2): two Laplacians, the first into a scratch array on the range widened by one
           bool nord2 = false;
@@ -596,6 +615,7 @@ struct Dycore {
             P[n].fn = [f](Exec& e, int) { f(e, MODE_NL); };
             P[n].modes = (1u << MODE_NL) | (1u << MODE_TL); P[n].ad_in.clear(); P[n].ad_in_slot.clear(); P[n].ad_out.clear(); P[n].ad_out_rect.clear(); P[n].set_wmask = nullptr;
           }
+          first_substep_only(n0);
           a.d2b_t = d2t;
         }
         Op tr{grp, [a, cp](Exec& e, int mode) { run_tp_fused(e, mode, a, *cp, true); }};
@@ -613,7 +633,9 @@ struct Dycore {
           for (int n = 1; n < 3; ++n) if (!dm.in[n].t) dm.in[n].nk = npz;
           dm.out[0] = fx; dm.out[1] = fy; dm.orect[0] = R(is, ie + 1, js, je); dm.orect[1] = R(is, ie, js, je + 1); dm.k1 = npz;
           dm.dsel = dsel; dm.use_mass = use_mass; dm.hsel = hsel;
+          const size_t n0 = P.size();
           add(P, grp, dm); P.back().modes = 1u << MODE_AD;
+          first_substep_only(n0);
         }
         Op ad{grp, [a, cp, adf](Exec& e, int) { if (adf == 2) run_tp_ad(e, a, *cp); else run_tp_outer_ad(e, a, *cp); }};
         ad.modes = 1u << MODE_AD; ad.name = adf == 2 ? "TpAd" : "TpOuter";

@@ -146,6 +146,11 @@ struct Dynamics : Dycore {
   Fld rf_pth;                                    // non-hydrostatic: the heated temperature of levels 1..kmax ("rf_pt")
   Progs pt_in_rf;                                // non-hydrostatic pt_in with the damping on (stages.h DynPtInNhRf)
   bool set_rayleigh(double tau, double rf_cutoff, const double* c2l);
+  // Tracer damping (fv3lm_set_tracer_damping): the effective trajectory and perturbation pairs live in LevelParams; the transport
+  // program carries the damping stages and the mass argument only while the trajectory's coefficient opens the gate
+  bool tr_damp = false;
+  bool set_tracer_damping(int nord_tr, double trdm2, int nord_tr_pert, double trdm2_pert, int split_damp_tr);
+  void rebuild_tracer();
   RfArgs rf_args();
   void rayleigh(int mode);
   // one field between the host's compact array and the device state.  which: 0 trajectory, 1 perturbation / adjoint
@@ -376,7 +381,8 @@ inline void Dynamics::build_tracer() {
   auto build_q = [&]() {
     Arena save = work; work = twork;
     Fld fx = W("tr_fx", npz), fy = W("tr_fy", npz);
-    build_tp(tracer_q, "tracer", "tpq", qc, cxs, cys, xfx, yfx, rax, ray, mfxs, mfys, Fld{}, HORD_TR, DAMP_NONE, false, fx, fy);
+    // mass = dp1, nord = nord_tr, damp_c = trdm2 where the damping is on (fv_tracer2d_tlm.F90:1060-1062)
+    build_tp(tracer_q, "tracer", "tpq", qc, cxs, cys, xfx, yfx, rax, ray, mfxs, mfys, tr_damp ? dp1 : Fld{}, HORD_TR, tr_damp ? DAMP_TR : DAMP_NONE, tr_damp, fx, fy);
     { TrUpdate s; s.in[0] = qc; s.in[1] = dp1; s.in[2] = dp2; s.in[3] = fx; s.in[4] = fy; s.out[0] = qc_o; s.orect[0] = R(is, ie, js, je); s.k1 = npz;
       add(tracer_q, "tracer", s); }
     twork = work; work = save;
@@ -388,6 +394,45 @@ inline void Dynamics::build_tracer() {
   }
   build_q();
   tracer_zero = plan_adjoint(tracer_q, twork);
+}
+
+// The tracer programs of every class again, on the same shared fields and a per-tracer work arena sized anew (the damping stages bring
+// their Laplacians).  Between complete steps only: nothing of a step in flight lives in these arrays.
+inline void Dynamics::rebuild_tracer() {
+  dev_sync(ex);
+  for (Progs* P_ : {&tracer_scale, &tracer_pre, &tracer_q}) P_->c.assign(classes.size(), Program{});
+  for (auto it = F.begin(); it != F.end();) { if (it->first.compare(0, 3, "tr_") == 0 || it->first.compare(0, 4, "tpq_") == 0) it = F.erase(it); else ++it; }
+  tshared.used = 0; twork.destroy(); twork = Arena{};
+  std::map<double*, size_t> tzero;
+  for (int c = 0; c < (int)classes.size(); ++c) {
+    set_class(c); reuse_fields = c > 0;
+    build_tracer();
+    for (auto& zr : tracer_zero) { auto it = tzero.find(zr.first); if (it == tzero.end() || it->second < zr.second) tzero[zr.first] = zr.second; }
+  }
+  reuse_fields = false; set_class(-1);
+  tracer_zero.assign(tzero.begin(), tzero.end());
+}
+
+// fv3lm_set_tracer_damping.  run_setup_pert (fv_control_tlmadm.F90:232-234): without split_damp_tr the trajectory's pair IS the
+// perturbation's.  The gate of the call site reads the trajectory's coefficient alone (fv_tracer2d_tlm.F90:1046).
+inline bool Dynamics::set_tracer_damping(int nord_tr, double trdm2, int nord_tr_pert, double trdm2_pert, int split_damp_tr) {
+  // by the bit pattern, as in set_rayleigh: the library is built with -ffinite-math-only
+  auto finite = [](double x) { volatile double v = x; const double y = v; uint64_t b; std::memcpy(&b, &y, 8); return ((b >> 52) & 0x7ffu) != 0x7ffu; };
+  if (!finite(trdm2) || !finite(trdm2_pert)) { err = "fv3lm_set_tracer_damping: trdm2 and trdm2_pert must be finite"; return false; }
+  if (trdm2 < 0. || trdm2_pert < 0.) { err = "fv3lm_set_tracer_damping: negative damping coefficient"; return false; }
+  if (split_damp_tr < 0 || split_damp_tr > 1) { err = "fv3lm_set_tracer_damping: split_damp_tr must be 0 or 1"; return false; }
+  if (nord_tr_pert < 0 || nord_tr_pert > 1) { err = "fv3lm_set_tracer_damping: nord_tr_pert must be 0 or 1 (the tangent of a higher-order deln_flux is not built)"; return false; }
+  if (nord_tr < 0 || nord_tr > 2) { err = "fv3lm_set_tracer_damping: nord_tr must be 0, 1 or 2 (nord_tr = 3 is not built)"; return false; }
+  const int n_t = split_damp_tr ? nord_tr : nord_tr_pert; const double d_t = split_damp_tr ? trdm2 : trdm2_pert;
+  if (n_t == 2 && opt.hord_tr == opt.hord_tr_pert) {
+    err = "fv3lm_set_tracer_damping: nord_tr = 2 needs hord_tr != hord_tr_pert (with equal schemes the damped call is the differentiated one, and the tangent of a nord-2 deln_flux is not built)";
+    return false;
+  }
+  for (LevelParams& l : lev_host) { l.nord_tr = n_t; l.trdm2 = d_t; l.nord_tr_p = nord_tr_pert; l.trdm2_p = trdm2_pert; }
+  h2d(ex, lev_dev, lev_host.data(), sizeof(LevelParams) * lev_host.size());
+  tr_damp = d_t > 1.e-4;
+  rebuild_tracer();
+  return true;
 }
 
 inline void Dynamics::set_tracer_levels(const std::vector<int>& ksplt) {

@@ -103,6 +103,17 @@ int fv3lm_rayleigh_profile(fv3lm_handle* h, double* rf, int* kmax) {
   *kmax = h->d.rf_kmax;
   return 0;
 }
+int fv3lm_set_tracer_damping(fv3lm_handle* h, int nord_tr, double trdm2, int nord_tr_pert, double trdm2_pert, int split_damp_tr) {
+  if (!h) return fail("fv3lm_set_tracer_damping: null handle");
+  if (!h->d.set_tracer_damping(nord_tr, trdm2, nord_tr_pert, trdm2_pert, split_damp_tr)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_tracer_damping(fv3lm_handle* h, int* nord2, double* trdm2) {
+  if (!h || !nord2 || !trdm2) return fail("fv3lm_tracer_damping: null argument");
+  const LevelParams& l = h->d.lev_host[0];
+  nord2[0] = l.nord_tr; nord2[1] = l.nord_tr_p; trdm2[0] = l.trdm2; trdm2[1] = l.trdm2_p;
+  return 0;
+}
 int fv3lm_set_exchange(fv3lm_handle* h, int kind, const int* rows, int nrows) {
   if (!rows && nrows > 0) return fail("fv3lm_set_exchange: null table");
   return h->d.set_exchange(kind, rows, nrows) ? 0 : fail(h->d.err);

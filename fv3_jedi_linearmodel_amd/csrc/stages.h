@@ -843,12 +843,15 @@ HD T lap_corner(const A& a, const Ctx& c, int tile, int i, int j) {
   T fyb = MET(del6_u, i, j + 1) * (ry(i, j) - ry(i, j + 1));
   return (fxa - fxb + (fya - fyb)) * MET(rarea, i, j);
 }
-enum DampSel { DAMP_NONE = 0, DAMP_V = 1, DAMP_T = 2 };
+enum DampSel { DAMP_NONE = 0, DAMP_V = 1, DAMP_T = 2, DAMP_TR = 3 };
 // pert: the level's transport runs with split schemes and this is the perturbation chain: nord_v_pert / damp_vt_pert for the mass
 // (sw_core_tlm.F90:1672-1679), nord_t_pert / damp_t_pert for the heat transport (:1795-1800) -- the latter pair is the former as it
 // stands BEFORE the perturbation sponge rules override it (dyn_core_tlm.F90:856-859 vs :913-917)
+// DAMP_TR: the tracer transport's nord_tr / trdm2, for the chain the tangent / adjoint is taken of on a level with split schemes the
+// perturbation's nord_tr_pert / trdm2_pert (fv_tracer2d_tlm.F90:1062, :1077, :1081)
 HD void damp_of(const LevelParams& l, int sel, int& nord, double& damp_c, bool pert = false) {
-  if (sel != DAMP_V && sel != DAMP_T) { nord = -1; damp_c = 0.; }
+  if (sel == DAMP_TR) { nord = pert ? l.nord_tr_p : l.nord_tr; damp_c = pert ? l.trdm2_p : l.trdm2; }
+  else if (sel != DAMP_V && sel != DAMP_T) { nord = -1; damp_c = 0.; }
   else if (pert) { if (sel == DAMP_V) { nord = l.nord_v_pert; damp_c = l.damp_vt_pert; } else { nord = l.nord_t_pert; damp_c = l.damp_t_pert; } }
   else if (sel == DAMP_V) { nord = l.nord_v; damp_c = l.damp_vt; }
   else { nord = l.nord_t; damp_c = l.damp_t; }
@@ -859,6 +862,7 @@ HD double damp_pow(double x, int nord) { double r = x; for (int n = 0; n < nord;
 // trajectory's?  split_hord: the schemes differ (sw_core_tlm.F90:1664-1682); split_damp: the reference takes the two-call branch for the
 // mass and heat transports whatever the schemes (:1664, :1787) -- the second call changes the values only where the damping pairs differ,
 // so only then is it made here.
+// The tracer transport (DAMP_TR) takes it for split schemes alone, whatever its damping pairs (fv_tracer2d_tlm.F90:1047).
 HD bool level_split(const LevelParams& l, int hsel, int dsel = DAMP_NONE) {
   if (hord_traj_of(l, hsel) != hord_of(l, hsel)) return true;
   if (!l.split_damp || (dsel != DAMP_V && dsel != DAMP_T)) return false;
@@ -866,6 +870,9 @@ HD bool level_split(const LevelParams& l, int hsel, int dsel = DAMP_NONE) {
   const bool on0 = d0 > 1.e-4, on1 = d1 > 1.e-4;
   return on0 != on1 || (on0 && (n0 != n1 || d0 != d1));
 }
+// Is the damping of this transport called for at all?  The tracers' is, in the first sub-step of tracer_2d and where the TRAJECTORY's
+// coefficient says so (it == 1 .and. trdm > 1e-4, fv_tracer2d_tlm.F90:1046); the coefficient actually passed is then tested as ever.
+HD bool damp_gate(const Ctx& c, const LevelParams& l, int dsel) { return dsel != DAMP_TR || (c.tr_it == 1 && l.trdm2 > 1.e-4); }
 struct TpD2D {
   static constexpr bool LDS_FW_OK = true;
   STAGE_BASE("TpD2", 1, 1)   // in: q   out: d2b  (is-1..ie+1, js-1..je+1); zero where the level does not use nord=1
@@ -884,7 +891,7 @@ struct TpD2D {
     int nord; double dc; damp_of(c.lev[k - 1], dsel, nord, dc, split && !traj);
     o[0] = T(0.);
     if (traj && !split) return;
-    if (nord < 1 || !(dc > 1.e-4)) return;
+    if (nord < 1 || !(dc > 1.e-4) || !damp_gate(c, c.lev[k - 1], dsel)) return;
     // nord = 2 (a trajectory pass only): this is the second Laplacian, of the first one's result (in[0] = TpD2D with pass = 1), sign as
     // in tp_core_tlm.F90:2019-2031
     if (pass == 1) { if (nord == 2) o[0] = lap_corner<EDGE, 0, T>(a, c, tile, i, j); return; }
@@ -905,7 +912,7 @@ struct TpFlux {
   template <class T, class A>
   HD void eval(const A& a, const Ctx& c, int tile, int i, int j, int k, T* o) const {
     int nord; double dc; damp_of(c.lev[k - 1], dsel, nord, dc, hsel >= 0 && level_split(c.lev[k - 1], hsel, dsel));
-    const bool dmp = (dsel != DAMP_NONE) && (dc > 1.e-4);
+    const bool dmp = (dsel != DAMP_NONE) && (dc > 1.e-4) && damp_gate(c, c.lev[k - 1], dsel);
     double damp = 0.;
     if (dmp) damp = damp_pow(dc * c.m.da_min, nord);
     o[0] = o[1] = T(0.);
@@ -957,7 +964,7 @@ struct TpDamp {
     double acc[3] = {0., 0., 0.};
     if (k >= k0 && k <= k1) {
       int nord; double dc; damp_of(c.lev[k - 1], dsel, nord, dc, hsel >= 0 && level_split(c.lev[k - 1], hsel, dsel));
-      if ((dsel != DAMP_NONE) && (dc > 1.e-4)) {
+      if ((dsel != DAMP_NONE) && (dc > 1.e-4) && damp_gate(c, c.lev[k - 1], dsel)) {
         const double damp = damp_pow(dc * c.m.da_min, nord);
         auto tr = [&](int m, int ii, int jj) { return in[m].t[pb + c.g.idx(ii, jj)]; };
         // face (ii, jj) of direction dir (0: x-face between cells ii-1, ii; 1: y-face between jj-1, jj): sgn = +1 if the point is the face's
@@ -995,7 +1002,7 @@ struct TpDamp {
   template <class T, class A>
   HD void eval(const A& a, const Ctx& c, int tile, int i, int j, int k, T* o) const {
     int nord; double dc; damp_of(c.lev[k - 1], dsel, nord, dc, hsel >= 0 && level_split(c.lev[k - 1], hsel, dsel));
-    const bool dmp = (dsel != DAMP_NONE) && (dc > 1.e-4);
+    const bool dmp = (dsel != DAMP_NONE) && (dc > 1.e-4) && damp_gate(c, c.lev[k - 1], dsel);
     o[0] = o[1] = T(0.);
     if (!dmp) return;
     const double damp = damp_pow(dc * c.m.da_min, nord);

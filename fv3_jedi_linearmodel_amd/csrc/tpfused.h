@@ -224,7 +224,7 @@ DEV void tp_fused_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int
   TPF_SYNC();
   // ---- outer sweeps and flux assembly (tp_core_tlm.F90:187-234; deln_flux :1918-2043 as in stages.h TpFlux)
   int nord; double dc; damp_of(c.lev[k - 1], a.dsel, nord, dc, split && !TRAJ);
-  const bool dmp = (a.dsel != DAMP_NONE) && (dc > 1.e-4);
+  const bool dmp = (a.dsel != DAMP_NONE) && (dc > 1.e-4) && damp_gate(c, c.lev[k - 1], a.dsel);
   double damp = 0.;
   if (dmp) damp = damp_pow(dc * c.m.da_min, nord);
   const Fld& d2 = TRAJ ? a.d2b_t : a.d2b;

@@ -20,12 +20,19 @@ def _apply_metrics_hook(hook, metrics, edge, ecorner):
     return {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in metrics.items()}, np.ascontiguousarray(edge), np.ascontiguousarray(ecorner)
 
 
+def _pop_tracer_damping(optkw):
+    """the nord_tr=, trdm2=, nord_tr_pert=, trdm2_pert=, split_damp_tr= keywords of a case (fv3lm_set_tracer_damping); None: never set"""
+    kw = {k: optkw.pop(k) for k in ("nord_tr", "trdm2", "nord_tr_pert", "trdm2_pert", "split_damp_tr") if k in optkw}
+    return kw or None
+
+
 class Case:
     def __init__(self, nx=12, ny=12, npz=8, n_split=2, k_split=1, dt=1800.0, backend="hip", seed=20250114, oracle=False, nq=0,
                  face=None, metrics_hook=None, edge_forms="extended", **optkw):
         """face=None: the doubly-periodic tile with no cube edge.  face=t (0..5): one whole face of a C<nx> cube with
         the real gnomonic metrics of that face and arbitrary smooth halo data (kernel-group tests).
         tau=, rf_cutoff=: Rayleigh damping of the upper layers (fv3lm_set_rayleigh; off by default).
+        nord_tr=, trdm2=, nord_tr_pert=, trdm2_pert=, split_damp_tr=: tracer damping (fv3lm_set_tracer_damping; never called by default).
         levels=(ak, bk): hybrid coefficients [npz+1] in place of grid.hybrid_levels; the state's delp follows them at the same ps.
         metrics_hook (face cases): callable(metrics, edge, ecorner) applied to the metric dict [1, pj, pi] and the a2b edge data of the
         face before the library instance (and the oracle) are created; it changes them in place or returns the three to use instead.
@@ -33,6 +40,7 @@ class Case:
         self.nx, self.ny, self.npz = nx, ny, npz
         self.tau, self.rf_cutoff = optkw.pop("tau", 0.0), optkw.pop("rf_cutoff", 0.0)
         levels = optkw.pop("levels", None)
+        self.tracer_damping = _pop_tracer_damping(optkw)
         self.opt = default_options(**optkw)
         self.face = face
         if face is None:
@@ -77,6 +85,8 @@ class Case:
         self._after_create(backend)
         if self.tau:
             self.dy.set_rayleigh(self.tau, self.rf_cutoff, self.c2l)
+        if self.tracer_damping is not None:
+            self.dy.set_tracer_damping(**self.tracer_damping)
 
     # hooks of tests/common.py (oracle as checker, host-emulation backend); the package itself knows the HIP library only
     def _make_oracle(self):
@@ -130,6 +140,7 @@ class CubeCase:
         self.npz, self.nq = npz, nq
         self.tau, self.rf_cutoff = optkw.pop("tau", 0.0), optkw.pop("rf_cutoff", 0.0)
         levels = optkw.pop("levels", None)
+        self.tracer_damping = _pop_tracer_damping(optkw)
         self.opt = default_options(**optkw)
         self.metrics, self.da_min, self.da_min_c, self.edge, self.ecorner, self.geo = cube.cubed_sphere_metrics(n, edge_forms=edge_forms)
         self.c2l = self.geo["c2l"]
@@ -186,6 +197,8 @@ class CubeCase:
         self._after_create(backend)
         if self.tau:
             self.dy.set_rayleigh(self.tau, self.rf_cutoff, self.c2l)
+        if self.tracer_damping is not None:
+            self.dy.set_tracer_damping(**self.tracer_damping)
         for k, t in self.tables.items():
             if world > 1 or loopback:
                 self.dy.set_exchange_split(k, t, rank, world, ntiles, loopback)

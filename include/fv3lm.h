@@ -98,6 +98,24 @@ int fv3lm_set_face_data(fv3lm_handle* h, const double* edge, const double* ecorn
 int fv3lm_set_rayleigh(fv3lm_handle* h, double tau, double rf_cutoff, const double* c2l);
 /* rf(k) for k = 1..npz (0 below the cutoff) and kmax, as the library computed them (tests, diagnostics). */
 int fv3lm_rayleigh_profile(fv3lm_handle* h, double* rf, int* kmax);
+/* Tracer damping of tracer_2d: the mass-weighted del-2 (nord 0) or del-4 (nord 1) flux deln_flux adds to every tracer's transport
+ * (fv_tracer2d_tlm.F90:1045-1111 tangent, :1390-1417 nonlinear, fv_tracer2d_adm.F90 adjoint; tp_core_tlm.F90:203-206, :1918-2043).
+ * nord_tr, trdm2: flagstruct%nord_tr, %trdm2 of the trajectory; nord_tr_pert, trdm2_pert, split_damp_tr: the same of the perturbation
+ * (fv_core_pert_nml, fv_arrays_tlmadm.F90:87-90).  As in the reference:
+ *   - split_damp_tr = 0: the trajectory's pair is overwritten by the perturbation's (run_setup_pert, fv_control_tlmadm.F90:232-234);
+ *   - the damping acts in the first sub-step of a sub-cycled level only, and only where the TRAJECTORY's trdm2 > 1e-4; the
+ *     perturbation's coefficient never switches it on;
+ *   - hord_tr == hord_tr_pert: one differentiated call with the trajectory's pair -- nord_tr_pert, trdm2_pert are not read, whatever
+ *     split_damp_tr says; hord_tr != hord_tr_pert: the tangent / adjoint with the perturbation's pair (no damping where its
+ *     trdm2_pert <= 1e-4), the values again with the trajectory's.
+ * Call after fv3lm_create, before the first step; may be called again between complete steps.  It rebuilds the tracer program: the
+ * damping stages and the mass argument (dp1) exist only while the effective trajectory trdm2 > 1e-4; a handle that never calls it, or
+ * whose effective trdm2 <= 1e-4, runs exactly the launches it ran without.  Refused, the handle left as it was: a coefficient that is
+ * not finite or negative, split_damp_tr outside 0..1, nord_tr_pert outside 0..1, nord_tr outside 0..2 (nord 3 is not built), an
+ * effective nord_tr = 2 with hord_tr == hord_tr_pert (the tangent of a nord-2 deln_flux is not built).  nq = 0: accepted, no effect. */
+int fv3lm_set_tracer_damping(fv3lm_handle* h, int nord_tr, double trdm2, int nord_tr_pert, double trdm2_pert, int split_damp_tr);
+/* The effective pairs after the first rule above: nord2 = {nord_tr, nord_tr_pert}, trdm2 = {trdm2, trdm2_pert} (tests, diagnostics). */
+int fv3lm_tracer_damping(fv3lm_handle* h, int* nord2, double* trdm2);
 /* Halo exchange between the resident faces: replaces the FMS calls mpp_update_domains / mpp_get_boundary that the
  * reference issues from DYN_CORE_TLM (dyn_core_tlm.F90:1744-1790, :1960-1990, :2280-2300, :2418-2434) and
  * FV_DYNAMICS_TLM (fv_dynamics_tlm.F90:646-651, :708-712).  One table per kind of exchange:
