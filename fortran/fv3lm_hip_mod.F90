@@ -19,6 +19,7 @@ module fv3lm_hip_mod
   public :: fv3lm_hip_step_tl, fv3lm_hip_step_ad
   public :: fv3lm_hip_traj_to_fv3, fv3lm_hip_pert_to_fv3, fv3lm_hip_fv3_to_pert
   public :: fv3lm_hip_set_tracer_damping, fv3lm_hip_tracer_damping
+  public :: fv3lm_hip_set_external_damping, fv3lm_hip_external_damping
   public :: fv3lm_hip_set_rayleigh, fv3lm_hip_rayleigh_profile
   public :: fv3lm_hip_turbulence_create, fv3lm_hip_turbulence_set_diagonals, fv3lm_hip_turbulence_set_simple
   public :: fv3lm_hip_turbulence, fv3lm_hip_turbulence_get
@@ -123,6 +124,18 @@ module fv3lm_hip_mod
       type(c_ptr), value :: h
       integer(c_int), intent(out) :: nord2(2)
       real(c_double), intent(out) :: trdm2(2)
+      integer(c_int) :: rc
+    end function
+    function c_set_external_damping(h, d_ext) bind(C, name="fv3lm_set_external_damping") result(rc)
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      real(c_double), value :: d_ext
+      integer(c_int) :: rc
+    end function
+    function c_external_damping(h, d_ext) bind(C, name="fv3lm_external_damping") result(rc)
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: h
+      real(c_double), intent(out) :: d_ext
       integer(c_int) :: rc
     end function
     function c_set_exchange(h, kind, rows, nrows) bind(C, name="fv3lm_set_exchange") result(rc)
@@ -414,6 +427,21 @@ contains
     real(c_double), intent(out) :: trdm2(2)
     call check(c_tracer_damping(self%handle, nord2, trdm2), 'tracer_damping')
   end subroutine fv3lm_hip_tracer_damping
+
+  !> External-mode divergence damping of the acoustic step: FV_Atm(1)%flagstruct%d_ext (include/fv3lm.h; 0 = off, the library's default).
+  !! Call after fv3lm_hip_create, before the first step or between complete steps.
+  subroutine fv3lm_hip_set_external_damping(self, d_ext)
+    type(fv3lm_hip_type), intent(inout) :: self
+    real(c_double), intent(in) :: d_ext
+    call check(c_set_external_damping(self%handle, d_ext), 'set_external_damping')
+  end subroutine fv3lm_hip_set_external_damping
+
+  !> d_ext as set
+  subroutine fv3lm_hip_external_damping(self, d_ext)
+    type(fv3lm_hip_type), intent(inout) :: self
+    real(c_double), intent(out) :: d_ext
+    call check(c_external_damping(self%handle, d_ext), 'external_damping')
+  end subroutine fv3lm_hip_external_damping
 
   !> One halo-exchange table (kind 0..4, include/fv3lm.h): rows(7, n) for the faces resident on this GPU, and the
   !! per-peer send/receive lists for faces held by other ranks (replaces mpp_update_domains / mpp_get_boundary).

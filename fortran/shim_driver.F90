@@ -23,7 +23,7 @@ program shim_driver
   real(c_double), allocatable :: up(:, :, :), vp(:, :, :), ptp(:, :, :), delpp(:, :, :), qp(:, :, :, :)
   character(len=8) :: qn
   integer(c_int) :: nord2(2)
-  real(c_double) :: trdm2(2)
+  real(c_double) :: trdm2(2), d_ext
 
   call get_command_argument(1, fin); call get_command_argument(2, fout)
   open(11, file=trim(fin), access='stream', form='unformatted', status='old')
@@ -48,6 +48,10 @@ program shim_driver
   call fv3lm_hip_set_tracer_damping(dyn, 1, 0.0_c_double, 0, 0.0_c_double, .true.)
   call fv3lm_hip_tracer_damping(dyn, nord2, trdm2)
   if (nord2(1) /= 1 .or. nord2(2) /= 0 .or. trdm2(1) /= 0.0_c_double .or. trdm2(2) /= 0.0_c_double) error stop 'fv3lm_hip_tracer_damping'
+  ! external-mode divergence damping, likewise: zero, the steps below are the ones without it
+  call fv3lm_hip_set_external_damping(dyn, 0.0_c_double)
+  call fv3lm_hip_external_damping(dyn, d_ext)
+  if (d_ext /= 0.0_c_double) error stop 'fv3lm_hip_external_damping'
   open(12, file=trim(fout), access='stream', form='unformatted', status='replace')
   ! ---- step_tl: trajectory and perturbation in, both advanced
   call put_all(0, u, v, pt, delp, q); call put_all(1, up, vp, ptp, delpp, qp)

@@ -265,6 +265,20 @@ class Dycore:
         self._chk(self.lib.L.fv3lm_tracer_damping(self.h, n, d))
         return (n[0], d[0]), (n[1], d[1])
 
+    # ---- external-mode divergence damping of the acoustic step (flagstruct%d_ext; dyn_core_tlm.F90:1031-1060; csrc/dext.h) ----
+    def set_external_damping(self, d_ext):
+        """fv3lm_set_external_damping: after create, before a step or between complete steps; 0 = off (the default).  Going on or off
+        rebuilds the acoustic program of a hydrostatic handle; a non-hydrostatic one remembers the value and launches nothing for it."""
+        self.lib.L.fv3lm_set_external_damping.argtypes = [C.c_void_p, C.c_double]
+        self._chk(self.lib.L.fv3lm_set_external_damping(self.h, float(d_ext)))
+
+    def external_damping(self):
+        """-> d_ext as set (0.0 on a handle that never called the setter)"""
+        d = C.c_double(0.0)
+        self.lib.L.fv3lm_external_damping.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        self._chk(self.lib.L.fv3lm_external_damping(self.h, C.byref(d)))
+        return d.value
+
     # ---- linearised boundary-layer turbulence (fv3jedi_lm_turbulence_mod.F90; csrc/turbulence.h), compact arrays [ntile, npz, ny, nx] ----
     def _compact(self, a, nk=None):
         a = np.ascontiguousarray(a, dtype=np.float64)

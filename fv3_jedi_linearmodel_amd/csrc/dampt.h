@@ -43,6 +43,7 @@ struct DampTArgs {
   double *s1, *s2;                               // ping-pong scratch for the iterated divergence
   double* ke2;                                   // out: KE + damping, values
   double dt;
+  double* dvt = nullptr;                         // out, optional: the undamped divergence of the levels with nord_k = 0 (dext.h), values
 };
 
 // one pass n of the n-loop (sw_core_tlm.F90:8463-8530) for the levels with nord_k >= pass: src -> dst on is-nt .. ie+1+nt, nt = nord_k - pass
@@ -117,6 +118,7 @@ struct DampTFinal {
       if (!(cx && j == 1)) d += vrt(i, j - 1);
       if (!(cx && j == npy)) d -= vrt(i, j);
       const double delpc = M(a.m.rarea_c, i, j) * d;
+      if (a.dvt) a.dvt[n0] = delpc;
       const double x = delpc * a.dt, abs2 = x >= 0. ? x : -x, y3 = l.dddmp * abs2, y1 = (0.20 > y3) ? y3 : 0.20, mx = (l.d2_divg < y1) ? y1 : l.d2_divg;
       a.ke2[n0] = a.ke[n0] + (da_min_c * mx) * delpc;
     } else {

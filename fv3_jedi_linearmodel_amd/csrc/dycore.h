@@ -18,6 +18,7 @@
 #include "tpad.h"
 #include "tp2.h"
 #include "dampt.h"
+#include "dext.h"
 #include <functional>
 #include <map>
 #include <memory>
@@ -688,7 +689,13 @@ struct Dycore {
     if (!is_empty(b.orect[0])) add(P, grp, b);
   }
 
+  // external-mode divergence damping (dext.h; fv3lm_set_external_damping): flagstruct%d_ext, 0 = off.  The hydrostatic step carries its
+  // launches only while it is > 0; the non-hydrostatic step (beta = 0: nh_p_grad) never reads divg2
+  double d_ext = 0.;
+  bool dext_on() const { return !nh && d_ext > 0.; }
   void build_acoustic();
+  void plan_acoustic(bool rebuild);
+  void rebuild_acoustic();
   bool init(int nx, int ny, int npz, int ntile, int face, int nq_, double bdt_, int n_split_, int k_split_, const Options& o,
             const double* const* metrics_host, double da_min, double da_min_c, const double* phis_host, int nface = 0, const int* ij0 = nullptr);
   void destroy();
@@ -881,31 +888,49 @@ inline bool Dycore::init(int nx, int ny, int npz, int ntile, int face, int nq_, 
     nh_tape.adj = (double*)dev_alloc((size_t)nh_tape.cap * nh_tape.stride * 8);
     nh_tape.overflow = (int*)dev_alloc(8);
   }
+  plan_acoustic(false);
+  for (const char* n_ : st_in) acoustic_set.add(n_, f(n_), np);      // sizes over all resident tiles (set_class(-1) above)
+  acoustic_set.alloc("acoustic", n_split * k_split);
+  for (const char* n_ : {"pe", "peln", "pk", "pkz"}) slot_p_set.add(n_, f(n_), np);
+  return true;
+}
+
+// The acoustic program of every tile class and the work arena it lives in.  rebuild: the state fields exist and are found by name; the
+// work arena is sized and allocated anew.
+inline void Dycore::plan_acoustic(bool rebuild) {
   acoustic.c.assign(classes.size(), Program{}); acoustic.cur = &cur_cls;
   {   // the work arena is sized by a dry run of the builder: which fields exist depends on the options
     const size_t state_mark = state.used;
     const std::map<std::string, Fld> F_mark = F;
     work.measure();
-    set_class(0);
+    set_class(0); reuse_fields = rebuild;
     build_acoustic();
     const size_t need = work.used;
-    acoustic.clear(); n_win = 0; state.used = state_mark; nW3 = nW3p = nS3 = nS3p = 0; F = F_mark;
+    acoustic.clear(); n_win = 0; state.used = state_mark; nW3 = nW3p = 0; if (!rebuild) nS3 = nS3p = 0; F = F_mark;
     work.init(need);
   }
   std::map<double*, size_t> zero_ranges;
   for (int c = 0; c < (int)classes.size(); ++c) {       // one program per tile class, the fields shared
-    set_class(c); reuse_fields = c > 0; n_win = 0;
+    set_class(c); reuse_fields = rebuild || c > 0; n_win = 0;
     build_acoustic();
     std::vector<double*> pre; for (const char* n_ : st_out) pre.push_back(f(n_).p);
     for (auto& zr : plan_adjoint(acoustic, work, pre)) { auto it = zero_ranges.find(zr.first); if (it == zero_ranges.end() || it->second < zr.second) zero_ranges[zr.first] = zr.second; }
   }
   reuse_fields = false; set_class(-1);
   acoustic_zero.assign(zero_ranges.begin(), zero_ranges.end());
-  for (const char* n_ : st_in) acoustic_set.add(n_, f(n_), np);      // sizes over all resident tiles (set_class(-1) above)
-  acoustic_set.alloc("acoustic", n_split * k_split);
-  for (const char* n_ : {"pe", "peln", "pk", "pkz"}) slot_p_set.add(n_, f(n_), np);
   ex.wlo = work.t; ex.whi = work.t + work.cap;
-  return true;
+}
+// Between complete steps only (nothing of a step in flight lives in the work arena): the program again, for the options as they are now, in
+// a work arena of its new size; the trajectory slots, which are copies of that arena, are planned anew from the memory then free.
+// The caller re-points what it keeps inside the arena (Dynamics::set_external_damping).
+inline void Dycore::rebuild_acoustic() {
+  dev_sync(ex);
+  for (double* q_ : traj_slot) dev_free(q_);
+  traj_slot.clear(); slot_p_set.destroy();
+  for (auto it = F.begin(); it != F.end();) { if (it->second.t >= work.t && it->second.t < work.t + work.cap) it = F.erase(it); else ++it; }
+  work.destroy(); work = Arena{};
+  plan_acoustic(true);
+  init_traj_slots();
 }
 
 inline bool Dycore::set_face_data(const double* edge, const double* ecorner) {
@@ -1093,6 +1118,13 @@ inline void Dycore::build_acoustic() {
   Fld delpc = W("delpc", npz), ptc = W("ptc", npz);
   { CswTransportD s; s.in[0] = delp; s.in[1] = pt; s.in[2] = utf; s.in[3] = vtf; s.out[0] = delpc; s.out[1] = ptc;
     s.orect[0] = s.orect[1] = R(is - 1, ie + 1, js - 1, je + 1); s.k1 = npz; add_face(P, "c_sw", s, 1); }
+  // ---- external-mode divergence damping (dext.h), hydrostatic with d_ext > 0: the step's input delp at the corners (a2b_ord2, dyn_core_nlm.F90:641-644)
+  const bool dext = dext_on();
+  Fld dx_wk{}, dx_dvt{}, divg2{}, dx_w{};
+  if (dext) {
+    dx_wk = W("dext_wk", npz);
+    A2bOrd2D s; s.in[0] = delp; s.out[0] = dx_wk; s.orect[0] = R(is, ie + 1, js, je + 1); s.k1 = npz; add_face(P, "d_ext", s, 1);
+  }
   Fld wc{};
   if (nh) {
     wc = W("wc", npz);
@@ -1207,16 +1239,36 @@ inline void Dycore::build_acoustic() {
       need = need || (l.split_damp && (l.nord != l.nord_p || l.d2_divg != l.d2_divg_p || l.dddmp != l.dddmp_p || l.d4_bg != l.d4_bg_p)); }
     if (need) {
       Fld s1 = max_nord >= 1 ? W("ddt_s1", npz) : Fld{}, s2 = max_nord >= 2 ? W("ddt_s2", npz) : Fld{};
+      if (dext) dx_dvt = W("dext_dvt", npz);      // the trajectory pass's own nord_k = 0 divergence, otherwise local to its kernel
+      const Fld dvt = dx_dvt;
       Dycore* self = this;
-      Op op{"d_sw", [self, u, v, ua, va, uc, vc, divgd, vortb, ke, ke2, s1, s2, dt, max_nord](Exec& e, int) {
+      Op op{"d_sw", [self, u, v, ua, va, uc, vc, divgd, vortb, ke, ke2, s1, s2, dt, max_nord, dvt](Exec& e, int) {
         DampTArgs a; a.g = self->g; a.m = self->ctx.m; a.lev = self->lev_dev;
         a.u = e.sh(u).t; a.v = e.sh(v).t; a.ua = e.sh(ua).t; a.va = e.sh(va).t; a.uc = e.sh(uc).t; a.vc = e.sh(vc).t;
         a.divgd = e.sh(divgd).t; a.vortb = e.sh(vortb).t; a.ke = e.sh(ke).t; a.ke2 = e.sh(ke2).t; a.s1 = e.sh(s1).t; a.s2 = e.sh(s2).t; a.dt = dt;
+        a.dvt = e.sh(dvt).t;
         run_damp_t(e, a, max_nord);
       }};
       op.modes = (1u << MODE_NL) | (1u << MODE_TL); op.name = "DampT";
       P.push_back(op);
     } }
+  // the column mean divg2 of the undamped divergence (dyn_core_nlm.F90:707-727): after the last launch that touches the adjoints of dd_c and
+  // divg_d, so that its adjoint is the first of the backward sweep to write them -- it stores them, with the adjoint of the corner delp
+  if (dext) {
+    divg2 = W("divg2", 1); dx_w = W("dext_w", 1);
+    const Fld wkc = dx_wk, dvt = dx_dvt, d2 = divg2, ws = dx_w, dgf = opt.nord > 0 ? divgd : Fld{};
+    Dycore* self = this;
+    Op op{"d_ext", [self, wkc, dc, dgf, dvt, d2, ws](Exec& e, int mode) {
+      DextArgs a{}; a.g = self->g; a.lev = self->lev_dev; a.cfac = self->d_ext * self->ctx.m.da_min_c;
+      a.wk = e.sh(wkc); a.dc = e.sh(dc); a.dg = e.sh(dgf); a.dvt = e.sh(dvt).t; a.d2 = e.sh(d2); a.ws = e.sh(ws);
+      run_dext_col(e, mode, a);
+    }};
+    op.ad_in = {wkc.p, dc.p}; if (dgf.p) op.ad_in.push_back(dgf.p);
+    op.ad_store = op.ad_in;
+    op.ad_out = {d2.p}; op.ad_out_rect = {R(is, ie + 1, js, je + 1)};
+    op.name = "DextCol";
+    P.push_back(op);
+  }
   Fld fxv = W("fxv", npz), fyv = W("fyv", npz);
   build_tp(P, "d_sw", "tpv", vorta, crx, cry, xfx, yfx, rax, ray, xfx, yfx, Fld{}, HORD_VT, DAMP_NONE, false, fxv, fyv);
   Fld d6 = W("del6_d2", npz);
@@ -1288,9 +1340,32 @@ inline void Dycore::build_acoustic() {
   Fld pkb = W("pk_b", npz + 1), gzb = W("gz_b", npz + 1);
   build_a2b(P, "one_grad_p", "a2bp", pkd, pkb, npz + 1);
   build_a2b(P, "one_grad_p", "a2bg", gzd, gzb, npz + 1);
-  { OneGradP s; s.in[0] = u_m; s.in[1] = v_m; s.in[2] = pkb; s.in[3] = gzb; s.out[0] = u_o; s.out[1] = v_o;
+  if (!dext) {
+    OneGradP s; s.in[0] = u_m; s.in[1] = v_m; s.in[2] = pkb; s.in[3] = gzb; s.out[0] = u_o; s.out[1] = v_o;
     s.orect[0] = R(is, ie, js, je + 1); s.orect[1] = R(is, ie + 1, js, je); s.dt = dt; s.ptk = std::pow(opt.ptop, opt.akap); s.k1 = npz;
-    add(P, "one_grad_p", s); }
+    add(P, "one_grad_p", s);
+  } else {
+    // the same stage with divg2 as a one-level operand: like a stage input it is pointed at the step's trajectory slot / tile class at run time
+    typedef OneGradPT<true> St;
+    St s; s.in[0] = u_m; s.in[1] = v_m; s.in[2] = pkb; s.in[3] = gzb; s.out[0] = u_o; s.out[1] = v_o;
+    s.orect[0] = R(is, ie, js, je + 1); s.orect[1] = R(is, ie + 1, js, je); s.dt = dt; s.ptk = std::pow(opt.ptop, opt.akap); s.k1 = npz;
+    Ctx* cp = &ctx; const Fld d2 = divg2;
+    auto sp = std::make_shared<St>(s);
+    Op op{"one_grad_p", [sp, cp, d2](Exec& e, int mode) { St t = *sp; t.d2 = e.sh(d2); run(e, mode, t, *cp); }};
+    declare(op, s);
+    op.set_wmask = [sp](unsigned w, Rect r) { sp->wmask = w; sp->wrect = r; };
+    op.name = St::name();
+    P.push_back(op);
+    // adjoint of divg2 from the adjoints of the winds (after the adjoint exchange of u_o, v_o; before anything reads it)
+    Dycore* self = this;
+    Op ga{"one_grad_p", [self, u_o, v_o, d2](Exec& e, int) {
+      DextArgs a{}; a.g = self->g; a.uo = e.sh(u_o); a.vo = e.sh(v_o); a.d2 = e.sh(d2); a.rdx = self->ctx.m.rdx; a.rdy = self->ctx.m.rdy;
+      run_dext_grad_ad(e, a);
+    }};
+    ga.modes = 1u << MODE_AD; ga.ad_in = {d2.p}; ga.ad_store = {d2.p}; ga.ad_out = {u_o.p, v_o.p};
+    ga.ad_out_rect = {R(is, ie, js, je + 1), R(is, ie + 1, js, je)}; ga.name = "DextGradAd";
+    P.push_back(ga);
+  }
   // it < n_split: halo update of u, v (:2432-2434); last step: shared edge rows only, mpp_get_boundary (:2418-2431)
   add_halo(P, "halo_uv", H_DVEC, u_o, v_o, 1); add_halo(P, "halo_uv", H_DEDGE, u_o, v_o, 2);
 }

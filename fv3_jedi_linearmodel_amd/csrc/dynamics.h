@@ -151,6 +151,9 @@ struct Dynamics : Dycore {
   bool tr_damp = false;
   bool set_tracer_damping(int nord_tr, double trdm2, int nord_tr_pert, double trdm2_pert, int split_damp_tr);
   void rebuild_tracer();
+  // External-mode divergence damping (dext.h; fv3lm_set_external_damping): the acoustic program and the trajectory-slot plan are rebuilt
+  // when the damping goes on or off
+  bool set_external_damping(double d_ext);
   RfArgs rf_args();
   void rayleigh(int mode);
   // one field between the host's compact array and the device state.  which: 0 trajectory, 1 perturbation / adjoint
@@ -432,6 +435,32 @@ inline bool Dynamics::set_tracer_damping(int nord_tr, double trdm2, int nord_tr_
   h2d(ex, lev_dev, lev_host.data(), sizeof(LevelParams) * lev_host.size());
   tr_damp = d_t > 1.e-4;
   rebuild_tracer();
+  return true;
+}
+
+// fv3lm_set_external_damping.  The coefficient is read at run time; the program changes only when the damping goes on or off on a
+// hydrostatic handle: then the work arena moves, and with it what else lives in it -- pt_o as the output of pt_in, and the remap's column
+// workspace in its perturbation side.
+inline bool Dynamics::set_external_damping(double d) {
+  auto finite = [](double x) { volatile double v = x; const double y = v; uint64_t b; std::memcpy(&b, &y, 8); return ((b >> 52) & 0x7ffu) != 0x7ffu; };
+  if (!finite(d)) { err = "fv3lm_set_external_damping: d_ext must be finite"; return false; }
+  if (d < 0.) { err = "fv3lm_set_external_damping: d_ext < 0 (0 switches the damping off)"; return false; }
+  const bool was = dext_on();
+  d_ext = d;
+  if (dext_on() == was) return true;
+  rebuild_acoustic();
+  pt_in.c.assign(classes.size(), Program{});
+  for (int c = 0; c < (int)classes.size(); ++c) {
+    set_class(c);
+    DynPtIn s; s.in[0] = f("pt"); s.in[1] = nq > 0 ? q[0] : Fld{}; if (!s.in[1].t) s.in[1].nk = g.npz; s.in[2] = f("pkz"); s.out[0] = f("pt_o");
+    s.orect[0] = R(g.is(), g.ie(), g.js(), g.je()); s.k1 = g.npz; s.zvir = opt.zvir; s.has_q = nq > 0; add(pt_in, "pt_in", s);
+  }
+  set_class(-1);
+  if (!remap_ws_own) {
+    const size_t need = (size_t)remap_ws_slots(nq) * (g.npz + 2) * ntile_all * g.plane;
+    remap_ws_own = need > work.cap;
+    remap_ws = remap_ws_own ? (double*)dev_alloc(need * 8) : work.p;
+  }
   return true;
 }
 

@@ -114,6 +114,16 @@ int fv3lm_tracer_damping(fv3lm_handle* h, int* nord2, double* trdm2) {
   nord2[0] = l.nord_tr; nord2[1] = l.nord_tr_p; trdm2[0] = l.trdm2; trdm2[1] = l.trdm2_p;
   return 0;
 }
+int fv3lm_set_external_damping(fv3lm_handle* h, double d_ext) {
+  if (!h) return fail("fv3lm_set_external_damping: null handle");
+  if (!h->d.set_external_damping(d_ext)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_external_damping(fv3lm_handle* h, double* d_ext) {
+  if (!h || !d_ext) return fail("fv3lm_external_damping: null argument");
+  *d_ext = h->d.d_ext;
+  return 0;
+}
 int fv3lm_set_exchange(fv3lm_handle* h, int kind, const int* rows, int nrows) {
   if (!rows && nrows > 0) return fail("fv3lm_set_exchange: null table");
   return h->d.set_exchange(kind, rows, nrows) ? 0 : fail(h->d.err);

@@ -1457,8 +1457,18 @@ struct DynPtInNhRf {
 
 // one_grad_p wind update from corner pk, gz (dyn_core_tlm.F90:4128-4157); level 1 of pk is the
 // constant top value (:4068-4072).
-struct OneGradP {
-  STAGE_BASE("OneGradP", 4, 2)   // in: u v pk_b gz_b (npz+1)   out: u_n v_n
+// DEXT: with the external-mode divergence damping on (dext.h), wk2 = divg2(i,j) - divg2(i+1,j) and wk1 = divg2(i,j) - divg2(i,j+1) enter
+// the brackets (dyn_core_nlm.F90:1713-1741, :1762-1775).  divg2 has one level, so it is no stage input: the form without it is the stage as
+// it always was, and the adjoint of divg2 is gathered per corner column (dext.h DextGradAdFn) -- the term is additive, the derivatives of
+// the stage inputs do not see it.
+HD void dext_diff(const Fld& d, size_t n0, size_t n1, double& r) { r = d.t[n0] - d.t[n1]; }
+HD void dext_diff(const Fld& d, size_t n0, size_t n1, Dual& r) { r = Dual(d.t[n0] - d.t[n1], d.p[n0] - d.p[n1]); }
+template <int N> HD void dext_diff(const Fld&, size_t, size_t, DualV<N>& r) { r = DualV<N>(0.); }
+struct DextOperand { Fld d2; };      // divg2, one level per tile
+struct NoOperand {};
+template <bool DEXT>
+struct OneGradPT : std::conditional<DEXT, DextOperand, NoOperand>::type {
+  STAGE_BASE(DEXT ? "OneGradPd" : "OneGradP", 4, 2)   // in: u v pk_b gz_b (npz+1)   out: u_n v_n
   STAGE_NO_ALIAS
   double dt, ptk;
   HD static constexpr bool uses(int M, int di, int dj, int) { return M < 2 || !(di == 1 && dj == 1); }
@@ -1475,15 +1485,24 @@ struct OneGradP {
     if ((a.want & 0x1u) && orect[0].has(i, j)) {
       T p10 = pk<T>(a, i + 1, j, k, 0), p11 = pk<T>(a, i + 1, j, k, 1);
       T g10 = IN(3, i + 1, j, 0), g11 = IN(3, i + 1, j, 1);
+      if constexpr (DEXT) {
+        const size_t d0 = (size_t)tile * c.g.plane + c.g.idx(i, j); T wk2; dext_diff(this->d2, d0, d0 + 1, wk2);
+        o[0] = MET(rdx, i, j) * (wk2 + IN(0, i, j) + dt / (wk0 + (p11 - p10)) * ((g01 - g10) * (p11 - p00) + (g00 - g11) * (p01 - p10)));
+      } else
       o[0] = MET(rdx, i, j) * (IN(0, i, j) + dt / (wk0 + (p11 - p10)) * ((g01 - g10) * (p11 - p00) + (g00 - g11) * (p01 - p10)));
     }
     if ((a.want & 0x2u) && orect[1].has(i, j)) {
       T p10 = pk<T>(a, i, j + 1, k, 0), p11 = pk<T>(a, i, j + 1, k, 1);
       T g10 = IN(3, i, j + 1, 0), g11 = IN(3, i, j + 1, 1);
+      if constexpr (DEXT) {
+        const size_t d0 = (size_t)tile * c.g.plane + c.g.idx(i, j); T wk1; dext_diff(this->d2, d0, d0 + (size_t)c.g.pi, wk1);
+        o[1] = MET(rdy, i, j) * (wk1 + IN(1, i, j) + dt / (wk0 + (p11 - p10)) * ((g01 - g10) * (p11 - p00) + (g00 - g11) * (p01 - p10)));
+      } else
       o[1] = MET(rdy, i, j) * (IN(1, i, j) + dt / (wk0 + (p11 - p10)) * ((g01 - g10) * (p11 - p00) + (g00 - g11) * (p01 - p10)));
     }
   }
 };
+typedef OneGradPT<false> OneGradP;
 
 // ===================================================================== non-hydrostatic stages
 // c_sw: w carried by the upwind mass fluxes of delp (sw_core_tlm.F90:758-778, :812-838); corner halo of delp and w through
@@ -1666,7 +1685,7 @@ struct NhPGrad {
 
 // level classes for the joint adjoint (exec.h): pkc/gz and pk_b/gz_b carry npz+1 levels, the winds npz
 constexpr int kclass_of(const PGradC*, int M) { return M < 2 ? 1 : 0; }
-constexpr int kclass_of(const OneGradP*, int M) { return M < 2 ? 0 : 1; }
+template <bool D> constexpr int kclass_of(const OneGradPT<D>*, int M) { return M < 2 ? 0 : 1; }
 constexpr int kclass_of(const PGradCNh*, int M) { return M < 2 ? 1 : 0; }
 constexpr int kclass_of(const NhPGrad*, int M) { return M < 3 ? 0 : 1; }
 

@@ -33,6 +33,7 @@ class Case:
         the real gnomonic metrics of that face and arbitrary smooth halo data (kernel-group tests).
         tau=, rf_cutoff=: Rayleigh damping of the upper layers (fv3lm_set_rayleigh; off by default).
         nord_tr=, trdm2=, nord_tr_pert=, trdm2_pert=, split_damp_tr=: tracer damping (fv3lm_set_tracer_damping; never called by default).
+        d_ext=: external-mode divergence damping (fv3lm_set_external_damping; never called by default).
         levels=(ak, bk): hybrid coefficients [npz+1] in place of grid.hybrid_levels; the state's delp follows them at the same ps.
         metrics_hook (face cases): callable(metrics, edge, ecorner) applied to the metric dict [1, pj, pi] and the a2b edge data of the
         face before the library instance (and the oracle) are created; it changes them in place or returns the three to use instead.
@@ -41,6 +42,7 @@ class Case:
         self.tau, self.rf_cutoff = optkw.pop("tau", 0.0), optkw.pop("rf_cutoff", 0.0)
         levels = optkw.pop("levels", None)
         self.tracer_damping = _pop_tracer_damping(optkw)
+        self.d_ext = optkw.pop("d_ext", None)
         self.opt = default_options(**optkw)
         self.face = face
         if face is None:
@@ -87,6 +89,8 @@ class Case:
             self.dy.set_rayleigh(self.tau, self.rf_cutoff, self.c2l)
         if self.tracer_damping is not None:
             self.dy.set_tracer_damping(**self.tracer_damping)
+        if self.d_ext is not None:
+            self.dy.set_external_damping(self.d_ext)
 
     # hooks of tests/common.py (oracle as checker, host-emulation backend); the package itself knows the HIP library only
     def _make_oracle(self):
@@ -141,6 +145,7 @@ class CubeCase:
         self.tau, self.rf_cutoff = optkw.pop("tau", 0.0), optkw.pop("rf_cutoff", 0.0)
         levels = optkw.pop("levels", None)
         self.tracer_damping = _pop_tracer_damping(optkw)
+        self.d_ext = optkw.pop("d_ext", None)
         self.opt = default_options(**optkw)
         self.metrics, self.da_min, self.da_min_c, self.edge, self.ecorner, self.geo = cube.cubed_sphere_metrics(n, edge_forms=edge_forms)
         self.c2l = self.geo["c2l"]
@@ -199,6 +204,8 @@ class CubeCase:
             self.dy.set_rayleigh(self.tau, self.rf_cutoff, self.c2l)
         if self.tracer_damping is not None:
             self.dy.set_tracer_damping(**self.tracer_damping)
+        if self.d_ext is not None:
+            self.dy.set_external_damping(self.d_ext)
         for k, t in self.tables.items():
             if world > 1 or loopback:
                 self.dy.set_exchange_split(k, t, rank, world, ntiles, loopback)

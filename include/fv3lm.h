@@ -116,6 +116,22 @@ int fv3lm_rayleigh_profile(fv3lm_handle* h, double* rf, int* kmax);
 int fv3lm_set_tracer_damping(fv3lm_handle* h, int nord_tr, double trdm2, int nord_tr_pert, double trdm2_pert, int split_damp_tr);
 /* The effective pairs after the first rule above: nord2 = {nord_tr, nord_tr_pert}, trdm2 = {trdm2, trdm2_pert} (tests, diagnostics). */
 int fv3lm_tracer_damping(fv3lm_handle* h, int* nord2, double* trdm2);
+/* External-mode divergence damping of the acoustic step (dyn_core_nlm.F90:641-644, :678-684, :707-727; dyn_core_tlm.F90:937-943,
+ * :999-1007, :1031-1060; consumed by one_grad_p, dyn_core_nlm.F90:1713-1741, :1762-1775).  d_ext: flagstruct%d_ext (the reference's
+ * default is 0.02; 0 switches it off, the default HERE -- a host passes its flagstruct%d_ext).  Per acoustic step: the step's input delp at
+ * the cell corners (a2b_ord2), the corner divergence d_sw sees before any damping (with split_damp its value from the trajectory's
+ * nord, its tangent / adjoint from nord_pert, level by level), their delp-weighted column mean divg2 = d_ext da_min_c sum(wk vt) / sum(wk),
+ * and its differences inside the brackets of one_grad_p's wind update -- nonlinear, tangent and adjoint.
+ * Call after fv3lm_create, before the first step; may be called again between complete steps.  Going from 0 to > 0 or back rebuilds the
+ * acoustic program and with it the plan of the trajectory slots of the backward sweep; a handle that never calls it, or calls it with
+ * 0, runs exactly the launches it ran without.  Refused, the handle left as it was: d_ext < 0, a value that is not finite.
+ * Non-hydrostatic handle: accepted and remembered, no launch added -- with beta = 0 the pressure gradient is nh_p_grad, which never reads
+ * divg2 (dyn_core_nlm.F90:871-880), so d_ext changes no output there.
+ * While it is on, fv3lm_field_get knows "divg2" (one level; corners is..ie+1, js..je+1 of the last acoustic step; value and tangent after
+ * a tangent-linear sweep). */
+int fv3lm_set_external_damping(fv3lm_handle* h, double d_ext);
+/* d_ext as set (0 on a handle that never called the setter). */
+int fv3lm_external_damping(fv3lm_handle* h, double* d_ext);
 /* Halo exchange between the resident faces: replaces the FMS calls mpp_update_domains / mpp_get_boundary that the
  * reference issues from DYN_CORE_TLM (dyn_core_tlm.F90:1744-1790, :1960-1990, :2280-2300, :2418-2434) and
  * FV_DYNAMICS_TLM (fv_dynamics_tlm.F90:646-651, :708-712).  One table per kind of exchange:

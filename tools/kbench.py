@@ -1,6 +1,6 @@
 """Kernel-level timing on the MI355X: the headline workload (six C192 L127 faces) or a smaller one, one step_tl + step_nl + step_ad under the
 library's HIP-event profiler, per-kernel table filtered by name.  Usage: python tools/kbench.py [--lib path.so] [--nx 192] [--npz 127] [--grep Tp]
-[--tau 10 --rf-cutoff 750] (Rayleigh damping of the upper layers on)
+[--tau 10 --rf-cutoff 750] (Rayleigh damping of the upper layers on) [--d-ext 0.02] (external-mode divergence damping on)
 Variants of one translation unit are compared by linking them into differently named libraries (FV3LM_LIB)."""
 import argparse
 import os
@@ -22,6 +22,7 @@ def main():
     ap.add_argument("--nh", action="store_true")
     ap.add_argument("--tau", type=float, default=0.0, help="Rayleigh damping e-folding time in days (0: off)")
     ap.add_argument("--rf-cutoff", type=float, default=750.0, help="Rayleigh damping cutoff pressure (Pa)")
+    ap.add_argument("--d-ext", type=float, default=0.0, help="external-mode divergence damping coefficient (0: the setter is never called)")
     ap.add_argument("--group", default="", help="after one ordinary step: time this kernel group alone (TL and NL), e.g. d_sw")
     ap.add_argument("--ad", action="store_true", help="group mode: time the adjoint of the group instead of TL + NL")
     ap.add_argument("--experiment", default="", help="comma list of FV3LM_TP2_EXPERIMENT values to time the group with (experiment builds only)")
@@ -32,6 +33,8 @@ def main():
     kw = dict(hydrostatic=0) if args.nh else {}
     if args.tau > 0:
         kw.update(tau=args.tau, rf_cutoff=args.rf_cutoff)
+    if args.d_ext > 0:
+        kw.update(d_ext=args.d_ext)
     c = CubeCase(n=args.nx, npz=args.npz, n_split=6, k_split=2, dt=450.0, backend="hip", nq=args.nq, **kw)
     T, P = cube_step_state(c)
     if args.nh:
@@ -68,6 +71,10 @@ def main():
     print("lib %s: %.1f ms per TL+AD step (kernel time %.1f ms, %d launches)" % (args.lib or "default", 1e3 * dt, tot, sum(v[0] for v in prof.values())))
     if args.tau > 0:
         print("Rayleigh damping: tau %g days, rf_cutoff %g Pa, kmax %d of %d levels" % (args.tau, args.rf_cutoff, c.dy.rayleigh_profile()[1], args.npz))
+    if args.d_ext > 0:
+        added = [k for k in prof if "dext" in k or "A2bOrd2" in k]
+        ms = sum(prof[k][1] for k in added)
+        print("external damping: d_ext %g, %d added launches, %.3f ms = %.2f %% of the kernel time" % (c.dy.external_damping(), sum(prof[k][0] for k in added), ms, 100. * ms / tot))
     rows = sorted(prof.items(), key=lambda kv: -kv[1][1])
     if args.grep:
         rows = [r for r in rows if any(g in r[0] for g in args.grep.split(","))]
