@@ -19,6 +19,7 @@
 #include "tp2.h"
 #include "dampt.h"
 #include "dext.h"
+#include "a2b.h"
 #include <functional>
 #include <map>
 #include <memory>
@@ -654,9 +655,32 @@ struct Dycore {
     const int npx = g.nx + 1, npy = g.ny + 1;
     A2bA_<false> a; a.in[0] = q; a.out[0] = qx; a.out[1] = qy; a.k1 = nk;
     A2bB_<false> b; b.in[0] = qx; b.in[1] = qy; b.in[2] = Fld{}; b.out[0] = qb; b.k1 = nk;
+    // the bulk as one LDS-tiled launch per mode (a2b.h); FV3LM_A2B_FUSED=0: the two staged launches
+    const char* fenv = std::getenv("FV3LM_A2B_FUSED");
+    const bool fuse_on = !(fenv && fenv[0] == '0') && q.nk == nk && qb.nk == nk;
+    auto same = [](const Rect& x, const Rect& y) { return x.i0 == y.i0 && x.i1 == y.i1 && x.j0 == y.j0 && x.j1 == y.j1; };
+    A2bArgs fa; fa.q = q; fa.qb = qb; fa.qx = qx; fa.qy = qy; fa.nk = nk; fa.rim = g.face ? 1 : 0;
+    // the fused launch derives the rectangles of qx, qy from the one of qb: it stands in where the staged rectangles are those (every
+    // periodic tile, whole face and window of a face wider than the stencil), the staged launches stay otherwise
+    auto fusable = [&]() { fa.rb = b.orect[0]; return fuse_on && !is_empty(fa.rb) && same(a.orect[0], fa.rx()) && same(a.orect[1], fa.ry()); };
+    auto add_fused = [&]() {
+      Ctx* cp = &ctx;
+      auto ap = std::make_shared<A2bArgs>(fa);
+      Op op{grp, [ap, cp](Exec& e, int mode) { run_a2b(e, mode, *ap, *cp); }};
+      op.name = "A2b";
+      if (q.p) { op.ad_in = {q.p}; op.ad_in_slot = {0}; }
+      op.ad_out = {qb.p}; op.ad_out_rect = {fa.rb};
+      if (fa.rim) { op.ad_out.push_back(qx.p); op.ad_out.push_back(qy.p); op.ad_out_rect.push_back(fa.rx()); op.ad_out_rect.push_back(fa.ry()); }
+      op.set_wmask = [ap](unsigned w, Rect r) { ap->wmask = w; ap->wrect = r; };
+      P.push_back(op);
+    };
     if (!g.face) {
-      a.orect[0] = R(is, ie + 1, js - 2, je + 2); a.orect[1] = R(is - 2, ie + 2, js, je + 1); add(P, grp, a);
-      b.orect[0] = R(is, ie + 1, js, je + 1); add(P, grp, b);
+      a.orect[0] = R(is, ie + 1, js - 2, je + 2); a.orect[1] = R(is - 2, ie + 2, js, je + 1);
+      b.orect[0] = R(is, ie + 1, js, je + 1);
+      const bool fuse = fusable();
+      add(P, grp, a); if (fuse) P.back().modes = 0;
+      add(P, grp, b); if (fuse) P.back().modes = 0;
+      if (fuse) add_fused();
       return;
     }
     // faces: the 4-point formulas away from the cube edges, the edge formulas on strips two points wide (column strips run with the wave
@@ -675,9 +699,13 @@ struct Dycore {
       ae.orect[e < 2 ? 0 : 1] = r; ae.orect[e < 2 ? 1 : 0] = empty_in(r); av.push_back(ae);
     }
     add_multi(P, grp, av);
-    if (a0 || a1) add(P, grp, a);            // bulk last: first in the backward sweep (plan_adjoint)
     const Rect qbr = R(is, ie + 1, js, je + 1);
     b.orect[0] = isect(qbr, R(3, npx - 2, 3, npy - 2));
+    // Fused: the bulk launch stands between the two sets of strips -- forward it leaves the rim of qx, qy for the B strips, backward it
+    // runs after their adjoint and reads what they accumulated there
+    const bool fuse = a0 && a1 && fusable();
+    if (a0 || a1) { add(P, grp, a); if (fuse) P.back().modes = 0; }            // bulk last: first in the backward sweep (plan_adjoint)
+    if (fuse) add_fused();
     A2bB_<true> be; be.in[0] = qx; be.in[1] = qy; be.in[2] = q; be.out[0] = qb; be.k1 = nk;
     std::vector<A2bB_<true>> bv;
     for (int e = 0; e < 4; ++e) {
@@ -686,7 +714,18 @@ struct Dycore {
       be.orect[0] = r; bv.push_back(be);
     }
     add_multi(P, grp, bv);
-    if (!is_empty(b.orect[0])) add(P, grp, b);
+    if (!is_empty(b.orect[0])) { add(P, grp, b); if (fuse) P.back().modes = 0; }
+    if (fuse && qx.p && qy.p) {
+      // first in the backward sweep: the strips' adjoint accumulates into qx_ad, qy_ad next to the cube edges, and nothing stores them
+      // before it now that the staged bulk adjoint is gone -- one thin launch stores the zeros (Op::ad_store) on the bands within four of
+      // an edge, which hold the rim and the outputs of the A strips
+      Ctx* cp = &ctx;
+      const Rect both[2] = {qxr, qyr}; const Rect frame = rect_union(both, 2);
+      Op z{grp, [fa, frame, cp](Exec& e, int) { run_a2b_rim_clear(e, fa, frame, *cp); }};
+      z.modes = 1u << MODE_AD; z.name = "A2bRim";
+      z.ad_in = {qx.p, qy.p}; z.ad_store = {qx.p, qy.p};
+      P.push_back(z);
+    }
   }
 
   // external-mode divergence damping (dext.h; fv3lm_set_external_damping): flagstruct%d_ext, 0 = off.  The hydrostatic step carries its

@@ -33,6 +33,13 @@ def short(name):
     m = re.search(r"k_tp2<(fv3::Dual|double)", name)
     if m:       # fv_tp_2d as one launch, wavefront layout (tp2.h): the same profile name as the first form
         return "TpFused.%s" % ("tl" if "Dual" in m.group(1) else "nl")
+    m = re.search(r"k_a2b<(fv3::Dual|double)", name)
+    if m:       # the bulk of a2b_ord4 as one launch (a2b.h)
+        return "A2b.%s" % ("tl" if "Dual" in m.group(1) else "nl")
+    if "k_a2b_ad" in name:
+        return "A2b.ad"
+    if "k_a2b_rim_clear" in name:
+        return "A2bRim.ad"
     if "k_zero16" in name:         # field-sized clears (dycore.h dev_zero)
         return "clear"
     if "k_tp_ad_corner" in name:   # corner-alias contributions of the fused adjoint (tpad.h)
