@@ -1,5 +1,7 @@
 """The face-edge operators of the product, point by point, against tests/face_oracle.py: the restatement of d2a2c_vect, divergence_corner,
-the area-flux scaling of c_sw, the first loops of d_sw, a2b_ord4 / one_grad_p and p_grad_c written from the reference's nonlinear
+the area-flux scaling of c_sw and what follows it (transport of delp, pt, kinetic energy, vorticity, wind update: c_sw_rest), the first
+loops of d_sw and what follows them (B-grid winds, xtp_u / ytp_v, kinetic energy, vorticity, divergence damping, del6_vt_flux:
+d_sw_rest, with u_m, v_m by composition), a2b_ord4 / one_grad_p and p_grad_c written from the reference's nonlinear
 Fortran (whole faces: check; six faces cut into tiles: check_layout).  The library receives
 the RESTATEMENT's metrics (harness metrics_hook), with 1e30 in every entry the reference leaves undefined, so product and reference share
 the corner points and nothing else.  Values and tangent through put / run_group(TL) / get; the adjoint with seeds on the compared outputs
@@ -48,6 +50,15 @@ def restatement_hook(n, face=None, value=1.0e30):
     return hook
 
 
+def detuned(M):
+    """sin_sg<k>, cos_sg<k> scaled by factors of their own (1 + 0.01 k, 1 - 0.005 k).  On the gnomonic cube the two cells across a face
+    edge hold the same angle, sin_sg(i, j-1, 4) = sin_sg(i, j, 2) to rounding, so which of the two a branch selects cannot show on the
+    true metrics; with these factors it does.  The planes stop being a geometry, which no operator here minds: product and restatement
+    get the same numbers."""
+    f = lambda k: (1 + 0.01 * int(k[-1])) if k.startswith("sin_sg") else (1 - 0.005 * int(k[-1])) if k.startswith("cos_sg") else 1.0
+    return {k: v * f(k) for k, v in M.items()}
+
+
 regions, region_errors = G.regions, G.region_errors
 
 
@@ -69,7 +80,7 @@ def both_signs(vals):
     return bool((vals > 0).any() and (vals < 0).any() and np.all(np.abs(vals) > 1e-6 * big))
 
 
-# ------------------------------------------------------------------------------------------------------------ the three operators
+# ------------------------------------------------------------------------------------------------------------ the operators
 class CSw:
     level_local = True
     group, ins = "c_sw", ["u", "v"]
@@ -185,8 +196,231 @@ class DSw:
         return all(both_signs(np.real(r)) for r in rows)
 
 
-OPERATORS = {"c_sw": CSw, "one_grad_p": OneGradP, "p_grad_c": PGradC, "d_sw": DSw}
-GHOST_FREE = ("pk", "gzd", "pkc", "gz")     # geopk outputs: the corner-halo columns hold no data; NaN for the restatement, 1e30 for the library
+class CSwRest:
+    """c_sw after the area fluxes (sw_core_nlm.F90:177-486): delp, pt, u, v -> delpc, ptc, the C-grid kinetic energy and absolute
+    vorticity, the time-centred winds uc1, vc1 and the d2a2c_vect winds uc0, vc0 they start from.  The operator's name in OPERATORS is
+    not the library's group: the whole group c_sw runs and the work fields are read back."""
+    level_local = True
+    group, ins = "c_sw", ["delp", "pt", "u", "v"]
+    outs = [("delpc", "Ah"), ("ptc", "Ah"), ("ke_c", "Ah"), ("vort_c", "B"), ("uc1", "V"), ("vc1", "U"), ("uc0", "UTF"), ("vc0", "VTF")]
+
+    def __init__(self, c):
+        self.n, self.dt2 = c.nx, 0.5 * c.dt_ac
+
+    def fixed(self, c):
+        return {}
+
+    def draw(self, c, rng):
+        shp = (c.npz, c.ny + 7, c.nx + 7)
+        T = dict(delp=1.0e3 * (1 + noise(rng, shp, 0.1)), pt=300.0 * (1 + noise(rng, shp, 0.05)), u=noise(rng, shp, 10.0), v=noise(rng, shp, 10.0))
+        P = dict(delp=noise(rng, shp, 10.0), pt=noise(rng, shp, 1.0), u=noise(rng, shp, 1.0), v=noise(rng, shp, 1.0))
+        return T, P
+
+    def apply(self, x, M, edge, ecorner):
+        return fo.c_sw_rest(x["delp"], x["pt"], x["u"], x["v"], M, self.n, self.dt2)
+
+    def signs_ok(self, x, M, edge, ecorner):
+        """both signs, none near zero, of: ut, vt on every edge row and corner block (the upwind cell of the transport, CSw.signs_ok);
+        ua on the columns 0, 1, npx-1, npx and va on the rows 0, 1, npy-1, npy (the sin_sg / cos_sg forms of the kinetic energy,
+        :318-353), whole and in each corner block; the vorticity-flux winds fy1 on the columns 1, npx and fx1 on the rows 1, npy (:438, :453)"""
+        if not CSw.signs_ok(self, x, M, edge, ecorner):
+            return False
+        o, n = self.apply(x, M, edge, ecorner), self.n
+        npx = n + 1
+        rows = []
+        for i in (0, 1, npx - 1, npx):
+            rows += [fo.V(o["ua"], i, i, 1, n), fo.V(o["va"], 1, n, i, i)]
+            rows += [fo.V(o["ua"], i, i, 1, 3), fo.V(o["ua"], i, i, n - 2, n), fo.V(o["va"], 1, 3, i, i), fo.V(o["va"], n - 2, n, i, i)]
+        for i in (1, npx):
+            rows += [fo.V(o["fy1v"], i, i, 1, n), fo.V(o["fx1v"], 1, n, i, i)]
+        return all(both_signs(np.real(r)) for r in rows)
+
+
+CAP = 0.20
+
+
+class CSwRestNh(CSwRest):
+    """c_sw_rest on a non-hydrostatic case: w joins the inputs (fill_4corners, sw_core_nlm.F90:211, :258) and wc the outputs (:280-281)"""
+    ins = CSwRest.ins + ["w"]
+    outs = CSwRest.outs + [("wc", "Ah")]
+
+    def draw(self, c, rng):
+        T, P = CSwRest.draw(self, c, rng)
+        shp = T["u"].shape
+        T["w"], P["w"] = noise(rng, shp, 1.0), noise(rng, shp, 0.1)
+        return T, P
+
+    def apply(self, x, M, edge, ecorner):
+        return fo.c_sw_rest(x["delp"], x["pt"], x["u"], x["v"], M, self.n, self.dt2, w=x["w"])
+
+
+class DSwRest:
+    """d_sw after its first loops (sw_core_nlm.F90:898-907, :1047-1221, :1260-1434, :1449-1470, :1487-1490): u, v, uc, vc, ua, va, divgd ->
+    ra_x, ra_y, the B-grid winds vb, ub, the kinetic energy ke, wk, vort_abs, the divergence dd_c, the corner vorticity vort_b, the damped
+    kinetic energy ke2 and the del-4 Laplacian del6_d2 (on the levels whose vorticity damping runs nord_v = 1).  u_m, v_m by composition
+    (`compose`): the restated last statements fed the restatement's own ke2 and del6 fluxes and the product's fxv, fyv as data.
+    Every level carries two parameter sets, restated (fo.level_rules, fo.level_rules_pert) and held to the library's: the trajectory's
+    and the perturbation's.  The linearised model differentiates the damping with the perturbation's set: with split_damp = 0 its
+    divergence damping is the trajectory's, its vorticity damping still its own; with split_damp = 1 the VALUES of ke2 (and of u_m, v_m)
+    are the trajectory's damping -- nord up to 3, the loop with fill_corners -- and every tangent and adjoint the perturbation's.
+    The winds of every level are scaled so that the argument x of max(d2_bg, min(0.20, dddmp x)) straddles the floor / linear switch
+    (amplify > 1: the 0.20 cap)."""
+    level_local = True
+    per_level = True                 # apply takes level0: the level a one-level slice stands for
+    group, ins = "d_sw", ["u", "v", "uc", "vc", "ua", "va", "divgd"]
+    outs = [("ra_x", "RAX"), ("ra_y", "RAY"), ("vb", "B"), ("ub", "B"), ("ke", "B"), ("wk", "cells"), ("vort_abs", "cells"), ("vort_b", "B"),
+            ("dd_c", "B"), ("ke2", "B"), ("del6_d2", "Ah")]
+    composed = [("u_m", "U"), ("v_m", "V")]
+    amplify = 1.0
+
+    def __init__(self, c):
+        self.n, self.dt, self.da_min_c, self.npz = c.nx, c.dt_ac, c.da_min_c, c.npz
+        o = c.opt
+        self.par, self.parp = [], []
+        for k in range(1, c.npz + 1):
+            ks = k <= o.n_sponge_pert - 1 and o.hord_ks_pert            # model_tlmadm/dyn_core_tlm.F90:862-875
+            iord = o.hord_mt_ks_pert if ks else o.hord_mt_pert
+            t = dict(fo.level_rules(o, k, c.npz), dddmp=o.dddmp, d4_bg=o.d4_bg, iord=iord)
+            q = dict(fo.level_rules_pert(o, k), dddmp=o.dddmp_pert, d4_bg=o.d4_bg_pert, iord=iord)
+            if not o.split_damp:        # run_setup_pert has made the two namelists equal; the divergence damping then takes the trajectory's level rule
+                q.update(nord=t["nord"], d2_divg=t["d2_divg"], dddmp=t["dddmp"], d4_bg=t["d4_bg"])
+            dy = getattr(c, "dy", None)
+            if dy is not None:          # the restated level rules against the library's
+                ip, rp = dy.level_params(k)
+                assert (ip[0], ip[5], ip[6], ip[9]) == (iord, t["nord"], t["nord_v"], q["nord_v"]), (k, ip, t, q)
+                assert (rp[0], rp[1], rp[5]) == (t["d2_divg"], t["damp_vt"], q["damp_vt"]), (k, rp, t, q)
+            assert iord in (1, 2) and t["nord"] in (0, 1, 2, 3) and q["nord"] in (0, 1), (t, q)
+            self.par.append(t); self.parp.append(q)
+        self.face = c.face if isinstance(c.face, int) else None
+        self._next = 0
+
+    def forms(self):
+        """(trajectory nord, perturbation nord, iord, trajectory nord_v) of each level, from the level parameters"""
+        return [(t["nord"], q["nord"], t["iord"], t["nord_v"]) for t, q in zip(self.par, self.parp)]
+
+    def levels_of(self, name):
+        if name == "del6_d2":       # the reference forms the inner Laplacian where a vorticity damping with nord_v = 1 runs
+            return [l for l, (t, q) in enumerate(zip(self.par, self.parp))
+                    if (t["nord_v"] == 1 and t["damp_vt"] > 1.0e-5) or (q["nord_v"] == 1 and q["damp_vt"] > 1.0e-5)]
+        return None
+
+    def fixed(self, c):
+        out = {"delp": c.traj["delp"][0], "pt": c.traj["pt"][0]}
+        out.update({k: np.zeros((c.npz, c.ny + 7, c.nx + 7)) for k in ("mfx", "mfy", "cx", "cy")})
+        return out
+
+    def draw(self, c, rng):
+        n, npz = self.n, self.npz
+        shp = (npz, n + 7, n + 7)
+        face = self.face if self.face is not None else self._next % 6
+        self._next += 1
+        unit = {k: noise(rng, shp, 1.0) for k in self.ins[:-1]}
+        d6 = noise(rng, (6, n + 7, n + 7, npz), n / 1.0e7)              # a divergence: wind / grid length; the halo by the data motion of the
+        fo._update_domains(n, "corner", d6)                             # corner-scalar exchange on six faces
+        unit["divgd"] = np.ascontiguousarray(np.moveaxis(d6[face], -1, 0))
+        x = self.apply(unit, *face_metrics_of(n, face, np.float64))["smag_x"]
+        T, P = {k: np.empty(shp) for k in self.ins}, {k: np.empty(shp) for k in self.ins}
+        for l, p in enumerate(self.parp):
+            xs = p["d2_divg"] / p["dddmp"]
+            xl = np.sort(np.abs(fo.V(x[l], 1, n + 1, 1, n + 1)).ravel())
+            q = int(0.45 * xl.size)                                     # the switch between two neighbours of the sorted x, clear of both
+            if self.amplify > 1.0:                                      # the cap draw: the same quantile of x on the cap's switch instead
+                xs = CAP / p["dddmp"]
+            amp = xs / np.sqrt(xl[q] * xl[q + 1]) if (p["d2_divg"] < CAP or self.amplify > 1.0) else 0.5 / xl[xl.size // 2]
+            for k in self.ins:
+                T[k][l] = amp * unit[k][l]
+                P[k][l] = 0.1 * amp * rng.standard_normal(shp[1:]) * (n / 1.0e7 if k == "divgd" else 1.0)
+        return T, P
+
+    def _level(self, x, l, p, M, edge, ecorner):
+        return fo.d_sw_rest_level(*[x[k][..., l, :, :] for k in self.ins], M, edge, ecorner, self.n, self.dt, self.da_min_c, p)
+
+    def apply(self, x, M, edge, ecorner, level0=0):
+        """the perturbation's chain on every level (values, and the imaginary part that check() reads as tangent and adjoint); where the
+        trajectory's divergence damping differs (split_damp), the real part of ke2 from the trajectory's"""
+        lv = []
+        for l in range(x["u"].shape[-3]):
+            t, q = self.par[level0 + l], self.parp[level0 + l]
+            o = self._level(x, l, q, M, edge, ecorner)
+            if any(t[k] != q[k] for k in ("nord", "d2_divg", "dddmp", "d4_bg")):
+                ot = self._level(x, l, t, M, edge, ecorner)
+                o["ke2"] = np.real(ot["ke2"]) + 1j * np.imag(o["ke2"]) if np.iscomplexobj(o["ke2"]) else ot["ke2"]
+            lv.append(o)
+        return {k: np.stack([o[k] for o in lv], axis=-3) for k in lv[0]}
+
+    def compose(self, x, fxv, fyv, M, edge, ecorner):
+        """u_m, v_m (:1474-1483, :1527-1539) from the restatement's ke2 and del6 fluxes and the given fxv, fyv.  The values with the
+        trajectory's vorticity damping; the tangent (imaginary part) with the perturbation's nord_v, damp_vt where the two differ."""
+        o = self.apply(x, M, edge, ecorner)
+        us, vs = [], []
+        for l in range(x["u"].shape[-3]):
+            t, q, L_ = self.par[l], self.parp[l], (lambda a: a[..., l, :, :])
+
+            def momentum(p):
+                fx2 = fy2 = None
+                if p["damp_vt"] > 1.0e-5:
+                    _, fx2, fy2 = fo.del6_vt_flux(p["nord_v"], (p["damp_vt"] * self.da_min_c) ** (p["nord_v"] + 1), L_(o["wk"]), M, self.n)
+                return fo.d_sw_momentum(L_(x["u"]), L_(x["v"]), L_(o["ke2"]), L_(fxv), L_(fyv), fx2, fy2, M, self.n, p["damp_vt"])
+            a, b = momentum(t)
+            if (q["nord_v"], q["damp_vt"]) != (t["nord_v"], t["damp_vt"]):
+                ap, bp = momentum(q)
+                a, b = np.real(a) + 1j * np.imag(ap), np.real(b) + 1j * np.imag(bp)
+            us.append(a); vs.append(b)
+        return dict(u_m=np.stack(us, axis=-3), v_m=np.stack(vs, axis=-3))
+
+    def branch_fractions(self, o):
+        """{(level, region): (floor, linear, cap)}: the fractions of the corner points 1..npx, 1..npy of the region on which each branch of
+        max(d2_bg, min(0.20, dddmp x)) is taken, on every level whose floor lies under the cap (a sponge level with d2_bg = 0.20 has no
+        linear branch); and whether every point is clear of a switch"""
+        n = self.n
+        reg = regions(n, (1, n + 1, 1, n + 1))
+        out, clear = {}, True
+        for l in range(o["smag_x"].shape[0]):
+            p = self.parp[l]
+            if p["d2_divg"] >= CAP:
+                continue
+            y = p["dddmp"] * np.real(o["smag_x"][l]).astype(np.float64)
+            for sw in (p["d2_divg"], CAP):
+                clear = clear and bool(np.all(np.abs(fo.V(y, 1, n + 1, 1, n + 1) - sw) > 1.0e-6 * sw))
+            for name, m in reg.items():
+                v = y[m]
+                out[(l, name)] = (float(np.mean(v <= p["d2_divg"])), float(np.mean((v > p["d2_divg"]) & (v < CAP))), float(np.mean(v >= CAP)))
+        return out, clear
+
+    def signs_ok(self, x, M, edge, ecorner):
+        """On the restatement alone: both signs, none near zero, of the Courant numbers (DSw.signs_ok), of vb, ub on every edge row and the
+        row next to it (the c > 0 branch of xtp_u / ytp_v with the one-sided edge values), of vc(., 1), vc(., npy), uc(1, .), uc(npx, .)
+        (the sin_sg selection of the nord = 0 divergence, :1288, :1308, :1315); on every level (branch_fractions) the floor and the linear
+        branch of max(d2_bg, min(0.20, dddmp x)) each at >= 10 % of the points of every region, no point within 1e-6 (relative) of a
+        switch.  amplify > 1: instead the cap at >= 10 % of the bulk and at least one point of every strip and corner block."""
+        if not DSw.signs_ok(self, x, M, edge, ecorner):
+            return False
+        o, n = self.apply(x, M, edge, ecorner), self.n
+        npx = n + 1
+        rows = []
+        for i in (1, 2, npx - 1, npx):
+            for f in ("vb", "ub"):
+                rows += [fo.V(o[f], i, i, 1, npx), fo.V(o[f], 1, npx, i, i)]
+        for i in (1, npx):
+            rows += [fo.V(x["vc"], 0, n + 1, i, i), fo.V(x["uc"], i, i, 0, n + 1)]
+        if not all(both_signs(np.real(r)) for r in rows):
+            return False
+        frac, clear = self.branch_fractions(o)
+        if not clear:
+            return False
+        for (l, name), (fl, li, cp) in frac.items():
+            if self.amplify > 1.0:
+                if not (cp >= 0.10 if name == "bulk" else cp > 0.0):
+                    return False
+            elif fl < 0.10 or li < 0.10:
+                return False
+        return True
+
+
+OPERATORS = {"c_sw": CSw, "one_grad_p": OneGradP, "p_grad_c": PGradC, "d_sw": DSw, "c_sw_rest": CSwRest, "d_sw_rest": DSwRest, "c_sw_rest_nh": CSwRestNh}
+# geopk outputs, and delp, pt as c_sw receives them: the corner-halo columns hold no data (the exchange leaves them alone); NaN for the
+# restatement, 1e30 for the library
+GHOST_FREE = ("pk", "gzd", "pkc", "gz", "delp", "pt", "w")
 
 
 def _ghost_fill(c, x, value):
@@ -209,7 +443,7 @@ def _tangent(op, T, P, M, edge, ecorner, dtype):
 SPACING, REACH = 14, 6
 
 
-def _adjoint(op, T, seeds, M, edge, ecorner, dtype, points, chunk=192, coloured=False):
+def _adjoint(op, T, seeds, M, edge, ecorner, dtype, points, chunk=192, coloured=False, level0=0):
     """J^T s at the listed input points {input: boolean [nlev, pj, pj]}: one unit perturbation per column, complex step.
     coloured: the statements are local -- an input point reaches no output further than REACH cells away, the corner rotations of
     d2a2c_vect and the replace of a2b_ord4 included -- so one column perturbs a whole lattice of points SPACING apart on one level and
@@ -218,15 +452,17 @@ def _adjoint(op, T, seeds, M, edge, ecorner, dtype, points, chunk=192, coloured=
     ct = np.clongdouble if dtype == np.longdouble else np.complex128
     if getattr(op, "level_local", False) and next(iter(T.values())).shape[0] > 1:      # no statement couples two levels: one at a time
         parts = [_adjoint(op, {k: v[l:l + 1] for k, v in T.items()}, {k: v[l:l + 1] for k, v in seeds.items()}, M, edge, ecorner, dtype,
-                          {k: v[l:l + 1] for k, v in points.items()}, chunk, coloured) for l in range(next(iter(T.values())).shape[0])]
+                          {k: v[l:l + 1] for k, v in points.items()}, chunk, coloured, level0=l) for l in range(next(iter(T.values())).shape[0])]
         return {k: np.concatenate([p_[k] for p_ in parts], axis=0) for k in T}
     res = {k: np.zeros(T[k].shape, dtype=dtype) for k in T}
+    lkw = {"level0": level0} if getattr(op, "per_level", False) else {}      # the level a one-level slice stands for (per-level parameters)
 
     def seeded(o):
         out = {}
         for on, s in seeds.items():
             d = np.where(s != 0, np.imag(o[on]) / dtype(H), 0)
             assert np.all(np.isfinite(d.astype(np.float64))), ("the restatement read an undefined entry", on)
+            assert np.all(np.isfinite(np.where(s != 0, np.real(o[on]), 0).astype(np.float64))), ("a seeded output the restatement does not form", on)
             out[on] = d * s
         return out
     for name in T:
@@ -240,7 +476,7 @@ def _adjoint(op, T, seeds, M, edge, ecorner, dtype, points, chunk=192, coloured=
                 for q, (l, a, b) in enumerate(sub):
                     zz[q, l, a::SPACING, b::SPACING] += 1j * ct(H)
                 z[name] = zz
-                ds = seeded(op.apply(z, M, edge, ecorner))
+                ds = seeded(op.apply(z, M, edge, ecorner, **lkw))
                 tot = sum(v.sum(axis=1) for v in ds.values())          # over the output levels: [ncol, pj, pj]
                 pad = np.zeros((len(sub), pj + 2 * REACH, pj + 2 * REACH), dtype=dtype)
                 pad[:, REACH:-REACH, REACH:-REACH] = tot
@@ -259,7 +495,7 @@ def _adjoint(op, T, seeds, M, edge, ecorner, dtype, points, chunk=192, coloured=
             zz = z[name].copy()
             zz[np.arange(len(sub)), sub[:, 0], sub[:, 1], sub[:, 2]] += 1j * ct(H)
             z[name] = zz
-            ds = seeded(op.apply(z, M, edge, ecorner))
+            ds = seeded(op.apply(z, M, edge, ecorner, **lkw))
             res[name][sub[:, 0], sub[:, 1], sub[:, 2]] = sum(v.reshape(len(sub), -1).sum(axis=1) for v in ds.values())
     return res
 
@@ -270,16 +506,47 @@ def near_edge(n, cells=4):
     return (I <= cells + 1) | (I >= n + 1 - cells) | (J <= cells + 1) | (J >= n + 1 - cells)
 
 
-def check(backend, group, n, face, npz=3, adjoint_all=True, seed=0, report=None, coloured=False, adjoint_levels=None, env=None):
+def _compose(op, T, P, fl, M, edge, ecorner, dtype):
+    """values and tangent of the outputs an operator forms by composition (op.compose): the restated statements on T + i h P, with the
+    product's own fields fl = {name: (values, tangent)} as data"""
+    ct = np.clongdouble if dtype == np.longdouble else np.complex128
+    z = {k: T[k].astype(ct) + 1j * ct(H) * P[k].astype(ct) for k in T}
+    zf = {k: a.astype(ct) + 1j * ct(H) * b.astype(ct) for k, (a, b) in fl.items()}
+    o = op.compose(z, zf["fxv"], zf["fyv"], M, edge, ecorner)
+    return {k: (np.real(v).astype(dtype), (np.imag(v) / dtype(H)).astype(dtype)) for k, v in o.items()}
+
+
+def _print_figures(label, rows):
+    """one line per mode and region class: worst movement of the restatement, worst error, worst error / bound (pytest -s / -rP shows them)"""
+    cls = lambda r: "bulk" if r == "bulk" else "corner" if r in ("sw", "se", "ne", "nw") else "strip" if r in ("west", "east", "south", "north") else r
+    w = {}
+    for (mode, out, reg, mv, bound, err) in rows:
+        a = w.setdefault((mode, cls(reg)), [0.0, 0.0, 0.0])
+        a[0], a[1], a[2] = max(a[0], mv), max(a[1], err), max(a[2], err / bound)
+    for (mode, c_), a in sorted(w.items()):
+        print("figures %s %s %s: movement %.1e error %.1e error/bound %.2f" % (label, mode, c_, a[0], a[1], a[2]))
+
+
+def check(backend, group, n, face, npz=3, adjoint_all=True, seed=0, report=None, coloured=False, adjoint_levels=None, env=None, opt=None,
+          amplify=None, adjoint_on=None, adjoint_thin=1, detune=False):
     """values, tangent and adjoint of one operator on one whole face; returns [(mode, output, region, movement, bound, error)].
     adjoint_all: J^T s entry by entry at every input point; otherwise at the points within four cells of a face edge on the first
-    adjoint_levels levels (None: all), and four random dot products <s, J dx> = <J^T s, dx> for all the other points."""
+    adjoint_levels levels (None: all), and four random dot products <s, J dx> = <J^T s, dx> for all the other points.
+    adjoint_on: a list of levels; entry by entry at every point of these levels and the dot products for the other levels.
+    adjoint_thin = k > 1: of the points so chosen, entry by entry only those on every k-th offset of the coloured lattice (1 in k of the
+    reference's columns); the others join the dot products.
+    opt: options of the case (default_options keywords); amplify: the operator's draw amplified (DSwRest: the 0.20 cap).
+    detune: library and restatement both get the metrics with every sin_sg / cos_sg plane scaled by a factor of its own (detuned)."""
     import os
     from common import Case
     old = {k: os.environ.get(k) for k in (env or {})}
     os.environ.update(env or {})                              # switches the library reads when an instance is created
     try:
-        c = Case(nx=n, ny=n, npz=npz, n_split=2, dt=1800.0, backend=backend, face=face, oracle=False, metrics_hook=restatement_hook(n, face))
+        hook = restatement_hook(n, face)
+        if detune:
+            plain = hook
+            hook = lambda m, e, ec: (lambda r: (detuned(r[0]), r[1], r[2]))(plain(m, e, ec))
+        c = Case(nx=n, ny=n, npz=npz, n_split=2, dt=1800.0, backend=backend, face=face, oracle=False, metrics_hook=hook, **(opt or {}))
     finally:
         for k, v in old.items():
             if v is None:
@@ -287,8 +554,13 @@ def check(backend, group, n, face, npz=3, adjoint_all=True, seed=0, report=None,
             else:
                 os.environ[k] = v
     op = OPERATORS[group](c)
+    if amplify is not None:
+        op.amplify = amplify
     M64, e64, ec64 = face_metrics_of(n, face, np.float64)
     ML, eL, ecL = face_metrics_of(n, face, np.longdouble)
+    if detune:
+        M64 = detuned(M64)
+        ML = {k: v.astype(np.longdouble) for k, v in M64.items()}       # the float64 numbers the library holds, exactly
     rng = np.random.default_rng(1000 * n + 10 * face + seed)
     for _ in range(50):                                      # redraw until the trajectory takes both branches everywhere, clear of zero
         T, P = op.draw(c, rng)
@@ -298,7 +570,14 @@ def check(backend, group, n, face, npz=3, adjoint_all=True, seed=0, report=None,
         raise AssertionError("no trajectory with both signs on every edge row")
     Tn, Pn = _ghost_fill(c, T, np.nan), _ghost_fill(c, P, np.nan)
     rects, rows = G.rects(c), []
-    masks = {o: compared_mask(c, o, rk) for o, rk in op.outs}
+    composed = list(getattr(op, "composed", []))
+    masks = {o: compared_mask(c, o, rk) for o, rk in op.outs + composed}
+    for o, m in masks.items():                               # what poison_checks.drop_undefined took out of the rect
+        nd = int(G.masked(c, np.ones((1, n + 7, n + 7)), dict(op.outs + composed)[o])[0].sum()) - int(m.sum())
+        if nd:
+            print("dropped (formed from undefined entries by the reference itself): %s %d points" % (o, nd))
+    lv = {o: (op.levels_of(o) if hasattr(op, "levels_of") and op.levels_of(o) is not None else slice(None)) for o, _ in op.outs + composed}
+    S = lambda a, o: a[lv[o]]                                 # the levels on which the reference forms the output
     L = lambda d: {k: v.astype(np.longdouble) for k, v in d.items()}
     ref = _tangent(op, L(Tn), L(Pn), ML, eL, ecL, np.longdouble)
     # ---- values and tangent
@@ -308,53 +587,72 @@ def check(backend, group, n, face, npz=3, adjoint_all=True, seed=0, report=None,
     Tg, Pg = _ghost_fill(c, T, 1.0e30), _ghost_fill(c, P, 1.0e30)
     for k in op.ins:
         c.dy.put(k, Tg[k][None], 0); c.dy.put(k, Pg[k][None], 1)
-    c.dy.run_group(group, TL)
-    got = {o: (c.dy.get(o, 0)[0], c.dy.get(o, 1)[0]) for o, _ in op.outs}
+    c.dy.run_group(op.group, TL)
+    got = {o: (c.dy.get(o, 0)[0], c.dy.get(o, 1)[0]) for o, _ in op.outs + composed}
+    if composed:                                             # the product's vorticity fluxes as data of the restated last statements
+        fl = {k: (c.dy.get(k, 0)[0], c.dy.get(k, 1)[0]) for k in ("fxv", "fyv")}
+        ref.update(_compose(op, L(Tn), L(Pn), fl, ML, eL, ecL, np.longdouble))
     move = {}
     for d in range(3):
         Td, Pd = {k: ulp_move(rng, v) for k, v in Tn.items()}, {k: ulp_move(rng, v) for k, v in Pn.items()}
         r64 = _tangent(op, Td, Pd, M64, e64, ec64, np.float64)
-        for o, rk in op.outs:
+        if composed:
+            r64.update(_compose(op, Td, Pd, fl, M64, e64, ec64, np.float64))
+        for o, rk in op.outs + composed:
             for w, tag in ((0, "values"), (1, "tangent")):
-                for reg, e in region_errors(r64[o][w], ref[o][w], masks[o], n, rects[rk]).items():
+                for reg, e in region_errors(S(r64[o][w], o), S(ref[o][w], o), masks[o], n, rects[rk]).items():
                     move[(tag, o, reg)] = max(move.get((tag, o, reg), 0.0), e)
-    for o, rk in op.outs:
+    for o, rk in op.outs + composed:
         for w, tag in ((0, "values"), (1, "tangent")):
-            for reg, e in region_errors(got[o][w], ref[o][w], masks[o], n, rects[rk]).items():
+            for reg, e in region_errors(S(got[o][w], o), S(ref[o][w], o), masks[o], n, rects[rk]).items():
                 mv = move[(tag, o, reg)]
                 rows.append((tag, o, reg, mv, max(8 * mv, FLOOR), e))
     # ---- adjoint: seeds on the compared outputs only
-    seeds = {o: np.where(masks[o], rng.standard_normal((c.dy.levels(o), n + 7, n + 7)), 0.0) for o, _ in op.outs}
+    seeded = [o for o, _ in op.outs]
+    seeds = {}
+    for o in seeded:
+        on = np.zeros((c.dy.levels(o), 1, 1), bool)
+        on[lv[o]] = True
+        seeds[o] = np.where(masks[o] & on, rng.standard_normal((c.dy.levels(o), n + 7, n + 7)), 0.0)
     for k, v in fixed.items():
         c.dy.put(k, v[None], 0)
     for k in op.ins:
         c.dy.put(k, Tg[k][None], 0)
-    c.dy.run_group(group, NL)
+    c.dy.run_group(op.group, NL)
     c.dy.zero_work_adjoint()
-    _, _, gins, gouts = G.table(c)[group]
-    for k in set(gins) | {o for o, _ in gouts if o}:
+    _, _, gins, gouts = G.table(c)[op.group]
+    for k in set(gins) | set(op.ins) | {o for o, _ in gouts if o}:
         c.dy.put(k, np.zeros(c.dy.shape(k)), 1)
     for o, s in seeds.items():
         c.dy.put(o, s[None], 1)
-    c.dy.run_group(group, AD)
+    c.dy.run_group(op.group, AD)
     gota = {k: c.dy.get(k, 1)[0] for k in op.ins}
     ne = near_edge(n)
+    if adjoint_on is not None:
+        adjoint_all, ne = False, np.ones_like(ne)
     pts = {k: np.broadcast_to(ne if not adjoint_all else np.ones_like(ne), T[k].shape).copy() for k in op.ins}
+    nl = {}                                                   # levels compared entry by entry
     for k in op.ins:
         if k in GHOST_FREE:
             pts[k][:, fo._ghost(n)] = False                   # no data there: nothing to differentiate with respect to
-        if not adjoint_all and adjoint_levels is not None:
-            pts[k][adjoint_levels:] = False
-    nl = {k: (T[k].shape[0] if adjoint_all or adjoint_levels is None else adjoint_levels) for k in op.ins}      # levels compared entry by entry
+        nl[k] = list(range(T[k].shape[0]))
+        if adjoint_on is not None:
+            nl[k] = [l for l in nl[k] if l in adjoint_on]
+        elif not adjoint_all and adjoint_levels is not None:
+            nl[k] = nl[k][:adjoint_levels]
+        pts[k][[l for l in range(T[k].shape[0]) if l not in nl[k]]] = False
+        if adjoint_thin > 1:
+            J_, I_ = np.meshgrid(np.arange(n + 7) % SPACING, np.arange(n + 7) % SPACING, indexing="ij")
+            pts[k] &= ((J_ * SPACING + I_ + face) % adjoint_thin == 0)
     refa = _adjoint(op, L(Tn), L(seeds), ML, eL, ecL, np.longdouble, pts, coloured=coloured)
     mva = {}
     for d in range(3):
         r64 = _adjoint(op, {k: ulp_move(rng, v) for k, v in Tn.items()}, seeds, M64, e64, ec64, np.float64, pts, coloured=coloured)
         for k in op.ins:
-            for reg, e in (region_errors(r64[k][:nl[k]], refa[k][:nl[k]], pts[k][0], n, rects["full"]).items() if nl[k] else ()):
+            for reg, e in (region_errors(r64[k][nl[k]], refa[k][nl[k]], pts[k][nl[k][0]], n, rects["full"]).items() if nl[k] else ()):
                 mva[(k, reg)] = max(mva.get((k, reg), 0.0), e)
     for k in op.ins:
-        for reg, e in (region_errors(gota[k][:nl[k]], refa[k][:nl[k]], pts[k][0], n, rects["full"]).items() if nl[k] else ()):
+        for reg, e in (region_errors(gota[k][nl[k]], refa[k][nl[k]], pts[k][nl[k][0]], n, rects["full"]).items() if nl[k] else ()):
             rows.append(("adjoint", k, reg, mva[(k, reg)], max(8 * mva[(k, reg)], FLOOR), e))
     if not adjoint_all:                                        # the rest of the plane: four random dot products <s, J dx> = <J^T s, dx>
         for d in range(4):
@@ -363,15 +661,44 @@ def check(backend, group, n, face, npz=3, adjoint_all=True, seed=0, report=None,
                 if k in dx:
                     dx[k][:, fo._ghost(n)] = 0.0
             jdx = _tangent(op, L(Tn), L(dx), ML, eL, ecL, np.longdouble)
-            lhs = sum(float(np.sum(np.where(seeds[o] != 0, jdx[o][1], 0) * seeds[o])) for o, _ in op.outs)
+            lhs = sum(float(np.sum(np.where(seeds[o] != 0, jdx[o][1], 0) * seeds[o])) for o in seeded)
             rhs = sum(float(np.sum(gota[k] * dx[k])) for k in op.ins)
-            scale = sum(float(np.sum(np.abs(np.where(seeds[o] != 0, jdx[o][1], 0) * seeds[o]))) for o, _ in op.outs)
+            scale = sum(float(np.sum(np.abs(np.where(seeds[o] != 0, jdx[o][1], 0) * seeds[o]))) for o in seeded)
             rows.append(("adjoint", "dot%d" % d, "rest", 0.0, FLOOR, abs(lhs - rhs) / scale))
     if report is not None:
         report.extend((group, n, face) + r for r in rows)
+    _print_figures("%s %s C%d face %d" % (backend, group, n, face), rows)
     bad = [r for r in rows if not r[5] <= r[4]]
     assert not bad, (group, n, face, bad[:8])
     return rows
+
+
+# The levels of the d_sw_rest cases, as (trajectory nord, perturbation nord, iord, nord_v).  d2_bg_k2 = 0.03 keeps level 2 a sponge level with a
+# floor well under the cap (0.12 leaves a linear window of 0.6 < x < 1 that a 4-point bulk rarely meets) and lets level 3 run nord = 1;
+# C70 with npz = 2 needs d2_bg_k2 = 0 for a level with nord = 1 and d2_bg_k1 = 0.02 for a floor under the cap on level 1.
+# split_damp: level 2 runs the trajectory's nord = 2 / 3 (values of ke2 through fill_corners) over the perturbation's nord = 1, every
+# coefficient of the two sets apart, the trajectory's vorticity damping with nord_v = 2.
+DSW_REST = dict(npz=3, opt=dict(n_sponge_pert=2, d2_bg_k2=0.03, d2_bg_k2_pert=0.03), forms=[(0, 0, 1, 0), (0, 0, 2, 0), (1, 1, 2, 1)])
+DSW_REST_C70 = dict(npz=2, opt=dict(n_sponge_pert=2, d2_bg_k1=0.02, d2_bg_k2=0.0, d2_bg_k1_pert=0.02, d2_bg_k2_pert=0.0), forms=[(0, 0, 1, 0), (1, 1, 2, 1)])
+_SPLIT = dict(split_damp=1, nord_pert=1, n_sponge_pert=1, dddmp=0.35, dddmp_pert=0.2, d4_bg=0.11, d4_bg_pert=0.15, d2_bg=0.02, d2_bg_pert=0.015,
+              vtdm4=0.03, vtdm4_pert=0.0005, d2_bg_k1=0.18, d2_bg_k2=0.0)
+DSW_SPLIT = {nord: dict(npz=2, opt=dict(_SPLIT, nord=nord), forms=[(0, 0, 2, 0), (nord, 1, 2, 2)]) for nord in (2, 3)}
+
+
+def check_d_sw_rest(backend, n, face, case=None, **kw):
+    """check() of d_sw_rest on a case whose levels run the forms it names: asserted here from the level parameters (fo.level_rules,
+    fo.level_rules_pert, which DSwRest holds to the library's own), before anything is computed"""
+    from fv3_jedi_linearmodel_amd import default_options
+    case = case or DSW_REST
+    o = default_options(**case["opt"])
+    got = []
+    for k in range(1, case["npz"] + 1):
+        t, q = fo.level_rules(o, k, case["npz"]), fo.level_rules_pert(o, k)
+        iord = o.hord_mt_ks_pert if (k <= o.n_sponge_pert - 1 and o.hord_ks_pert) else o.hord_mt_pert
+        got.append((t["nord"], q["nord"] if o.split_damp else t["nord"], iord, t["nord_v"]))
+    assert got == case["forms"], got
+    assert 0 in {f[1] for f in got} and 1 in {f[1] for f in got}
+    return check(backend, "d_sw_rest", n, face, npz=case["npz"], opt=case["opt"], **kw)
 
 
 # ------------------------------------------------------------------------------------------------------------ faces cut into tiles
@@ -379,21 +706,23 @@ class _FaceShape:
     """what the operator classes and groups.py read of a case, for a whole face of the cube behind a tiled CubeCase"""
     def __init__(self, c):
         self.nx = self.ny = c.n
-        self.npz, self.dt_ac, self.opt, self.face = c.npz, c.dt_ac, c.opt, "cube"
+        self.npz, self.dt_ac, self.opt, self.face, self.da_min_c = c.npz, c.dt_ac, c.opt, "cube", c.da_min_c
 
     def rect(self, i0, i1, j0, j1):
         return (Ellipsis, slice(j0 + 2, j1 + 3), slice(i0 + 2, i1 + 3))
 
 
-def check_layout(backend, group, n=16, layout=2, npz=3, report=None):
+def check_layout(backend, group, n=16, layout=2, npz=3, report=None, opt=None):
     """Six faces of C<n> cut layout x layout (the tile offset into edge[] and the clipped strip rects of the a2b builders): every tile's
     outputs on its own rects against the windows of the whole-face restatement, values and tangent per point and region (regions of the
-    tile), and the adjoint through four dot products <s, J dx> = <J^T s, dx> summed over the tiles, dx and J dx from the restatement."""
+    tile), and the adjoint through four dot products <s, J dx> = <J^T s, dx> summed over the tiles, dx and J dx from the restatement.
+    (The outputs an operator forms by composition, DSwRest.composed, are not compared here.)"""
     from common import CubeCase
     from fv3_jedi_linearmodel_amd import cube
-    c = CubeCase(n=n, npz=npz, n_split=2, backend=backend, layout=layout, oracle=False, metrics_hook=restatement_hook(n))
+    c = CubeCase(n=n, npz=npz, n_split=2, backend=backend, layout=layout, oracle=False, metrics_hook=restatement_hook(n), **(opt or {}))
     fc = _FaceShape(c)
     op = OPERATORS[group](fc)
+    lv = {o: (op.levels_of(o) if hasattr(op, "levels_of") and op.levels_of(o) is not None else slice(None)) for o, _ in op.outs}
     nt, tl = c.nt, c.tiles
     W = lambda a: cube.tile_window(a, tl, nt)                    # [6, ..., pj, pj] -> [ntile, ..., nt+7, nt+7]
     rng = np.random.default_rng(7 * n + layout)
@@ -401,6 +730,7 @@ def check_layout(backend, group, n=16, layout=2, npz=3, report=None):
     MLs = [face_metrics_of(n, f, np.longdouble) for f in range(6)]
     T6, P6 = [], []
     for f in range(6):
+        op.face = f                                              # (DSwRest: the face whose divgd halo and metrics the draw takes)
         for _ in range(50):
             T, P = op.draw(fc, rng)
             if op.signs_ok(T, *Ms[f]):
@@ -420,13 +750,21 @@ def check_layout(backend, group, n=16, layout=2, npz=3, report=None):
     for o, rk in op.outs:
         dropped = W(np.stack([G.drop_face_corners(fc, o, one[f]) for f in range(6)]))[:, 0] == 0
         masks[o] = (G.masked(c, np.ones((len(tl), 1, nt + 7, nt + 7)), rk)[:, 0] != 0) & ~dropped
-    if group == "c_sw":
-        for k in ("delp", "pt"):
-            c.dy.put(k, c.traj[k], 0); c.dy.put(k, np.zeros_like(c.traj[k]), 1)
+    # the inputs of the library's group that the operator leaves alone: delp, pt of the case, plausible winds (DSw), empty accumulators
+    _, _, gins, gouts = G.table(c)[op.group]
+    frng = np.random.default_rng(5)
+    fixed = {}
+    for k in gins:
+        if k in op.ins:
+            continue
+        fixed[k] = c.traj[k] if k in ("delp", "pt") else np.zeros(c.dy.shape(k)) if k in ("mfx", "mfy", "cx", "cy") else \
+            noise(frng, c.dy.shape(k), 1e-6 if k == "divgd" else 5.0)
+    for k, v in fixed.items():
+        c.dy.put(k, v, 0); c.dy.put(k, np.zeros_like(v), 1)
     Tg = {k: W(v) for k, v in stack(T6, 1.0e30).items()}; Pg = {k: W(v) for k, v in stack(P6, 1.0e30).items()}
     for k in op.ins:
         c.dy.put(k, Tg[k], 0); c.dy.put(k, Pg[k], 1)
-    c.dy.run_group(group, TL)
+    c.dy.run_group(op.group, TL)
     got = {o: (c.dy.get(o, 0), c.dy.get(o, 1)) for o, _ in op.outs}
     move, rows = {}, []
     for d in range(3):
@@ -436,31 +774,33 @@ def check_layout(backend, group, n=16, layout=2, npz=3, report=None):
             for w, tag in ((0, "values"), (1, "tangent")):
                 rw = W(np.stack([r64[f][o][w] for f in range(6)]))
                 for t in range(len(tl)):
-                    for reg, e in region_errors(rw[t], refw[o][w][t], masks[o][t], nt, rects[rk]).items():
+                    for reg, e in region_errors(rw[t][lv[o]], refw[o][w][t][lv[o]], masks[o][t], nt, rects[rk]).items():
                         move[(tag, o, reg)] = max(move.get((tag, o, reg), 0.0), e)
     err = {}
     for o, rk in op.outs:
         for w, tag in ((0, "values"), (1, "tangent")):
             for t in range(len(tl)):
-                for reg, e in region_errors(got[o][w][t], refw[o][w][t], masks[o][t], nt, rects[rk]).items():
+                for reg, e in region_errors(got[o][w][t][lv[o]], refw[o][w][t][lv[o]], masks[o][t], nt, rects[rk]).items():
                     err[(tag, o, reg)] = max(err.get((tag, o, reg), 0.0), e)
     for k, e in sorted(err.items()):
         rows.append(k + (move[k], max(8 * move[k], FLOOR), e))
     # ---- adjoint: seeds on the compared outputs of every tile
-    seeds = {o: np.where(masks[o][:, None], rng.standard_normal(got[o][0].shape), 0.0) for o, _ in op.outs}
-    if group == "c_sw":
-        for k in ("delp", "pt"):
-            c.dy.put(k, c.traj[k], 0)
+    seeds = {}
+    for o, _ in op.outs:
+        on = np.zeros((1, got[o][0].shape[1], 1, 1), bool)
+        on[:, lv[o]] = True
+        seeds[o] = np.where(masks[o][:, None] & on, rng.standard_normal(got[o][0].shape), 0.0)
+    for k, v in fixed.items():
+        c.dy.put(k, v, 0)
     for k in op.ins:
         c.dy.put(k, Tg[k], 0)
-    c.dy.run_group(group, NL)
+    c.dy.run_group(op.group, NL)
     c.dy.zero_work_adjoint()
-    _, _, gins, gouts = G.table(c)[group]
-    for k in set(gins) | {o for o, _ in gouts if o}:
+    for k in set(gins) | set(op.ins) | {o for o, _ in gouts if o}:
         c.dy.put(k, np.zeros(c.dy.shape(k)), 1)
     for o, s in seeds.items():
         c.dy.put(o, s, 1)
-    c.dy.run_group(group, AD)
+    c.dy.run_group(op.group, AD)
     gota = {k: c.dy.get(k, 1) for k in op.ins}
     g6 = fo._ghost(n)
     for d in range(4):
@@ -481,6 +821,7 @@ def check_layout(backend, group, n=16, layout=2, npz=3, report=None):
         rows.append(("adjoint", "dot%d" % d, "tiles", 0.0, FLOOR, abs(lhs - rhs) / scale))
     if report is not None:
         report.extend((group, n, "2x2") + r for r in rows)
+    _print_figures("%s %s C%d cut %dx%d" % (backend, group, n, layout, layout), rows)
     bad = [r for r in rows if not r[5] <= r[4]]
     assert not bad, (group, n, layout, bad[:8])
     return rows

@@ -14,7 +14,7 @@ def rects(c):
         A=(1, nx, 1, ny), Ah=(0, nx + 1, 0, ny + 1), Ah2=(-1, nx + 2, -1, ny + 2),
         U=(1, nx, 1, ny + 1), V=(1, nx + 1, 1, ny), B=(1, nx + 1, 1, ny + 1),
         CX=(1, nx + 1, jsd, jed), CY=(isd, ied, 1, ny + 1), UTF=(0, nx + 2, 0, ny + 1), VTF=(0, nx + 1, 0, ny + 2),
-        full=full)
+        RAX=(1, nx, jsd, jed), RAY=(isd, ied, 1, ny), cells=(isd, ied, jsd, jed), full=full)
 
 
 # group -> (oracle method, scalar maker, [(oracle-in order) product field], [(product out field, rect key)])
@@ -49,7 +49,9 @@ def drop_face_corners(c, name, arr):
     afterwards; the product reads those views through an index map and leaves the stored value alone."""
     if getattr(c, "face", None) is None:
         return arr
-    if name in ("pe_c", "pkc", "gz", "pe", "pk", "gzd"):    # geopk: corner-halo columns hold no exchanged data, product skips them
+    # wk, vort_abs of d_sw over the whole padded plane: in the corner-halo squares the reference forms them with rarea = -1 / big_number
+    # (fill_ghost; sw_core_nlm.F90:1219, :1453)
+    if name in ("pe_c", "pkc", "gz", "pe", "pk", "gzd", "wk", "vort_abs"):    # geopk: corner-halo columns hold no exchanged data, product skips them
         out = arr.copy()
         for js in (slice(0, 3), slice(c.ny + 3, None)):
             for isl in (slice(0, 3), slice(c.nx + 3, None)):
@@ -58,8 +60,15 @@ def drop_face_corners(c, name, arr):
     # c_sw at the four corner-halo cells: the reference forms delpc, ptc there with rarea = -1 / big_number (fill_ghost,
     # fv_grid_tools_nlm.F90:902; sw_core_nlm.F90:246-256) and the area fluxes ut, vt around them with sin_sg = tiny_number and the
     # corner-halo cosa_u/v, rsin_u/v (:157-174): by its own account they hold no value, though the rects Ah, UTF, VTF include them
+    # wc of the non-hydrostatic c_sw at the four cells: rarea = -1 / big_number as for delpc, ptc (sw_core_nlm.F90:280-281).
+    # del6_d2 (the inner Laplacian of del6_vt_flux) at the same four cells: rarea = -1 / big_number again (sw_core_nlm.F90:1626), then
+    # overwritten by copy_corners.
+    # ke_c (the C-grid kinetic energy of c_sw) at the same four cells is not a poison case: sw_core_nlm.F90:362 forms it from ua, va of
+    # the corner-halo cell, the two entries dropped for the reason in the docstring -- in the reference the rotated neighbour values
+    # left behind by d2a2c_vect, in the product the stored ones, formed with cosa_s = big_number (sw_core_nlm.F90:2894) -- and no
+    # statement reads it: :477 reads ke(i-1 .. i, js .. je), :482 ke(is .. ie, j-1 .. j).
     cells = [(0, 0), (c.nx + 1, 0), (0, c.ny + 1), (c.nx + 1, c.ny + 1)]
-    pts = {"ua": cells, "va": cells, "delpc": cells, "ptc": cells, "utf": [(0, 0), (c.nx + 2, 0), (0, c.ny + 1), (c.nx + 2, c.ny + 1)],
+    pts = {"ua": cells, "va": cells, "delpc": cells, "ptc": cells, "ke_c": cells, "del6_d2": cells, "wc": cells, "utf": [(0, 0), (c.nx + 2, 0), (0, c.ny + 1), (c.nx + 2, c.ny + 1)],
            "vtf": [(0, 0), (c.nx + 1, 0), (0, c.ny + 2), (c.nx + 1, c.ny + 2)]}
     if name not in pts:
         return arr
