@@ -20,6 +20,7 @@
 #include "dampt.h"
 #include "dext.h"
 #include "a2b.h"
+#include "d2a2c.h"
 #include <functional>
 #include <map>
 #include <memory>
@@ -728,6 +729,51 @@ struct Dycore {
     }
   }
 
+  // Forward modes: the ops [n0, n1) (a chain of strip launches, each reading what the one before wrote) go to the strip stream in their
+  // order and run beside op n1 (the bulk launch, which reads none of their outputs and writes none of them); the main stream waits for
+  // them after it.  The adjoint keeps everything in line, as add_face does.
+  void beside_bulk(Program& P, size_t n0, size_t n1) {
+#ifndef FV3LM_HOST_EMUL
+    if (n1 <= n0 || n1 >= P.size()) return;
+    for (size_t n = n0; n < n1; ++n) {
+      auto fs = P[n].fn; const bool first = n == n0, last = n + 1 == n1;
+      P[n].fn = [fs, first, last](Exec& e, int mode) {
+        if (mode == MODE_AD || !e.sstream) { fs(e, mode); return; }
+        if (first) { HIPCHK(hipEventRecord(e.ev_s0, e.stream)); HIPCHK(hipStreamWaitEvent(e.sstream, e.ev_s0, 0)); }
+        hipStream_t main = e.stream; e.stream = e.sstream;
+        fs(e, mode);
+        e.stream = main;
+        if (last) { HIPCHK(hipEventRecord(e.ev_s1, e.sstream)); e.side_pending = true; }
+      };
+    }
+    auto fb = P[n1].fn;
+    P[n1].fn = [fb](Exec& e, int mode) {
+      fb(e, mode);
+      if (e.side_pending) { HIPCHK(hipStreamWaitEvent(e.stream, e.ev_s1, 0)); e.side_pending = false; }
+    };
+#else
+    (void)P; (void)n0; (void)n1;
+#endif
+  }
+  // the strips of add_face (south, north, west, east; W points wide) without a bulk launch
+  template <class D>
+  std::vector<Edged<D, true>> face_strips(const D& s, int W) const {
+    const int lo = 1 + W, hi = g.nx - W, BIG = 1 << 20;
+    const Rect regs[4] = {{-BIG, BIG, -BIG, lo - 1}, {-BIG, BIG, hi + 1, BIG}, {-BIG, lo - 1, lo, hi}, {hi + 1, BIG, lo, hi}};
+    std::vector<Edged<D, true>> strips;
+    for (int r = 0; r < 4; ++r) {
+      D t = s; Rect anchor{1, 0, 1, 0}; bool any = false;
+      for (int n = 0; n < D::NOUT; ++n) {
+        t.orect[n] = isect(s.orect[n], regs[r]);
+        if (!is_empty(t.orect[n]) && !any) { anchor = t.orect[n]; any = true; }
+      }
+      if (!any) continue;
+      for (int n = 0; n < D::NOUT; ++n) if (is_empty(t.orect[n])) t.orect[n] = empty_in(anchor);
+      strips.push_back(Edged<D, true>(t));
+    }
+    return strips;
+  }
+
   // external-mode divergence damping (dext.h; fv3lm_set_external_damping): flagstruct%d_ext, 0 = off.  The hydrostatic step carries its
   // launches only while it is > 0; the non-hydrostatic step (beta = 0: nh_p_grad) never reads divg2
   double d_ext = 0.;
@@ -1117,6 +1163,12 @@ inline void Dycore::build_acoustic() {
   }
   // ---- c_sw
   Fld utmp = W("utmp", npz), vtmp = W("vtmp", npz), ua = W("ua", npz), va = W("va", npz);
+  // the bulk of d2a2c_vect as one LDS-tiled launch per mode (d2a2c.h); FV3LM_D2A2C_FUSED=0: the two staged launches
+  const char* d2c_env = std::getenv("FV3LM_D2A2C_FUSED");
+  const bool d2c_fused = !(d2c_env && d2c_env[0] == '0');
+  D2a2cArgs d2c; d2c.u = u; d2c.v = v; d2c.ua = ua; d2c.va = va; d2c.utmp = utmp; d2c.vtmp = vtmp; d2c.dt2 = dt2; d2c.nk = npz; d2c.face = g.face ? 1 : 0;
+  d2c.ru = d2c.rv = d2c.ra = Rect{1, 0, 1, 0};
+  const size_t d2c_n0 = P.size();
   { CswInterpAD s; s.in[0] = u; s.in[1] = v; s.out[0] = utmp; s.out[1] = vtmp; s.out[2] = ua; s.out[3] = va;
     s.orect[0] = R(isd, ied, js - 1, je + 1); s.orect[1] = R(is - 1, ie + 1, jsd, jed);
     s.orect[2] = s.orect[3] = R(is - 1, ie + 1, js - 1, je + 1);
@@ -1124,13 +1176,25 @@ inline void Dycore::build_acoustic() {
       const int il = is == 1 ? isd : is - 1, ih = ie == g.nx ? ied : ie + 1, jl = js == 1 ? jsd : js - 1, jh = je == g.ny ? jed : je + 1;
       s.orect[0] = R(isd, ied, jl, jh); s.orect[1] = R(il, ih, jsd, jed); s.orect[2] = s.orect[3] = R(il, ih, jl, jh);
     }
-    s.k1 = npz; add_face(P, "c_sw", s, 3); }
+    s.k1 = npz;
+    if (!d2c_fused) add_face(P, "c_sw", s, 3);
+    else {
+      // the strips of add_face(.., 3) stay (they store utmp, vtmp, ua, va on the bands); ua, va of its bulk rectangle go to the fused launch
+      const Rect both[2] = {s.orect[0], s.orect[1]};
+      d2c.rtmp = rect_union(both, 2);
+      d2c.ra = g.face ? isect(s.orect[2], R(4, g.nx - 3, 4, g.nx - 3)) : s.orect[2];
+      if (is_empty(d2c.ra)) d2c.ra = Rect{1, 0, 1, 0};
+      if (g.face) add_multi(P, "c_sw", face_strips(s, 3));
+    } }
   Fld uc0 = W("uc0", npz), utf = W("utf", npz), vc0 = W("vc0", npz), vtf = W("vtf", npz);
+  d2c.uc0 = uc0; d2c.utf = utf; d2c.vc0 = vc0; d2c.vtf = vtf;
   const Fld none{};
   { CswInterpC_<false> s; s.in[0] = utmp; s.in[1] = vtmp; s.in[2] = u; s.in[3] = v; s.out[0] = uc0; s.out[1] = utf; s.out[2] = vc0; s.out[3] = vtf;
     s.dt2 = dt2; s.k1 = npz;
     if (!g.face) {
-      s.orect[0] = s.orect[1] = R(is - 1, ie + 2, js - 1, je + 1); s.orect[2] = s.orect[3] = R(is - 1, ie + 1, js - 1, je + 2); add(P, "c_sw", s);
+      s.orect[0] = s.orect[1] = R(is - 1, ie + 2, js - 1, je + 1); s.orect[2] = s.orect[3] = R(is - 1, ie + 1, js - 1, je + 2);
+      if (!d2c_fused) add(P, "c_sw", s);
+      else { d2c.ru = s.orect[0]; d2c.rv = s.orect[2]; }
     } else {   // 4-point interpolation away from the cube edges; one-sided / edge formulas and corner views on 3-wide strips (global indices)
       const int npx = g.nx + 1, npy = g.ny + 1;
       const Rect ur = R(is - 1, ie + 2, js - 1, je + 1), vr = R(is - 1, ie + 1, js - 1, je + 2);
@@ -1147,8 +1211,27 @@ inline void Dycore::build_acoustic() {
         e.orect[0] = e.orect[1] = m < 2 ? r : empty_in(r); e.orect[2] = e.orect[3] = m < 2 ? empty_in(r) : r; ev.push_back(e);
       }
       add_multi(P, "c_sw", ev);
-      if (b0 || b2) add(P, "c_sw", s);       // bulk last: first in the backward sweep (plan_adjoint)
+      if (!d2c_fused) { if (b0 || b2) add(P, "c_sw", s); }       // bulk last: first in the backward sweep (plan_adjoint)
+      else { if (b0) d2c.ru = s.orect[0]; if (b2) d2c.rv = s.orect[2]; }
     } }
+  if (d2c_fused && !is_empty(d2c.all())) {
+    // Forward the launch reads u, v alone and the two sets of strips (the C strips read the bands the A strips store) run beside it on the
+    // strip stream.  Backward it is the first of the routine: it stores the zeros the C strips' adjoint accumulates onto in utmp_ad,
+    // vtmp_ad, which the A strips' adjoint then reads -- the staged bulk adjoint that used to store them is gone.
+    d2c.clear_tmp = (g.face && utmp.p && vtmp.p) ? 1 : 0;
+    Ctx* cp = &ctx;
+    auto ap = std::make_shared<D2a2cArgs>(d2c);
+    Op op{"c_sw", [ap, cp](Exec& e, int mode) { run_d2a2c(e, mode, *ap, *cp); }};
+    op.name = "D2a2c";
+    op.ad_in = {u.p, v.p}; op.ad_in_slot = {0, 1};
+    op.ad_out = {uc0.p, utf.p, vc0.p, vtf.p, ua.p, va.p};
+    op.ad_out_rect = {d2c.ru, d2c.ru, d2c.rv, d2c.rv, d2c.ra, d2c.ra};
+    if (d2c.clear_tmp) op.ad_store = {utmp.p, vtmp.p};
+    op.set_wmask = [ap](unsigned w, Rect r) { ap->wmask = w; ap->wrect = r; };
+    const size_t d2c_n1 = P.size();
+    P.push_back(op);
+    beside_bulk(P, d2c_n0, d2c_n1);
+  }
   Fld divgd = W("divgd", npz);
   if (opt.nord > 0) {
     CswDivgD s; s.in[0] = u; s.in[1] = v; s.in[2] = ua; s.in[3] = va; s.out[0] = divgd; s.orect[0] = R(is, ie + 1, js, je + 1); s.k1 = npz;

@@ -40,6 +40,11 @@ def short(name):
         return "A2b.ad"
     if "k_a2b_rim_clear" in name:
         return "A2bRim.ad"
+    m = re.search(r"k_d2a2c<(fv3::Dual|double)", name)
+    if m:       # the bulk of d2a2c_vect as one launch (d2a2c.h)
+        return "D2a2c.%s" % ("tl" if "Dual" in m.group(1) else "nl")
+    if "k_d2a2c_ad" in name:
+        return "D2a2c.ad"
     if "k_zero16" in name:         # field-sized clears (dycore.h dev_zero)
         return "clear"
     if "k_tp_ad_corner" in name:   # corner-alias contributions of the fused adjoint (tpad.h)
