@@ -19,7 +19,8 @@
 // the rim, which is four bands -- costs two to four launches and a second pass over q_ad there).
 #pragma once
 #include <algorithm>
-#include "tpfused.h"
+#include "stages.h"
+#include "tiled.h"
 
 namespace fv3 {
 
@@ -69,23 +70,20 @@ constexpr int A2B_NQ = A2B_QW * A2B_QH, A2B_NA = A2B_W * A2B_QH, A2B_NB = A2B_QW
 // the rim: rows / columns of bulk qx / qy that the edge strips read (n1 = npx or npy)
 HD bool a2b_rim(int m, int n1) { return m <= 4 || m >= n1 - 4; }
 
-// One block of the forward modes: corner points I0..I1 x J0..J1 of level k of one tile.  tid / nth: this thread and the number of
-// threads sharing the block (host emulation: 0 / 1).
+// One block of the forward modes: corner points I0..I1 x J0..J1 of level k of one tile, blocks laid over Qr = a.rb.
 template <class T, int NTH>
-DEV void a2b_block(const A2bArgs& a, const Ctx& c, int tile, int k, int bx, int by, double* lds, int tid, int nth) {
+DEV void a2b_block(const A2bArgs& a, const Ctx& c, const Rect& Qr, int tile, int k, int bx, int by, double* lds, int tid) {
   typedef TpfIO<T> IO;
-  (void)nth;
   const Geom& g = c.g;
   const int npx = g.nx + 1, npy = g.ny + 1;
-  const int I0 = a.rb.i0 + bx * A2B_W, I1 = (I0 + A2B_W - 1 < a.rb.i1) ? I0 + A2B_W - 1 : a.rb.i1;
-  const int J0 = a.rb.j0 + by * A2B_H, J1 = (J0 + A2B_H - 1 < a.rb.j1) ? J0 + A2B_H - 1 : a.rb.j1;
-  const bool firstx = bx == 0, lastx = I1 == a.rb.i1, firsty = by == 0, lasty = J1 == a.rb.j1;
-  auto at = [&](const Fld& f, int i, int j) -> size_t { return (size_t)(tile * f.nk + k - 1) * g.plane + (size_t)g.idx(i, j); };
+  const TileBlk B = tile_blk(Qr, bx, by, A2B_W, A2B_H);
+  const int I0 = B.I0, I1 = B.I1, J0 = B.J0, J1 = B.J1;
+  const bool firstx = bx == 0, lastx = I1 == Qr.i1, firsty = by == 0, lasty = J1 == Qr.j1;
   double* const Q = lds; double* const QX = lds + A2B_NQ; double* const QY = QX + A2B_NA;
   // ---- q on [I0-2, I1+1] x [J0-2, J1+1]
   TPF_LOOP(e, A2B_NQ) {
     const int i = I0 - 2 + e % A2B_QW, j = J0 - 2 + e / A2B_QW;
-    if (i <= I1 + 1 && j <= J1 + 1) IO::lset(Q, A2B_NT, e, IO::ld(a.q, at(a.q, i, j)));
+    if (i <= I1 + 1 && j <= J1 + 1) IO::lset(Q, A2B_NT, e, IO::ld(a.q, fld_at(g, a.q, tile, k, i, j)));
   }
   TPF_SYNC();
   // ---- qx on [I0, I1] x [J0-2, J1+1], qy on [I0-2, I1+1] x [J0, J1] (A2bA_::line std4); the rim goes to memory, each element by the block
@@ -96,7 +94,7 @@ DEV void a2b_block(const A2bArgs& a, const Ctx& c, int tile, int k, int bx, int 
     auto q = [&](int ii) -> T { return IO::lget(Q, A2B_NT, r * A2B_QW + (ii - (I0 - 2))); };
     const T v = B2 * (q(i - 2) + q(i + 1)) + B1 * (q(i - 1) + q(i));
     IO::lset(QX, A2B_NT, e, v);
-    if (a.rim && a2b_rim(j, npy) && ((j >= J0 && j <= J1) || (firsty && j < J0) || (lasty && j > J1))) IO::st(a.qx, at(a.qx, i, j), v);
+    if (a.rim && a2b_rim(j, npy) && ((j >= J0 && j <= J1) || (firsty && j < J0) || (lasty && j > J1))) IO::st(a.qx, fld_at(g, a.qx, tile, k, i, j), v);
   }
   TPF_LOOP(e, A2B_NB) {
     const int x = e % A2B_QW, r = e / A2B_QW, i = I0 - 2 + x, j = J0 + r;
@@ -104,7 +102,7 @@ DEV void a2b_block(const A2bArgs& a, const Ctx& c, int tile, int k, int bx, int 
     auto q = [&](int jj) -> T { return IO::lget(Q, A2B_NT, (jj - (J0 - 2)) * A2B_QW + x); };
     const T v = B2 * (q(j - 2) + q(j + 1)) + B1 * (q(j - 1) + q(j));
     IO::lset(QY, A2B_NT, e, v);
-    if (a.rim && a2b_rim(i, npx) && ((i >= I0 && i <= I1) || (firstx && i < I0) || (lastx && i > I1))) IO::st(a.qy, at(a.qy, i, j), v);
+    if (a.rim && a2b_rim(i, npx) && ((i >= I0 && i <= I1) || (firstx && i < I0) || (lastx && i > I1))) IO::st(a.qy, fld_at(g, a.qy, tile, k, i, j), v);
   }
   TPF_SYNC();
   // ---- qb (A2bB_::qxx, qyy, eval)
@@ -115,25 +113,23 @@ DEV void a2b_block(const A2bArgs& a, const Ctx& c, int tile, int k, int bx, int 
     auto qy = [&](int ii) -> T { return IO::lget(QY, A2B_NT, r * A2B_QW + (ii - (I0 - 2))); };
     const T qxx = A2 * (qx(j - 2) + qx(j + 1)) + A1 * (qx(j - 1) + qx(j));
     const T qyy = A2 * (qy(i - 2) + qy(i + 1)) + A1 * (qy(i - 1) + qy(i));
-    IO::st(a.qb, at(a.qb, i, j), 0.5 * (qxx + qyy));
+    IO::st(a.qb, fld_at(g, a.qb, tile, k, i, j), 0.5 * (qxx + qyy));
   }
 }
 
 // One block of the adjoint: the points I0..I1 x J0..J1 of q_ad, blocks laid over Qr (the reach of the bulk, widened in store mode).
 template <int NTH>
-DEV void a2b_ad_block(const A2bArgs& a, const Ctx& c, const Rect& Qr, int tile, int k, int bx, int by, double* lds, int tid, int nth) {
-  (void)nth;
+DEV void a2b_ad_block(const A2bArgs& a, const Ctx& c, const Rect& Qr, int tile, int k, int bx, int by, double* lds, int tid) {
   const Geom& g = c.g;
   const int npx = g.nx + 1, npy = g.ny + 1;
-  const int I0 = Qr.i0 + bx * A2B_W, I1 = (I0 + A2B_W - 1 < Qr.i1) ? I0 + A2B_W - 1 : Qr.i1;
-  const int J0 = Qr.j0 + by * A2B_H, J1 = (J0 + A2B_H - 1 < Qr.j1) ? J0 + A2B_H - 1 : Qr.j1;
+  const TileBlk B = tile_blk(Qr, bx, by, A2B_W, A2B_H);
+  const int I0 = B.I0, I1 = B.I1, J0 = B.J0, J1 = B.J1;
   const Rect rx = a.rx(), ry = a.ry(), rq = a.reach();
-  auto at = [&](const Fld& f, int i, int j) -> size_t { return (size_t)(tile * f.nk + k - 1) * g.plane + (size_t)g.idx(i, j); };
   double* const QB = lds; double* const QX = lds + A2B_NQ; double* const QY = QX + A2B_NB;
   // ---- qb_ad on [I0-1, I0+W+1] x [J0-1, J0+H+1], zero outside the bulk rectangle
   TPF_LOOP(e, A2B_NQ) {
     const int i = I0 - 1 + e % A2B_QW, j = J0 - 1 + e / A2B_QW;
-    QB[e] = a.rb.has(i, j) ? a.qb.p[at(a.qb, i, j)] : 0.;
+    QB[e] = a.rb.has(i, j) ? a.qb.p[fld_at(g, a.qb, tile, k, i, j)] : 0.;
   }
   TPF_SYNC();
   // ---- qx_ad on [I0-1, I0+W+1] x [J0, J0+H-1], qy_ad on [I0, I0+W-1] x [J0-1, J0+H+1]: the transposed A1 / A2 sums, + on the rim what the
@@ -144,7 +140,7 @@ DEV void a2b_ad_block(const A2bArgs& a, const Ctx& c, const Rect& Qr, int tile, 
     if (rx.has(i, j)) {
       const double* b = QB + r * A2B_QW + x;       // qb_ad(i, j-1)
       v = 0.5 * (A2 * (b[0] + b[3 * A2B_QW]) + A1 * (b[A2B_QW] + b[2 * A2B_QW]));
-      if (a.rim && a2b_rim(j, npy)) v += a.qx.p[at(a.qx, i, j)];
+      if (a.rim && a2b_rim(j, npy)) v += a.qx.p[fld_at(g, a.qx, tile, k, i, j)];
     }
     QX[e] = v;
   }
@@ -154,7 +150,7 @@ DEV void a2b_ad_block(const A2bArgs& a, const Ctx& c, const Rect& Qr, int tile, 
     if (ry.has(i, j)) {
       const double* b = QB + r * A2B_QW + x;       // qb_ad(i-1, j)
       v = 0.5 * (A2 * (b[0] + b[3]) + A1 * (b[1] + b[2]));
-      if (a.rim && a2b_rim(i, npx)) v += a.qy.p[at(a.qy, i, j)];
+      if (a.rim && a2b_rim(i, npx)) v += a.qy.p[fld_at(g, a.qy, tile, k, i, j)];
     }
     QY[e] = v;
   }
@@ -168,24 +164,19 @@ DEV void a2b_ad_block(const A2bArgs& a, const Ctx& c, const Rect& Qr, int tile, 
     const double* px = QX + r * A2B_QW + x;        // qx_ad(i-1, j)
     const double* py = QY + r * A2B_W + x;         // qy_ad(i, j-1)
     const double acc = (B2 * (px[0] + px[3]) + B1 * (px[1] + px[2])) + (B2 * (py[0] + py[3 * A2B_W]) + B1 * (py[A2B_W] + py[2 * A2B_W]));
-    double* q = &a.q.p[at(a.q, i, j)];
+    double* q = &a.q.p[fld_at(g, a.q, tile, k, i, j)];
     if (a.wmask & 1u) *q = in ? acc : 0.; else *q += acc;
   }
 }
-
-// the rectangle the adjoint launch is laid over: the reach of the bulk; store mode: also where the stored adjoint is read later
-inline Rect a2b_ad_rect(const A2bArgs& a, const Geom& g) {
-  Rect q = a.reach();
-  if ((a.wmask & 1u) && a.wrect.i0 <= a.wrect.i1) {
-    if (a.wrect.i0 < q.i0) q.i0 = a.wrect.i0; if (a.wrect.i1 > q.i1) q.i1 = a.wrect.i1;
-    if (a.wrect.j0 < q.j0) q.j0 = a.wrect.j0; if (a.wrect.j1 > q.j1) q.j1 = a.wrect.j1;
-  }
-  if (q.i0 < g.isd()) q.i0 = g.isd();
-  if (q.j0 < g.jsd()) q.j0 = g.jsd();
-  if (q.i1 > g.ied() + 1) q.i1 = g.ied() + 1;
-  if (q.j1 > g.jed() + 1) q.j1 = g.jed() + 1;
-  return q;
-}
+// the block descriptors (tiled.h)
+template <class T, int N> struct A2bFwd {
+  typedef A2bArgs Args; static constexpr int NTH = N; static constexpr size_t LDS_BYTES = (size_t)A2B_NT * 8 * TpfIO<T>::NC;
+  DEV static void block(const Args& a, const Ctx& c, const Rect& Qr, int tile, int k, int bx, int by, double* lds, int tid) { a2b_block<T, N>(a, c, Qr, tile, k, bx, by, lds, tid); }
+};
+template <int N> struct A2bAd {
+  typedef A2bArgs Args; static constexpr int NTH = N; static constexpr size_t LDS_BYTES = (size_t)A2B_NT * 8;
+  DEV static void block(const Args& a, const Ctx& c, const Rect& Qr, int tile, int k, int bx, int by, double* lds, int tid) { a2b_ad_block<N>(a, c, Qr, tile, k, bx, by, lds, tid); }
+};
 
 // The bands of `frame` within four of a cube edge, as up to four rectangles (south, north, west, east; disjoint).
 struct A2bBands { Rect r[4]; int off[5]; };
@@ -214,18 +205,6 @@ HD void a2b_rim_clear_point(const A2bArgs& a, const Ctx& c, const A2bBands& b, i
 }
 
 #ifndef FV3LM_HOST_EMUL
-template <class T, int NTH>
-__global__ void __launch_bounds__(NTH) k_a2b(A2bArgs a, Ctx c) {
-  extern __shared__ double a2b_lds[];
-  int bx = blockIdx.x, by = blockIdx.y; xcd_block(gridDim.x, gridDim.y, bx, by);
-  a2b_block<T, NTH>(a, c, blockIdx.z / a.nk, 1 + blockIdx.z % a.nk, bx, by, a2b_lds, threadIdx.x, NTH);
-}
-template <int NTH>
-__global__ void __launch_bounds__(NTH) k_a2b_ad(A2bArgs a, Ctx c, Rect Qr) {
-  extern __shared__ double a2b_lds[];
-  int bx = blockIdx.x, by = blockIdx.y; xcd_block(gridDim.x, gridDim.y, bx, by);
-  a2b_ad_block<NTH>(a, c, Qr, blockIdx.z / a.nk, 1 + blockIdx.z % a.nk, bx, by, a2b_lds, threadIdx.x, NTH);
-}
 __global__ void __launch_bounds__(256) k_a2b_rim_clear(A2bArgs a, Ctx c, A2bBands b) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e < b.off[4]) a2b_rim_clear_point(a, c, b, e, blockIdx.y);
@@ -237,26 +216,13 @@ FV3LM_LINK void run_a2b(Exec& ex, int mode, const A2bArgs& a0, const Ctx& c) {
   for (Fld* f : {&a.q, &a.qb, &a.qx, &a.qy}) *f = ex.sh(*f);
   if (ex.no_wmask) a.wmask = 0;
   if (mode == MODE_AD && !a.q.p) return;
-  const Rect Qr = mode == MODE_AD ? a2b_ad_rect(a, c.g) : a.rb;
-  const int nbx = (Qr.i1 - Qr.i0 + A2B_W) / A2B_W, nby = (Qr.j1 - Qr.j0 + A2B_H) / A2B_H, nz = c.g.ntile * a.nk;
-  ex.mark_begin("A2b", mode == MODE_NL ? ".nl" : mode == MODE_TL ? ".tl" : ".ad", a2b_bytes(a, c.g, mode));
-#ifdef FV3LM_HOST_EMUL
-  std::vector<double> lds((size_t)A2B_NT * 2);
-  for (int z = 0; z < nz; ++z)
-    for (int by = 0; by < nby; ++by)
-      for (int bx = 0; bx < nbx; ++bx) {
-        if (mode == MODE_TL) a2b_block<Dual, 1>(a, c, z / a.nk, 1 + z % a.nk, bx, by, lds.data(), 0, 1);
-        else if (mode == MODE_NL) a2b_block<double, 1>(a, c, z / a.nk, 1 + z % a.nk, bx, by, lds.data(), 0, 1);
-        else a2b_ad_block<1>(a, c, Qr, z / a.nk, 1 + z % a.nk, bx, by, lds.data(), 0, 1);
-      }
-#else
-  const dim3 grid(nbx, nby, nz);
-  if (mode == MODE_TL) hipLaunchKernelGGL((k_a2b<Dual, FV3LM_A2B_THREADS_TL>), grid, dim3(FV3LM_A2B_THREADS_TL), A2B_NT * 16, ex.stream, a, c);
-  else if (mode == MODE_NL) hipLaunchKernelGGL((k_a2b<double, FV3LM_A2B_THREADS_NL>), grid, dim3(FV3LM_A2B_THREADS_NL), A2B_NT * 8, ex.stream, a, c);
-  else hipLaunchKernelGGL((k_a2b_ad<FV3LM_A2B_THREADS_AD>), grid, dim3(FV3LM_A2B_THREADS_AD), A2B_NT * 8, ex.stream, a, c, Qr);
-#endif
-  ex.mark_end();
-  ex.launches++;
+  // adjoint: the blocks are laid over the reach of the bulk; store mode: also over where the stored adjoint is read later
+  const Rect Qr = mode == MODE_AD ? ad_launch_rect(a.reach(), a.wmask & 1u, a.wrect, c.g) : a.rb;
+  const int nbx = tiled_blocks(Qr.i0, Qr.i1, A2B_W), nby = tiled_blocks(Qr.j0, Qr.j1, A2B_H);
+  const double bytes = a2b_bytes(a, c.g, mode);
+  if (mode == MODE_TL) run_tiled<A2bFwd<Dual, tiled_nth(FV3LM_A2B_THREADS_TL)>>(ex, "A2b", mode_tag(mode), bytes, Qr, nbx, nby, a, c);
+  else if (mode == MODE_NL) run_tiled<A2bFwd<double, tiled_nth(FV3LM_A2B_THREADS_NL)>>(ex, "A2b", mode_tag(mode), bytes, Qr, nbx, nby, a, c);
+  else run_tiled<A2bAd<tiled_nth(FV3LM_A2B_THREADS_AD)>>(ex, "A2b", mode_tag(mode), bytes, Qr, nbx, nby, a, c);
 }
 
 FV3LM_LINK void run_a2b_rim_clear(Exec& ex, const A2bArgs& a0, const Rect& frame, const Ctx& c) {

@@ -24,7 +24,8 @@
 // those strips accumulate onto (Op::ad_store), on the band points of its launch rectangle.
 #pragma once
 #include <algorithm>
-#include "tpfused.h"
+#include "stages.h"
+#include "tiled.h"
 
 namespace fv3 {
 
@@ -40,18 +41,11 @@ struct D2a2cArgs {
   int clear_tmp = 0;
   unsigned wmask = 0;              // adjoint: u_ad (bit 0), v_ad (bit 1) stored instead of accumulated (dycore.h plan_adjoint) ...
   Rect wrect{1, 0, 1, 0};          // ... over the launch rectangle widened to this one
-  HD static bool none(const Rect& r) { return r.i0 > r.i1 || r.j0 > r.j1; }
   // utmp is formed where uc0 reads it (ru widened by -2, +1 in i) and on ra; vtmp the transpose
   HD bool has_ut(int i, int j) const { return (i >= ru.i0 - 2 && i <= ru.i1 + 1 && j >= ru.j0 && j <= ru.j1) || ra.has(i, j); }
   HD bool has_vt(int i, int j) const { return (i >= rv.i0 && i <= rv.i1 && j >= rv.j0 - 2 && j <= rv.j1 + 1) || ra.has(i, j); }
   Rect all() const {               // the rectangle the forward launch is laid over
-    Rect q{1, 0, 1, 0};
-    for (const Rect* r : {&ru, &rv, &ra}) {
-      if (none(*r)) continue;
-      if (none(q)) q = *r;
-      else { q.i0 = std::min(q.i0, r->i0); q.i1 = std::max(q.i1, r->i1); q.j0 = std::min(q.j0, r->j0); q.j1 = std::max(q.j1, r->j1); }
-    }
-    return q;
+    return rect_join(rect_join(ru, rv), ra);
   }
 };
 // nonlinear / tangent / adjoint launch of the bulk
@@ -101,16 +95,13 @@ DEV void d2c_metrics(const Ctx& c, int tile, int i, int j, double* m) {
 // an index clamped to where (m, m - 1) both lie in the padded plane
 HD int d2c_clamp(int m, int lo, int hi) { return m <= lo ? lo + 1 : m > hi ? hi : m; }
 
-// One block of the forward modes: the points I0..I1 x J0..J1 of level k of one tile, blocks laid over a.all().  tid / nth: this thread
-// and the number of threads sharing the block (host emulation: 0 / 1).
+// One block of the forward modes: the points I0..I1 x J0..J1 of level k of one tile, blocks laid over Qr = a.all().
 template <class T, int NTH>
-DEV void d2a2c_block(const D2a2cArgs& a, const Ctx& c, const Rect& Qr, int tile, int k, int bx, int by, double* lds, int tid, int nth) {
+DEV void d2a2c_block(const D2a2cArgs& a, const Ctx& c, const Rect& Qr, int tile, int k, int bx, int by, double* lds, int tid) {
   typedef TpfIO<T> IO;
-  (void)nth;
   const Geom& g = c.g;
-  const int I0 = Qr.i0 + bx * D2C_W, I1 = (I0 + D2C_W - 1 < Qr.i1) ? I0 + D2C_W - 1 : Qr.i1;
-  const int J0 = Qr.j0 + by * D2C_H, J1 = (J0 + D2C_H - 1 < Qr.j1) ? J0 + D2C_H - 1 : Qr.j1;
-  auto at = [&](const Fld& f, int i, int j) -> size_t { return (size_t)(tile * f.nk + k - 1) * g.plane + (size_t)g.idx(i, j); };
+  const TileBlk B = tile_blk(Qr, bx, by, D2C_W, D2C_H);
+  const int I0 = B.I0, I1 = B.I1, J0 = B.J0, J1 = B.J1;
   double* const U = lds; double* const V = U + D2C_NQ; double* const UT = V + D2C_NQ; double* const VT = UT + D2C_NUT;
   // ---- u on [I0-2, I1+1] x [J0-1, J1+2], v on [I0-1, I1+2] x [J0-2, J1+1].  Every element of a tile is loaded, from its index clamped
   // into the plane and the block's reach (more than is read below; a clamped element is never read): loads without a branch around
@@ -124,8 +115,8 @@ DEV void d2a2c_block(const D2a2cArgs& a, const Ctx& c, const Rect& Qr, int tile,
     D2C_UNROLL
     for (int s = 0; s < E; ++s) {
       const int e = (tid + s * NTH < D2C_NQ) ? tid + s * NTH : D2C_NQ - 1, x = e % D2C_QW, r = e / D2C_QW;
-      ru[s] = IO::ld(a.u, at(a.u, ci(I0 - 2 + x), cj(J0 - 1 + r)));
-      rv[s] = IO::ld(a.v, at(a.v, ci(I0 - 1 + x), cj(J0 - 2 + r)));
+      ru[s] = IO::ld(a.u, fld_at(g, a.u, tile, k, ci(I0 - 2 + x), cj(J0 - 1 + r)));
+      rv[s] = IO::ld(a.v, fld_at(g, a.v, tile, k, ci(I0 - 1 + x), cj(J0 - 2 + r)));
     }
     D2C_UNROLL
     for (int s = 0; s < E; ++s) {
@@ -171,32 +162,30 @@ DEV void d2a2c_block(const D2a2cArgs& a, const Ctx& c, const Rect& Qr, int tile,
     if (a.ra.has(i, j)) {
       const T ut = utmp(i), vt = vtmp(j);
       const double cs = mm[M_CS], r2 = mm[M_R2];
-      IO::st(a.ua, at(a.ua, i, j), (ut - vt * cs) * r2);
-      IO::st(a.va, at(a.va, i, j), (vt - ut * cs) * r2);
+      IO::st(a.ua, fld_at(g, a.ua, tile, k, i, j), (ut - vt * cs) * r2);
+      IO::st(a.va, fld_at(g, a.va, tile, k, i, j), (vt - ut * cs) * r2);
     }
     if (a.ru.has(i, j)) {
       const T uc = A2 * (utmp(i - 2) + utmp(i + 1)) + A1 * (utmp(i - 1) + utmp(i));
       const T ut = (uc - IO::lget(V, D2C_NT, (r + 2) * D2C_QW + (x + 1)) * mm[M_CU]) * mm[M_RU];
-      IO::st(a.uc0, at(a.uc0, i, j), uc);
-      IO::st(a.utf, at(a.utf, i, j), (val(ut) > 0.) ? a.dt2 * ut * mm[M_DY] * mm[M_S3] : a.dt2 * ut * mm[M_DY] * mm[M_S1]);
+      IO::st(a.uc0, fld_at(g, a.uc0, tile, k, i, j), uc);
+      IO::st(a.utf, fld_at(g, a.utf, tile, k, i, j), (val(ut) > 0.) ? a.dt2 * ut * mm[M_DY] * mm[M_S3] : a.dt2 * ut * mm[M_DY] * mm[M_S1]);
     }
     if (a.rv.has(i, j)) {
       const T vc = A2 * (vtmp(j - 2) + vtmp(j + 1)) + A1 * (vtmp(j - 1) + vtmp(j));
       const T vt = (vc - IO::lget(U, D2C_NT, (r + 1) * D2C_QW + (x + 2)) * mm[M_CV]) * mm[M_RV];
-      IO::st(a.vc0, at(a.vc0, i, j), vc);
-      IO::st(a.vtf, at(a.vtf, i, j), (val(vt) > 0.) ? a.dt2 * vt * mm[M_DX] * mm[M_S4] : a.dt2 * vt * mm[M_DX] * mm[M_S2]);
+      IO::st(a.vc0, fld_at(g, a.vc0, tile, k, i, j), vc);
+      IO::st(a.vtf, fld_at(g, a.vtf, tile, k, i, j), (val(vt) > 0.) ? a.dt2 * vt * mm[M_DX] * mm[M_S4] : a.dt2 * vt * mm[M_DX] * mm[M_S2]);
     }
   }
 }
 
-// One block of the adjoint: the points I0..I1 x J0..J1 of u_ad, v_ad, blocks laid over Qr (d2a2c_ad_rect).
+// One block of the adjoint: the points I0..I1 x J0..J1 of u_ad, v_ad, blocks laid over Qr (run_d2a2c).
 template <int NTH>
-DEV void d2a2c_ad_block(const D2a2cArgs& a, const Ctx& c, const Rect& Qr, int tile, int k, int bx, int by, double* lds, int tid, int nth) {
-  (void)nth;
+DEV void d2a2c_ad_block(const D2a2cArgs& a, const Ctx& c, const Rect& Qr, int tile, int k, int bx, int by, double* lds, int tid) {
   const Geom& g = c.g;
-  const int I0 = Qr.i0 + bx * D2C_W, I1 = (I0 + D2C_W - 1 < Qr.i1) ? I0 + D2C_W - 1 : Qr.i1;
-  const int J0 = Qr.j0 + by * D2C_H, J1 = (J0 + D2C_H - 1 < Qr.j1) ? J0 + D2C_H - 1 : Qr.j1;
-  auto at = [&](const Fld& f, int i, int j) -> size_t { return (size_t)(tile * f.nk + k - 1) * g.plane + (size_t)g.idx(i, j); };
+  const TileBlk B = tile_blk(Qr, bx, by, D2C_W, D2C_H);
+  const int I0 = B.I0, I1 = B.I1, J0 = B.J0, J1 = B.J1;
   double* const UC = lds; double* const VC = UC + D2C_NQ; double* const GU = VC + D2C_NQ; double* const GV = GU + D2C_NB;
   double* const UTA = GV + D2C_NB; double* const VTA = UTA + D2C_NVT;
   // ---- uc_ad on [I0-1, I0+W+1] x [J0-2, J0+H], vc_ad on [I0-2, I0+W] x [J0-1, J0+H+1]: the adjoint of uc0 + the one of utf through ut (the
@@ -211,7 +200,7 @@ DEV void d2a2c_ad_block(const D2a2cArgs& a, const Ctx& c, const Rect& Qr, int ti
     for (int s = 0; s < E1; ++s) {
       const int e = (tid + s * NTH < D2C_NQ) ? tid + s * NTH : D2C_NQ - 1;
       const int i = d2c_clamp(I0 - 1 + e % D2C_QW, ilo, ihi), j = d2c_clamp(J0 - 2 + e / D2C_QW, jlo, jhi);
-      const size_t m = at(a.utf, i, j);
+      const size_t m = fld_at(g, a.utf, tile, k, i, j);
       q[s][0] = a.utf.t[m]; q[s][1] = a.utf.p[m]; q[s][2] = a.uc0.p[m];
       q[s][3] = MET(dy, i, j); q[s][4] = SSG(3, i - 1, j); q[s][5] = SSG(1, i, j); q[s][6] = MET(rsin_u, i, j);
     }
@@ -236,7 +225,7 @@ DEV void d2a2c_ad_block(const D2a2cArgs& a, const Ctx& c, const Rect& Qr, int ti
     for (int s = 0; s < E1; ++s) {
       const int e = (tid + s * NTH < D2C_NQ) ? tid + s * NTH : D2C_NQ - 1;
       const int i = d2c_clamp(I0 - 2 + e % D2C_QW, ilo, ihi), j = d2c_clamp(J0 - 1 + e / D2C_QW, jlo, jhi);
-      const size_t m = at(a.vtf, i, j);
+      const size_t m = fld_at(g, a.vtf, tile, k, i, j);
       q[s][0] = a.vtf.t[m]; q[s][1] = a.vtf.p[m]; q[s][2] = a.vc0.p[m];
       q[s][3] = MET(dx, i, j); q[s][4] = SSG(4, i, j - 1); q[s][5] = SSG(2, i, j); q[s][6] = MET(rsin_v, i, j);
     }
@@ -264,7 +253,7 @@ DEV void d2a2c_ad_block(const D2a2cArgs& a, const Ctx& c, const Rect& Qr, int ti
     for (int s = 0; s < E2; ++s) {
       const int e = (tid + s * NTH < D2C_NVT) ? tid + s * NTH : D2C_NVT - 1;
       const int i = d2c_clamp(I0 + e % D2C_W, ilo, ihi), j = d2c_clamp(J0 - 2 + e / D2C_W, jlo, jhi);
-      const size_t m = at(a.ua, i, j);
+      const size_t m = fld_at(g, a.ua, tile, k, i, j);
       q[s][0] = a.ua.p[m]; q[s][1] = a.va.p[m]; q[s][2] = MET(rsin2, i, j); q[s][3] = MET(cosa_s, i, j);
     }
     D2C_UNROLL
@@ -288,7 +277,7 @@ DEV void d2a2c_ad_block(const D2a2cArgs& a, const Ctx& c, const Rect& Qr, int ti
     for (int s = 0; s < E2; ++s) {
       const int e = (tid + s * NTH < D2C_NUT) ? tid + s * NTH : D2C_NUT - 1;
       const int i = d2c_clamp(I0 - 2 + e % D2C_QW, ilo, ihi), j = d2c_clamp(J0 + e / D2C_QW, jlo, jhi);
-      const size_t m = at(a.ua, i, j);
+      const size_t m = fld_at(g, a.ua, tile, k, i, j);
       q[s][0] = a.ua.p[m]; q[s][1] = a.va.p[m]; q[s][2] = MET(rsin2, i, j); q[s][3] = MET(cosa_s, i, j);
     }
     D2C_UNROLL
@@ -315,7 +304,7 @@ DEV void d2a2c_ad_block(const D2a2cArgs& a, const Ctx& c, const Rect& Qr, int ti
   for (int s = 0; s < E3; ++s) {
     const int e = (tid + s * NTH < D2C_NB) ? tid + s * NTH : D2C_NB - 1;
     const int i = (I0 + e % D2C_W < I1) ? I0 + e % D2C_W : I1, j = (J0 + e / D2C_W < J1) ? J0 + e / D2C_W : J1;      // the block's own points: in the plane
-    const size_t m = at(a.u, i, j);
+    const size_t m = fld_at(g, a.u, tile, k, i, j);
     q[s][0] = acc_u ? a.u.p[m] : 0.; q[s][1] = acc_v ? a.v.p[m] : 0.; q[s][2] = MET(cosa_v, i, j); q[s][3] = MET(cosa_u, i, j);
   }
   D2C_UNROLL
@@ -333,45 +322,22 @@ DEV void d2a2c_ad_block(const D2a2cArgs& a, const Ctx& c, const Rect& Qr, int ti
     }
     if (a.rv.has(i, j)) au -= q[s][2] * GV[e];
     if (a.ru.has(i, j)) av -= q[s][3] * GU[e];
-    const size_t m = at(a.u, i, j);
+    const size_t m = fld_at(g, a.u, tile, k, i, j);
     if (a.u.p) a.u.p[m] = q[s][0] + au;
     if (a.v.p) a.v.p[m] = q[s][1] + av;
     if (a.clear_tmp && a.rtmp.has(i, j) && d2c_band(a, g, i, j)) { a.utmp.p[m] = 0.; a.vtmp.p[m] = 0.; }
   }
 }
 
-// the rectangle the adjoint launch is laid over: three points around everything the bulk forms (the reach of the two interpolations),
-// where the zeros of utmp_ad / vtmp_ad go, and in store mode where the stored adjoint is read later
-inline Rect d2a2c_ad_rect(const D2a2cArgs& a, const Geom& g) {
-  Rect q = a.all();
-  q.i0 -= 3; q.i1 += 3; q.j0 -= 3; q.j1 += 3;
-  auto grow = [&](const Rect& r) {
-    if (r.i0 > r.i1 || r.j0 > r.j1) return;
-    q.i0 = std::min(q.i0, r.i0); q.i1 = std::max(q.i1, r.i1); q.j0 = std::min(q.j0, r.j0); q.j1 = std::max(q.j1, r.j1);
-  };
-  if (a.clear_tmp) grow(a.rtmp);
-  if (a.wmask) grow(a.wrect);
-  if (q.i0 < g.isd()) q.i0 = g.isd();
-  if (q.j0 < g.jsd()) q.j0 = g.jsd();
-  if (q.i1 > g.ied() + 1) q.i1 = g.ied() + 1;
-  if (q.j1 > g.jed() + 1) q.j1 = g.jed() + 1;
-  return q;
-}
-
-#ifndef FV3LM_HOST_EMUL
-template <class T, int NTH>
-__global__ void __launch_bounds__(NTH) k_d2a2c(D2a2cArgs a, Ctx c, Rect Qr) {
-  extern __shared__ double d2c_lds[];
-  int bx = blockIdx.x, by = blockIdx.y; xcd_block(gridDim.x, gridDim.y, bx, by);
-  d2a2c_block<T, NTH>(a, c, Qr, blockIdx.z / a.nk, 1 + blockIdx.z % a.nk, bx, by, d2c_lds, threadIdx.x, NTH);
-}
-template <int NTH>
-__global__ void __launch_bounds__(NTH) k_d2a2c_ad(D2a2cArgs a, Ctx c, Rect Qr) {
-  extern __shared__ double d2c_lds[];
-  int bx = blockIdx.x, by = blockIdx.y; xcd_block(gridDim.x, gridDim.y, bx, by);
-  d2a2c_ad_block<NTH>(a, c, Qr, blockIdx.z / a.nk, 1 + blockIdx.z % a.nk, bx, by, d2c_lds, threadIdx.x, NTH);
-}
-#endif
+// the block descriptors (tiled.h)
+template <class T, int N> struct D2a2cFwd {
+  typedef D2a2cArgs Args; static constexpr int NTH = N; static constexpr size_t LDS_BYTES = (size_t)D2C_NT * 8 * TpfIO<T>::NC;
+  DEV static void block(const Args& a, const Ctx& c, const Rect& Qr, int tile, int k, int bx, int by, double* lds, int tid) { d2a2c_block<T, N>(a, c, Qr, tile, k, bx, by, lds, tid); }
+};
+template <int N> struct D2a2cAd {
+  typedef D2a2cArgs Args; static constexpr int NTH = N; static constexpr size_t LDS_BYTES = (size_t)D2C_NT_AD * 8;
+  DEV static void block(const Args& a, const Ctx& c, const Rect& Qr, int tile, int k, int bx, int by, double* lds, int tid) { d2a2c_ad_block<N>(a, c, Qr, tile, k, bx, by, lds, tid); }
+};
 
 FV3LM_LINK void run_d2a2c(Exec& ex, int mode, const D2a2cArgs& a0, const Ctx& c) {
   D2a2cArgs a = a0;
@@ -379,26 +345,19 @@ FV3LM_LINK void run_d2a2c(Exec& ex, int mode, const D2a2cArgs& a0, const Ctx& c)
   if (ex.no_wmask) a.wmask = 0;
   if (!a.utmp.p || !a.vtmp.p) a.clear_tmp = 0;
   if (mode == MODE_AD && !a.u.p && !a.v.p && !a.clear_tmp) return;
-  const Rect Qr = mode == MODE_AD ? d2a2c_ad_rect(a, c.g) : a.all();
-  const int nbx = (Qr.i1 - Qr.i0 + D2C_W) / D2C_W, nby = (Qr.j1 - Qr.j0 + D2C_H) / D2C_H, nz = c.g.ntile * a.nk;
-  ex.mark_begin("D2a2c", mode == MODE_NL ? ".nl" : mode == MODE_TL ? ".tl" : ".ad", d2a2c_bytes(a, c.g, mode));
-#ifdef FV3LM_HOST_EMUL
-  std::vector<double> lds((size_t)std::max(D2C_NT * 2, D2C_NT_AD));
-  for (int z = 0; z < nz; ++z)
-    for (int by = 0; by < nby; ++by)
-      for (int bx = 0; bx < nbx; ++bx) {
-        if (mode == MODE_TL) d2a2c_block<Dual, 1>(a, c, Qr, z / a.nk, 1 + z % a.nk, bx, by, lds.data(), 0, 1);
-        else if (mode == MODE_NL) d2a2c_block<double, 1>(a, c, Qr, z / a.nk, 1 + z % a.nk, bx, by, lds.data(), 0, 1);
-        else d2a2c_ad_block<1>(a, c, Qr, z / a.nk, 1 + z % a.nk, bx, by, lds.data(), 0, 1);
-      }
-#else
-  const dim3 grid(nbx, nby, nz);
-  if (mode == MODE_TL) hipLaunchKernelGGL((k_d2a2c<Dual, FV3LM_D2A2C_THREADS_TL>), grid, dim3(FV3LM_D2A2C_THREADS_TL), D2C_NT * 16, ex.stream, a, c, Qr);
-  else if (mode == MODE_NL) hipLaunchKernelGGL((k_d2a2c<double, FV3LM_D2A2C_THREADS_NL>), grid, dim3(FV3LM_D2A2C_THREADS_NL), D2C_NT * 8, ex.stream, a, c, Qr);
-  else hipLaunchKernelGGL((k_d2a2c_ad<FV3LM_D2A2C_THREADS_AD>), grid, dim3(FV3LM_D2A2C_THREADS_AD), D2C_NT_AD * 8, ex.stream, a, c, Qr);
-#endif
-  ex.mark_end();
-  ex.launches++;
+  Rect Qr = a.all();
+  if (mode == MODE_AD) {
+    // three points around everything the bulk forms (the reach of the two interpolations), where the zeros of utmp_ad / vtmp_ad go, and
+    // in store mode where the stored adjoint is read later
+    Qr.i0 -= 3; Qr.i1 += 3; Qr.j0 -= 3; Qr.j1 += 3;
+    if (a.clear_tmp) Qr = rect_join(Qr, a.rtmp);
+    Qr = ad_launch_rect(Qr, a.wmask != 0, a.wrect, c.g);
+  }
+  const int nbx = tiled_blocks(Qr.i0, Qr.i1, D2C_W), nby = tiled_blocks(Qr.j0, Qr.j1, D2C_H);
+  const double bytes = d2a2c_bytes(a, c.g, mode);
+  if (mode == MODE_TL) run_tiled<D2a2cFwd<Dual, tiled_nth(FV3LM_D2A2C_THREADS_TL)>>(ex, "D2a2c", mode_tag(mode), bytes, Qr, nbx, nby, a, c);
+  else if (mode == MODE_NL) run_tiled<D2a2cFwd<double, tiled_nth(FV3LM_D2A2C_THREADS_NL)>>(ex, "D2a2c", mode_tag(mode), bytes, Qr, nbx, nby, a, c);
+  else run_tiled<D2a2cAd<tiled_nth(FV3LM_D2A2C_THREADS_AD)>>(ex, "D2a2c", mode_tag(mode), bytes, Qr, nbx, nby, a, c);
 }
 
 }  // namespace fv3

@@ -338,6 +338,22 @@ struct Dycore {
     op.name = St::name();
     P.push_back(op);
   }
+  // A hand-written LDS-tiled launch (tiled.h) as an op: `run(exec, mode, args, ctx)` in the modes of `modes`; ad_in (with the slots of
+  // the write mask) the adjoints its adjoint accumulates into or, in write mode, stores; ad_out the ones it reads, formed forward over
+  // ad_out_rect; ad_store the ones it stores whatever the plan says.  Args with a write mask (wmask, wrect) take part in plan_adjoint.
+  struct TiledAd { std::vector<double*> in; std::vector<int> in_slot; std::vector<double*> out; std::vector<Rect> out_rect; std::vector<double*> store; };
+  template <class A, class = void> struct has_wmask : std::false_type {};
+  template <class A> struct has_wmask<A, decltype((void)std::declval<A&>().wmask, (void)std::declval<A&>().wrect)> : std::true_type {};
+  template <class A, class F>
+  Op& add_tiled(Program& P, const char* group, const char* name, std::shared_ptr<A> ap, F run, unsigned modes, const TiledAd& ad = TiledAd{}) {
+    Ctx* cp = &ctx;
+    Op op{group, [ap, cp, run](Exec& e, int mode) { run(e, mode, *ap, *cp); }};
+    op.name = name; op.modes = modes;
+    op.ad_in = ad.in; op.ad_in_slot = ad.in_slot; op.ad_out = ad.out; op.ad_out_rect = ad.out_rect; op.ad_store = ad.store;
+    if constexpr (has_wmask<A>::value) op.set_wmask = [ap](unsigned w, Rect r) { ap->wmask = w; ap->wrect = r; };
+    P.push_back(op);
+    return P.back();
+  }
   // several instances of one stage type (the edge strips of a face) as one launch (exec.h run_multi)
   template <class St>
   void add_multi(Program& P, const char* group, const std::vector<St>& v) {
@@ -491,8 +507,7 @@ struct Dycore {
     const int is = g.is(), ie = g.ie(), js = g.js(), je = g.je(), isd = g.isd(), ied = g.ied(), jsd = g.jsd(), jed = g.jed(), npz = nk ? nk : g.npz;
     // nonlinear and tangent modes: the whole routine as one LDS-tiled launch (tpfused.h); the staged launches below then serve the
     // adjoint only (FV3LM_TP_FUSED=0 runs them in every mode -- the two forms agree bit for bit)
-    const char* fenv = std::getenv("FV3LM_TP_FUSED");
-    const bool fused = !(fenv && fenv[0] == '0');
+    const bool fused = switch_on("FV3LM_TP_FUSED");
     // The outer fluxes fxo, fyo are trajectory arrays of their own only while something reads them: the staged flux assembly.  With the
     // hand-written outer adjoint (which re-evaluates them from q_i, q_j in passing) they are neither stored by the nonlinear launch nor
     // part of a trajectory slot; the names then alias fx2 / fy2 for the staged ops that never run.
@@ -590,14 +605,12 @@ struct Dycore {
       a.hsel = hsel; a.dsel = dsel; a.use_mass = use_mass ? 1 : 0; a.nk = npz;
       a.do_acc = 0; a.store_fo = own_fo ? 1 : 0; a.store_mid = own_mid ? 1 : 0;
       if (acc4) { a.acx = acc4[0]; a.acy = acc4[1]; a.amfx = acc4[2]; a.amfy = acc4[3]; }
-      Ctx* cp = &ctx;
-      Op op{grp, [a, cp](Exec& e, int mode) { run_tp_fused(e, mode, a, *cp); }};
-      op.modes = (1u << MODE_NL) | (1u << MODE_TL);
-      op.name = "TpFused";
+      const unsigned fwd = (1u << MODE_NL) | (1u << MODE_TL);
       // what the launch reads / writes (add_halo_async looks for the last op that touches a field; plan_adjoint skips this op: not an adjoint op)
-      for (const Fld* f_ : {&a.q, &a.crx, &a.cry, &a.xfx, &a.yfx, &a.rax, &a.ray, &a.mx, &a.my, &a.mass, &a.d2b}) if (f_->p) op.ad_in.push_back(f_->p);
-      for (const Fld* f_ : {&a.fx, &a.fy, &a.fy2, &a.q_i, &a.fxo, &a.fx2, &a.q_j, &a.fyo, &a.acx, &a.acy, &a.amfx, &a.amfy}) if (f_->p) op.ad_out.push_back(f_->p);
-      P.push_back(op);
+      TiledAd io;
+      for (const Fld* f_ : {&a.q, &a.crx, &a.cry, &a.xfx, &a.yfx, &a.rax, &a.ray, &a.mx, &a.my, &a.mass, &a.d2b}) if (f_->p) io.in.push_back(f_->p);
+      for (const Fld* f_ : {&a.fx, &a.fy, &a.fy2, &a.q_i, &a.fxo, &a.fx2, &a.q_j, &a.fyo, &a.acx, &a.acy, &a.amfx, &a.amfy}) if (f_->p) io.out.push_back(f_->p);
+      add_tiled(P, grp, "TpFused", std::make_shared<TpFusedArgs>(a), [](Exec& e, int mode, const TpFusedArgs& a_, const Ctx& c_) { run_tp_fused(e, mode, a_, c_); }, fwd, io);
       if (any_split) {       // the trajectory pass of the split levels: its own damping Laplacian (run as a nonlinear launch in the tangent mode too), then the chain
         if (need_d2t) {
           Fld d2t = W((pre + "_d2t").c_str(), npz);
@@ -621,9 +634,7 @@ struct Dycore {
           first_substep_only(n0);
           a.d2b_t = d2t;
         }
-        Op tr{grp, [a, cp](Exec& e, int mode) { run_tp_fused(e, mode, a, *cp, true); }};
-        tr.modes = (1u << MODE_NL) | (1u << MODE_TL); tr.name = "TpFusedTraj";
-        P.push_back(tr);
+        add_tiled(P, grp, "TpFusedTraj", std::make_shared<TpFusedArgs>(a), [](Exec& e, int mode, const TpFusedArgs& a_, const Ctx& c_) { run_tp_fused(e, mode, a_, c_, true); }, fwd);
       }
       // adjoint: the whole routine as ONE hand-written launch (tpad.h); the staged launches then never run, the damping part of the flux keeps a
       // (small) stage of its own.  FV3LM_TP_AD_FUSED=1: round 2's form (outer half fused, inner half staged); =0: all staged.
@@ -640,12 +651,12 @@ struct Dycore {
           add(P, grp, dm); P.back().modes = 1u << MODE_AD;
           first_substep_only(n0);
         }
-        Op ad{grp, [a, cp, adf](Exec& e, int) { if (adf == 2) run_tp_ad(e, a, *cp); else run_tp_outer_ad(e, a, *cp); }};
-        ad.modes = 1u << MODE_AD; ad.name = adf == 2 ? "TpAd" : "TpOuter";
-        ad.ad_out = {fx.p, fy.p}; ad.ad_out_rect = {R(is, ie + 1, js, je), R(is, ie, js, je + 1)};
-        if (adf == 2) ad.ad_in = {q.p, crx.p, cry.p, xfx.p, yfx.p, rax.p, ray.p, mx.p, my.p};
-        else { ad.ad_store = {q_i.p, q_j.p, fx2.p, fy2.p}; ad.ad_in = {crx.p, cry.p, mx.p, my.p}; }
-        P.push_back(ad);
+        TiledAd ad; ad.out = {fx.p, fy.p}; ad.out_rect = {R(is, ie + 1, js, je), R(is, ie, js, je + 1)};
+        if (adf == 2) ad.in = {q.p, crx.p, cry.p, xfx.p, yfx.p, rax.p, ray.p, mx.p, my.p};
+        else { ad.store = {q_i.p, q_j.p, fx2.p, fy2.p}; ad.in = {crx.p, cry.p, mx.p, my.p}; }
+        const auto ap = std::make_shared<TpFusedArgs>(a);
+        if (adf == 2) add_tiled(P, grp, "TpAd", ap, [](Exec& e, int, const TpFusedArgs& a_, const Ctx& c_) { run_tp_ad(e, a_, c_); }, 1u << MODE_AD, ad);
+        else add_tiled(P, grp, "TpOuter", ap, [](Exec& e, int, const TpFusedArgs& a_, const Ctx& c_) { run_tp_outer_ad(e, a_, c_); }, 1u << MODE_AD, ad);
       }
     }
   }
@@ -657,23 +668,18 @@ struct Dycore {
     A2bA_<false> a; a.in[0] = q; a.out[0] = qx; a.out[1] = qy; a.k1 = nk;
     A2bB_<false> b; b.in[0] = qx; b.in[1] = qy; b.in[2] = Fld{}; b.out[0] = qb; b.k1 = nk;
     // the bulk as one LDS-tiled launch per mode (a2b.h); FV3LM_A2B_FUSED=0: the two staged launches
-    const char* fenv = std::getenv("FV3LM_A2B_FUSED");
-    const bool fuse_on = !(fenv && fenv[0] == '0') && q.nk == nk && qb.nk == nk;
+    const bool fuse_on = switch_on("FV3LM_A2B_FUSED") && q.nk == nk && qb.nk == nk;
     auto same = [](const Rect& x, const Rect& y) { return x.i0 == y.i0 && x.i1 == y.i1 && x.j0 == y.j0 && x.j1 == y.j1; };
     A2bArgs fa; fa.q = q; fa.qb = qb; fa.qx = qx; fa.qy = qy; fa.nk = nk; fa.rim = g.face ? 1 : 0;
     // the fused launch derives the rectangles of qx, qy from the one of qb: it stands in where the staged rectangles are those (every
     // periodic tile, whole face and window of a face wider than the stencil), the staged launches stay otherwise
     auto fusable = [&]() { fa.rb = b.orect[0]; return fuse_on && !is_empty(fa.rb) && same(a.orect[0], fa.rx()) && same(a.orect[1], fa.ry()); };
     auto add_fused = [&]() {
-      Ctx* cp = &ctx;
-      auto ap = std::make_shared<A2bArgs>(fa);
-      Op op{grp, [ap, cp](Exec& e, int mode) { run_a2b(e, mode, *ap, *cp); }};
-      op.name = "A2b";
-      if (q.p) { op.ad_in = {q.p}; op.ad_in_slot = {0}; }
-      op.ad_out = {qb.p}; op.ad_out_rect = {fa.rb};
-      if (fa.rim) { op.ad_out.push_back(qx.p); op.ad_out.push_back(qy.p); op.ad_out_rect.push_back(fa.rx()); op.ad_out_rect.push_back(fa.ry()); }
-      op.set_wmask = [ap](unsigned w, Rect r) { ap->wmask = w; ap->wrect = r; };
-      P.push_back(op);
+      TiledAd ad;
+      if (q.p) { ad.in = {q.p}; ad.in_slot = {0}; }
+      ad.out = {qb.p}; ad.out_rect = {fa.rb};
+      if (fa.rim) { ad.out.push_back(qx.p); ad.out.push_back(qy.p); ad.out_rect.push_back(fa.rx()); ad.out_rect.push_back(fa.ry()); }
+      add_tiled(P, grp, "A2b", std::make_shared<A2bArgs>(fa), run_a2b, 7u, ad);
     };
     if (!g.face) {
       a.orect[0] = R(is, ie + 1, js - 2, je + 2); a.orect[1] = R(is - 2, ie + 2, js, je + 1);
@@ -1164,8 +1170,7 @@ inline void Dycore::build_acoustic() {
   // ---- c_sw
   Fld utmp = W("utmp", npz), vtmp = W("vtmp", npz), ua = W("ua", npz), va = W("va", npz);
   // the bulk of d2a2c_vect as one LDS-tiled launch per mode (d2a2c.h); FV3LM_D2A2C_FUSED=0: the two staged launches
-  const char* d2c_env = std::getenv("FV3LM_D2A2C_FUSED");
-  const bool d2c_fused = !(d2c_env && d2c_env[0] == '0');
+  const bool d2c_fused = switch_on("FV3LM_D2A2C_FUSED");
   D2a2cArgs d2c; d2c.u = u; d2c.v = v; d2c.ua = ua; d2c.va = va; d2c.utmp = utmp; d2c.vtmp = vtmp; d2c.dt2 = dt2; d2c.nk = npz; d2c.face = g.face ? 1 : 0;
   d2c.ru = d2c.rv = d2c.ra = Rect{1, 0, 1, 0};
   const size_t d2c_n0 = P.size();
@@ -1219,17 +1224,12 @@ inline void Dycore::build_acoustic() {
     // strip stream.  Backward it is the first of the routine: it stores the zeros the C strips' adjoint accumulates onto in utmp_ad,
     // vtmp_ad, which the A strips' adjoint then reads -- the staged bulk adjoint that used to store them is gone.
     d2c.clear_tmp = (g.face && utmp.p && vtmp.p) ? 1 : 0;
-    Ctx* cp = &ctx;
-    auto ap = std::make_shared<D2a2cArgs>(d2c);
-    Op op{"c_sw", [ap, cp](Exec& e, int mode) { run_d2a2c(e, mode, *ap, *cp); }};
-    op.name = "D2a2c";
-    op.ad_in = {u.p, v.p}; op.ad_in_slot = {0, 1};
-    op.ad_out = {uc0.p, utf.p, vc0.p, vtf.p, ua.p, va.p};
-    op.ad_out_rect = {d2c.ru, d2c.ru, d2c.rv, d2c.rv, d2c.ra, d2c.ra};
-    if (d2c.clear_tmp) op.ad_store = {utmp.p, vtmp.p};
-    op.set_wmask = [ap](unsigned w, Rect r) { ap->wmask = w; ap->wrect = r; };
+    TiledAd ad; ad.in = {u.p, v.p}; ad.in_slot = {0, 1};
+    ad.out = {uc0.p, utf.p, vc0.p, vtf.p, ua.p, va.p};
+    ad.out_rect = {d2c.ru, d2c.ru, d2c.rv, d2c.rv, d2c.ra, d2c.ra};
+    if (d2c.clear_tmp) ad.store = {utmp.p, vtmp.p};
     const size_t d2c_n1 = P.size();
-    P.push_back(op);
+    add_tiled(P, "c_sw", "D2a2c", std::make_shared<D2a2cArgs>(d2c), run_d2a2c, 7u, ad);
     beside_bulk(P, d2c_n0, d2c_n1);
   }
   Fld divgd = W("divgd", npz);
@@ -1315,7 +1315,7 @@ inline void Dycore::build_acoustic() {
   Fld fx = W("fx", npz), fy = W("fy", npz), gx = W("gx", npz), gy = W("gy", npz);
   // the flux capacitors ride along in the fused fv_tp_2d launch of delp (nonlinear + tangent); their staged form serves the adjoint
   const Fld acc4[4] = {cx, cy, mfx, mfy};
-  const bool tpf_on = !(std::getenv("FV3LM_TP_FUSED") && std::getenv("FV3LM_TP_FUSED")[0] == '0');
+  const bool tpf_on = switch_on("FV3LM_TP_FUSED");
   build_tp(P, "d_sw", "tpd", delp, crx, cry, xfx, yfx, rax, ray, xfx, yfx, Fld{}, HORD_DP, DAMP_V, false, fx, fy, 0, tpf_on ? acc4 : nullptr);
   { const size_t n0 = P.size();
     add_accum(P, "d_sw", cx, crx, R(is, ie + 1, jsd, jed)); add_accum(P, "d_sw", mfx, fx, R(is, ie + 1, js, je));

@@ -20,6 +20,8 @@ namespace fv3 {
 // (like one MPI rank of the reference), so the record is per process.
 inline std::string& sticky_error() { static std::string e; return e; }
 inline void set_sticky(const std::string& m) { if (sticky_error().empty()) sticky_error() = m; }
+// a run-time switch of the environment that is on unless set to a value starting with 0
+inline bool switch_on(const char* name) { const char* e = std::getenv(name); return !(e && e[0] == '0'); }
 
 // Per-kernel measurement: HIP events recorded on the library's own stream around every launch while
 // profiling is on (bench.py's roofline leg), aggregated by kernel name together with the algorithmic
@@ -96,6 +98,23 @@ HD Rect rect_union(const Rect* r, int n) {
     if (r[m].j1 > u.j1) u.j1 = r[m].j1;
   }
   return u;
+}
+// the union of two rectangles of which either may be empty
+HD Rect rect_join(const Rect& a, const Rect& b) {
+  if (b.i0 > b.i1 || b.j0 > b.j1) return a;
+  if (a.i0 > a.i1 || a.j0 > a.j1) return b;
+  const Rect both[2] = {a, b};
+  return rect_union(both, 2);
+}
+// The rectangle an adjoint launch is laid over: its reach q; in store mode also wrect, where the stored adjoints are read later although
+// the launch does not reach; clamped to the padded plane.
+inline Rect ad_launch_rect(Rect q, bool store, const Rect& wrect, const Geom& g) {
+  if (store) q = rect_join(q, wrect);
+  if (q.i0 < g.isd()) q.i0 = g.isd();
+  if (q.j0 < g.jsd()) q.j0 = g.jsd();
+  if (q.i1 > g.ied() + 1) q.i1 = g.ied() + 1;
+  if (q.j1 > g.jed() + 1) q.j1 = g.jed() + 1;
+  return q;
 }
 
 // ---- per-point bodies ---------------------------------------------------------------------
@@ -348,15 +367,7 @@ inline Rect ad_input_rect(const S& s, const Ctx& c, const Rect& R) {
     if (R.j0 + b.dj0 < q.j0) q.j0 = R.j0 + b.dj0;
     if (R.j1 + b.dj1 > q.j1) q.j1 = R.j1 + b.dj1;
   }
-  if (s.wmask && s.wrect.i0 <= s.wrect.i1) {     // write mode: also where the stored adjoints are read later although this stage does not reach
-    if (s.wrect.i0 < q.i0) q.i0 = s.wrect.i0; if (s.wrect.i1 > q.i1) q.i1 = s.wrect.i1;
-    if (s.wrect.j0 < q.j0) q.j0 = s.wrect.j0; if (s.wrect.j1 > q.j1) q.j1 = s.wrect.j1;
-  }
-  if (q.i0 < c.g.isd()) q.i0 = c.g.isd();
-  if (q.j0 < c.g.jsd()) q.j0 = c.g.jsd();
-  if (q.i1 > c.g.ied() + 1) q.i1 = c.g.ied() + 1;
-  if (q.j1 > c.g.jed() + 1) q.j1 = c.g.jed() + 1;
-  return q;
+  return ad_launch_rect(q, s.wmask != 0, s.wrect, c.g);
 }
 
 enum Mode { MODE_NL = 0, MODE_TL = 1, MODE_AD = 2 };

@@ -108,7 +108,8 @@ DEV T tp2_flux2(const T* p, const T& cc, bool up, const double* w0, const double
   return qt + (1. - sc) * (al0 - qt - sc * (B + al0 - (qt + qt)));
 }
 
-// One block: cells I0..I1 x J0..J1 of level k of one tile.  NWV waves share it (host emulation: NWV = 1, tid = 0).
+// One block: cells I0..I1 x J0..J1 of level k of one tile, blocks laid over the tile's window.  NWV waves share it (host emulation:
+// NWV = 1, tid = 0).
 template <class T, int NWV>
 DEV void tp2_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, int by, T* lds, int tid) {
   // timing experiments (tools/kbench.py --group, a library built with -DFV3LM_TP2_EXP=1; results are garbage): a.exp bit 0 = fluxes without
@@ -128,8 +129,8 @@ DEV void tp2_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, 
   const int nx = g.nx, ny = g.ny, pi = g.pi;
   const bool face = g.face != 0;
   const int is = g.is(), ie = g.ie(), js = g.js(), je = g.je();      // the tile's window of the face (nx, ny: the FACE, for the edge formulas)
-  const int I0 = is + bx * TP2_W, I1 = (I0 + TP2_W - 1 < ie) ? I0 + TP2_W - 1 : ie;
-  const int J0 = js + by * TP2_H, J1 = (J0 + TP2_H - 1 < je) ? J0 + TP2_H - 1 : je;
+  const TileBlk B = tile_blk(Rect{is, ie, js, je}, bx, by, TP2_W, TP2_H);
+  const int I0 = B.I0, I1 = B.I1, J0 = B.J0, J1 = B.J1;
   const bool firstx = bx == 0, lastx = I1 == ie, firsty = by == 0, lasty = J1 == je;
   const size_t base = (size_t)(tile * a.nk + k - 1) * g.plane + (size_t)g.idx(I0 - 3, J0 - 3);     // element (x, r) of the halo'd tile: base + r * pi + x
   const size_t mbase = (size_t)tile * g.plane + (size_t)g.idx(I0 - 3, J0 - 3);
@@ -352,16 +353,11 @@ DEV void tp2_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, 
   });
 }
 
-inline void tp2_grid(const Geom& g, int& nbx, int& nby) { nbx = (g.tx + TP2_W - 1) / TP2_W; nby = (g.ty + TP2_H - 1) / TP2_H; }
-
-#ifndef FV3LM_HOST_EMUL
-template <class T, int NWV>
-__global__ void __launch_bounds__(64 * NWV) k_tp2(TpFusedArgs a, Ctx c) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char tp2_lds[];
-  int bx = blockIdx.x, by = blockIdx.y; xcd_block(gridDim.x, gridDim.y, bx, by);
-  tp2_block<T, NWV>(a, c, blockIdx.z / a.nk, 1 + blockIdx.z % a.nk, bx, by, reinterpret_cast<T*>(tp2_lds), threadIdx.x);
-}
-#endif
+// the block descriptor (tiled.h)
+template <class T, int NWV> struct Tp2Blk {
+  typedef TpFusedArgs Args; static constexpr int NTH = 64 * NWV; static constexpr size_t LDS_BYTES = tp2_lds_bytes<T>();
+  DEV static void block(const Args& a, const Ctx& c, const Rect&, int tile, int k, int bx, int by, double* lds, int tid) { tp2_block<T, NWV>(a, c, tile, k, bx, by, reinterpret_cast<T*>(lds), tid); }
+};
 
 // nonlinear (nothing stored for the staged adjoint) / tangent-linear launch; profile names as tpfused.h: it is the same routine
 FV3LM_LINK void run_tp2(Exec& ex, int mode, const TpFusedArgs& a0, const Ctx& c) {
@@ -372,29 +368,10 @@ FV3LM_LINK void run_tp2(Exec& ex, int mode, const TpFusedArgs& a0, const Ctx& c)
 #if FV3LM_TP2_EXP
   if (const char* e = std::getenv("FV3LM_TP2_EXPERIMENT")) a.exp = std::atoi(e);
 #endif
-  int nbx, nby; tp2_grid(c.g, nbx, nby);
-  ex.mark_begin("TpFused", mode == MODE_TL ? ".tl" : ".nl", tpf_bytes(a, c.g, mode));
-#ifdef FV3LM_HOST_EMUL
-  std::vector<double> lds((tp2_lds_bytes<Dual>() + 7) / 8);
-  for (int z = 0; z < c.g.ntile * a.nk; ++z)
-    for (int by = 0; by < nby; ++by)
-      for (int bx = 0; bx < nbx; ++bx) {
-        if (mode == MODE_TL) tp2_block<Dual, 1>(a, c, z / a.nk, 1 + z % a.nk, bx, by, reinterpret_cast<Dual*>(lds.data()), 0);
-        else tp2_block<double, 1>(a, c, z / a.nk, 1 + z % a.nk, bx, by, lds.data(), 0);
-      }
-#else
-  const dim3 grid(nbx, nby, c.g.ntile * a.nk);
-  static bool attr = false;      // more LDS per block than the 64 KB default limit of a launch
-  if (!attr) {
-    if ((tp2_lds_bytes<Dual>() <= 160 * 1024 && hipFuncSetAttribute((const void*)k_tp2<Dual, FV3LM_TP2_WAVES_TL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tp2_lds_bytes<Dual>()) != hipSuccess) ||
-        hipFuncSetAttribute((const void*)k_tp2<double, FV3LM_TP2_WAVES_NL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tp2_lds_bytes<double>()) != hipSuccess) set_sticky("hipFuncSetAttribute(k_tp2) failed");
-    attr = true;
-  }
-  if (mode == MODE_TL) hipLaunchKernelGGL((k_tp2<Dual, FV3LM_TP2_WAVES_TL>), grid, dim3(64 * FV3LM_TP2_WAVES_TL), tp2_lds_bytes<Dual>(), ex.stream, a, c);
-  else hipLaunchKernelGGL((k_tp2<double, FV3LM_TP2_WAVES_NL>), grid, dim3(64 * FV3LM_TP2_WAVES_NL), tp2_lds_bytes<double>(), ex.stream, a, c);
-#endif
-  ex.mark_end();
-  ex.launches++;
+  const Rect Qr = tp_window(c.g);
+  const int nbx = tiled_blocks(Qr.i0, Qr.i1, TP2_W), nby = tiled_blocks(Qr.j0, Qr.j1, TP2_H);
+  if (mode == MODE_TL) run_tiled<Tp2Blk<Dual, tiled_nth(FV3LM_TP2_WAVES_TL)>>(ex, "TpFused", ".tl", tpf_bytes(a, c.g, mode), Qr, nbx, nby, a, c);
+  else run_tiled<Tp2Blk<double, tiled_nth(FV3LM_TP2_WAVES_NL)>>(ex, "TpFused", ".nl", tpf_bytes(a, c.g, mode), Qr, nbx, nby, a, c);
 }
 
 }  // namespace fv3

@@ -123,16 +123,16 @@ DEV void tpd_flux2(bool face, int m, int n1, const double* cell0, double c, cons
   dc = up ? dsc : -dsc;
 }
 
-// One block: cells I0..I1 x J0..J1 of level k of one tile (+ the halo cells next to them in the first / last block row and column).
+// One block: cells I0..I1 x J0..J1 of level k of one tile (+ the halo cells next to them in the first / last block row and column),
+// blocks laid over the tile's window.
 template <int NTH>
-DEV void tp_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, int by, double* lds, int tid, int nth) {
-  (void)nth;
+DEV void tp_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, int by, double* lds, int tid) {
   const Geom& g = c.g;
   const int nx = g.nx, ny = g.ny;                                     // the FACE: cube-edge weights and corner views test global indices against these
   const int is = g.is(), ie = g.ie(), js = g.js(), je = g.je();       // the tile's window of the face: ranges of cells and fluxes
   const bool face = g.face != 0;
-  const int I0 = is + bx * TPD_W, I1 = (I0 + TPD_W - 1 < ie) ? I0 + TPD_W - 1 : ie;
-  const int J0 = js + by * TPD_H, J1 = (J0 + TPD_H - 1 < je) ? J0 + TPD_H - 1 : je;
+  const TileBlk B = tile_blk(Rect{is, ie, js, je}, bx, by, TPD_W, TPD_H);
+  const int I0 = B.I0, I1 = B.I1, J0 = B.J0, J1 = B.J1;
   const bool firstx = bx == 0, lastx = I1 == ie, firsty = by == 0, lasty = J1 == je;
   const int GI0 = firstx ? I0 - 3 : I0, GI1 = lastx ? I1 + 3 : I1, GJ0 = firsty ? J0 - 3 : J0, GJ1 = lasty ? J1 + 3 : J1;     // owned cells incl. the halo
   const size_t base = (size_t)(tile * a.nk + k - 1) * g.plane;
@@ -581,12 +581,13 @@ DEV void tp_ad_corner_point(const TpFusedArgs& a, const Ctx& c, int tile, int k,
   if (s != 0.) a.q.p[at(si, sj)] += s;
 }
 
+// the block descriptor (tiled.h)
+template <int N> struct TpAdBlk {
+  typedef TpFusedArgs Args; static constexpr int NTH = N; static constexpr size_t LDS_BYTES = (size_t)TPD_NT * 8;
+  DEV static void block(const Args& a, const Ctx& c, const Rect&, int tile, int k, int bx, int by, double* lds, int tid) { tp_ad_block<N>(a, c, tile, k, bx, by, lds, tid); }
+};
+
 #ifndef FV3LM_HOST_EMUL
-__global__ void __launch_bounds__(TPD_THREADS) k_tp_ad(TpFusedArgs a, Ctx c) {
-  extern __shared__ double tpd_lds[];
-  int bx = blockIdx.x, by = blockIdx.y; xcd_block(gridDim.x, gridDim.y, bx, by);
-  tp_ad_block<TPD_THREADS>(a, c, blockIdx.z / a.nk, 1 + blockIdx.z % a.nk, bx, by, tpd_lds, threadIdx.x, TPD_THREADS);
-}
 __global__ void __launch_bounds__(128) k_tp_ad_corner(TpFusedArgs a, Ctx c) {
   // 4 corners x 9 sources per direction: the first wave takes direction 2, the second direction 1 (no source belongs to both: the
   // direction-2 sources lie in the south / north halo rows, the direction-1 sources in the west / east halo columns)
@@ -600,29 +601,18 @@ __global__ void __launch_bounds__(128) k_tp_ad_corner(TpFusedArgs a, Ctx c) {
 FV3LM_LINK void run_tp_ad(Exec& ex, const TpFusedArgs& a0, const Ctx& c) {
   TpFusedArgs a = a0;
   for (Fld* f : {&a.q, &a.crx, &a.cry, &a.xfx, &a.yfx, &a.rax, &a.ray, &a.mx, &a.my, &a.fx, &a.fy}) *f = ex.sh(*f);
-  const int nbx = (c.g.tx + TPD_W - 1) / TPD_W, nby = (c.g.ty + TPD_H - 1) / TPD_H;
+  const Rect Qr = tp_window(c.g);
 #if FV3LM_TPD_EXP
   if (const char* e = std::getenv("FV3LM_TP2_EXPERIMENT")) a.exp = std::atoi(e);
 #endif
   // algorithmic bytes: trajectory q, crx, cry, xfx, yfx, ra_x, ra_y, mx, my and the adjoints fx, fy read; the nine input adjoints read-modify-written
   const double cells = double(c.g.tx) * c.g.ty * c.g.ntile * a.nk;
-  ex.mark_begin("TpAd", ".ad", 8. * cells * (9. + 2. + 18.));
+  run_tiled<TpAdBlk<tiled_nth(TPD_THREADS)>>(ex, "TpAd", ".ad", 8. * cells * (9. + 2. + 18.), Qr, tiled_blocks(Qr.i0, Qr.i1, TPD_W), tiled_blocks(Qr.j0, Qr.j1, TPD_H), a, c);
 #ifdef FV3LM_HOST_EMUL
-  std::vector<double> lds((size_t)TPD_NT);
-  for (int z = 0; z < c.g.ntile * a.nk; ++z)
-    for (int by = 0; by < nby; ++by)
-      for (int bx = 0; bx < nbx; ++bx) tp_ad_block<1>(a, c, z / a.nk, 1 + z % a.nk, bx, by, lds.data(), 0, 1);
   if (c.g.face)
     for (int z = 0; z < c.g.ntile * a.nk; ++z)
       for (int t = 0; t < 36; ++t) { tp_ad_corner_point(a, c, z / a.nk, 1 + z % a.nk, t / 9, t % 9, 2); tp_ad_corner_point(a, c, z / a.nk, 1 + z % a.nk, t / 9, t % 9, 1); }
 #else
-  static bool attr = false;
-  if (!attr) { if (hipFuncSetAttribute((const void*)k_tp_ad, hipFuncAttributeMaxDynamicSharedMemorySize, TPD_NT * 8) != hipSuccess) set_sticky("hipFuncSetAttribute(k_tp_ad) failed"); attr = true; }
-  hipLaunchKernelGGL(k_tp_ad, dim3(nbx, nby, c.g.ntile * a.nk), dim3(TPD_THREADS), TPD_NT * 8, ex.stream, a, c);
-#endif
-  ex.mark_end();
-  ex.launches++;
-#ifndef FV3LM_HOST_EMUL
   if (c.g.face) {
     ex.mark_begin("TpAd", ".ad_corner", 0.);
     hipLaunchKernelGGL(k_tp_ad_corner, dim3(c.g.ntile * a.nk), dim3(128), 0, ex.stream, a, c);

@@ -12,6 +12,7 @@
 // Per output point the staged tangent chain moves 64 doubles, this kernel 22 (9 inputs + 2 outputs, value and tangent).
 #pragma once
 #include "stages.h"
+#include "tiled.h"
 
 namespace fv3 {
 
@@ -35,41 +36,9 @@ FV3LM_LINK void run_tp_fused(Exec& ex, int mode, const TpFusedArgs& a0, const Ct
 FV3LM_LINK void run_tp_outer_ad(Exec& ex, const TpFusedArgs& a0, const Ctx& c);
 // the same routine laid out for the wavefront (tp2.h): takes the nonlinear and tangent launches that store nothing for the staged adjoint
 FV3LM_LINK void run_tp2(Exec& ex, int mode, const TpFusedArgs& a0, const Ctx& c);
-inline bool tp2_enabled() { const char* e = std::getenv("FV3LM_TP2"); return !(e && e[0] == '0'); }      // read per launch: a test switches it between two models
-}  // namespace fv3
-
-#ifdef FV3LM_HOST_EMUL
-#define TPF_SYNC() ((void)0)
-#define TPF_LOOP(e, n) for (int e = tid; e < (n); e += nth)
-#define TPF_LOOPU(e, u, n, E) for (int u = 0, e = 0; e < (n); ++e, ++u)      /* one "thread": slot u of a per-thread array is element e */
-#else
-#define TPF_SYNC() __syncthreads()
-// constant trip count, unrolled: the global loads of a thread's elements of a phase are issued together
-#ifdef FV3LM_TPF_NOUNROLL      /* experiment: real loops, a quarter of the code */
-#define TPF_LOOP(e, n) _Pragma("nounroll") for (int e = tid; e < (n); e += NTH)
-#else
-#define TPF_LOOP(e, n) _Pragma("unroll") for (int e = tid; e < (n); e += NTH)
-#endif
-// the same with the slot index u of a per-thread register array (constant trip count E = ceil(n / NTH): static indices after unrolling)
-#define TPF_LOOPU(e, u, n, E) _Pragma("unroll") for (int u = 0; u < (E); ++u) if (const int e = tid + u * NTH; e < (n))
-#endif
-
-namespace fv3 {
-template <class T> struct TpfIO;
-template <> struct TpfIO<double> {
-  static constexpr int NC = 1;
-  DEV static double ld(const Fld& f, size_t n) { return f.t[n]; }
-  DEV static void st(const Fld& f, size_t n, double x) { f.t[n] = x; }
-  DEV static double lget(const double* v, int, int e) { return v[e]; }
-  DEV static void lset(double* v, int, int e, double x) { v[e] = x; }
-};
-template <> struct TpfIO<Dual> {
-  static constexpr int NC = 2;
-  DEV static Dual ld(const Fld& f, size_t n) { return Dual(f.t[n], f.p ? f.p[n] : 0.0); }
-  DEV static void st(const Fld& f, size_t n, const Dual& x) { f.t[n] = x.v; f.p[n] = x.d; }
-  DEV static Dual lget(const double* v, int nt, int e) { return Dual(v[e], v[nt + e]); }
-  DEV static void lset(double* v, int nt, int e, const Dual& x) { v[e] = x.v; v[nt + e] = x.d; }
-};
+inline bool tp2_enabled() { return switch_on("FV3LM_TP2"); }      // read per launch: a test switches it between two models
+// the rectangle the blocks of the fv_tp_2d launches are laid over: the tile's window of the face
+inline Rect tp_window(const Geom& g) { return Rect{g.is(), g.ie(), g.js(), g.je()}; }
 // algorithmic bytes of one launch: 9 inputs (+ d2b, mass) read and 2 outputs written per cell (x2 in the tangent mode), + the six stored
 // trajectory intermediates of the nonlinear mode
 inline double tpf_bytes(const TpFusedArgs& a, const Geom& g, int mode) {
@@ -107,13 +76,12 @@ struct TpfTile {
   DEV void set(int i, int j, const T& x) const { TpfIO<T>::lset(v, TPF_NT, (j - j0) * w + (i - i0), x); }
 };
 
-// One block: cells I0..I1 x J0..J1 of level k of one tile.  tid / nth: this thread and the number of threads sharing the block
-// (host emulation: 0 / 1).
+// One block: cells I0..I1 x J0..J1 of level k of one tile, blocks laid over the tile's window.
 // TRAJ: the values-only second pass of a level whose trajectory scheme differs from the scheme the tangent / adjoint is taken of
 // (split_hord, sw_core_tlm.F90:1664-1682): the whole chain again with the trajectory scheme (inner sweeps: 8 where it is 10,
 // tp_core_tlm.F90:135-136) and the trajectory damping, fx.t / fy.t overwritten; levels without a split return at once.
 template <class T, bool STORE, int NTH, bool TRAJ = false>
-DEV void tp_fused_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, int by, double* lds, int tid, int nth) {
+DEV void tp_fused_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, int by, double* lds, int tid) {
   typedef TpfIO<T> IO;
   static_assert(!TRAJ || (std::is_same<T, double>::value && !STORE), "the trajectory pass computes values only");
   const bool split = level_split(c.lev[k - 1], a.hsel, a.dsel);
@@ -122,8 +90,8 @@ DEV void tp_fused_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int
   const int nx = g.nx, ny = g.ny;
   const bool face = g.face != 0;
   const int is = g.is(), ie = g.ie(), js = g.js(), je = g.je();      // the tile's window of the face (nx, ny: the FACE, for the edge formulas)
-  const int I0 = is + bx * TPF_W, I1 = (I0 + TPF_W - 1 < ie) ? I0 + TPF_W - 1 : ie;
-  const int J0 = js + by * TPF_H, J1 = (J0 + TPF_H - 1 < je) ? J0 + TPF_H - 1 : je;
+  const TileBlk B = tile_blk(Rect{is, ie, js, je}, bx, by, TPF_W, TPF_H);
+  const int I0 = B.I0, I1 = B.I1, J0 = B.J0, J1 = B.J1;
   const bool firstx = bx == 0, lastx = I1 == ie, firsty = by == 0, lasty = J1 == je;
   const size_t base = (size_t)(tile * a.nk + k - 1) * g.plane;
   auto at = [&](int i, int j) -> size_t { return base + g.idx(i, j); };
@@ -267,49 +235,24 @@ DEV void tp_fused_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int
     } }
 }
 
-inline void tpf_grid(const Geom& g, int& nbx, int& nby) { nbx = (g.tx + TPF_W - 1) / TPF_W; nby = (g.ty + TPF_H - 1) / TPF_H; }
-#ifndef FV3LM_HOST_EMUL
-template <class T, bool STORE, int NTH, bool TRAJ = false>
-__global__ void __launch_bounds__(NTH) k_tp_fused(TpFusedArgs a, Ctx c) {
-  extern __shared__ double tpf_lds[];
-  int bx = blockIdx.x, by = blockIdx.y; xcd_block(gridDim.x, gridDim.y, bx, by);
-  tp_fused_block<T, STORE, NTH, TRAJ>(a, c, blockIdx.z / a.nk, 1 + blockIdx.z % a.nk, bx, by, tpf_lds, threadIdx.x, NTH);
-}
-#endif
+// the block descriptors (tiled.h); the block functions take the launch rectangle, the tile's window, from the geometry
+template <class T, bool STORE, int N, bool TRAJ = false> struct TpFusedBlk {
+  typedef TpFusedArgs Args; static constexpr int NTH = N; static constexpr size_t LDS_BYTES = (size_t)TPF_NT * 8 * TpfIO<T>::NC;
+  DEV static void block(const Args& a, const Ctx& c, const Rect&, int tile, int k, int bx, int by, double* lds, int tid) { tp_fused_block<T, STORE, N, TRAJ>(a, c, tile, k, bx, by, lds, tid); }
+};
 
 FV3LM_LINK void run_tp_fused(Exec& ex, int mode, const TpFusedArgs& a0, const Ctx& c, bool traj) {
   if (!traj && (mode == MODE_TL || !a0.store_mid) && tp2_enabled() && !(mode == MODE_TL && std::getenv("FV3LM_TP2_NL_ONLY"))) { run_tp2(ex, mode, a0, c); return; }
   TpFusedArgs a = a0;
   for (Fld* f : {&a.q, &a.crx, &a.cry, &a.xfx, &a.yfx, &a.rax, &a.ray, &a.mx, &a.my, &a.mass, &a.d2b, &a.d2b_t, &a.fx, &a.fy, &a.fy2, &a.q_i, &a.fxo, &a.fx2, &a.q_j, &a.fyo, &a.acx, &a.acy, &a.amfx, &a.amfy}) *f = ex.sh(*f);
   a.do_acc = (a.acx.t && !ex.skip_accum) ? 1 : 0;
-  int nbx, nby; tpf_grid(c.g, nbx, nby);
-  ex.mark_begin(traj ? "TpFusedTraj" : "TpFused", traj ? ".nl" : mode == MODE_TL ? ".tl" : ".nl", traj ? 0. : tpf_bytes(a, c.g, mode));
-#ifdef FV3LM_HOST_EMUL
-  std::vector<double> lds((size_t)TPF_NT * 2);
-  for (int z = 0; z < c.g.ntile * a.nk; ++z)
-    for (int by = 0; by < nby; ++by)
-      for (int bx = 0; bx < nbx; ++bx) {
-        if (traj) tp_fused_block<double, false, 1, true>(a, c, z / a.nk, 1 + z % a.nk, bx, by, lds.data(), 0, 1);
-        else if (mode == MODE_TL) tp_fused_block<Dual, false, 1>(a, c, z / a.nk, 1 + z % a.nk, bx, by, lds.data(), 0, 1);
-        else if (a.store_mid) tp_fused_block<double, true, 1>(a, c, z / a.nk, 1 + z % a.nk, bx, by, lds.data(), 0, 1);
-        else tp_fused_block<double, false, 1>(a, c, z / a.nk, 1 + z % a.nk, bx, by, lds.data(), 0, 1);
-      }
-#else
-  const dim3 grid(nbx, nby, c.g.ntile * a.nk);
-  if (traj) {
-    hipLaunchKernelGGL((k_tp_fused<double, false, TPF_THREADS_NL, true>), grid, dim3(TPF_THREADS_NL), TPF_NT * 8, ex.stream, a, c);
-  } else if (mode == MODE_TL) {
-    static bool attr = false;      // 2 x 53.5 KB of LDS per block: above the 64 KB default limit of a launch
-    if (!attr) { if (hipFuncSetAttribute((const void*)k_tp_fused<Dual, false, TPF_THREADS_TL>, hipFuncAttributeMaxDynamicSharedMemorySize, TPF_NT * 16) != hipSuccess) set_sticky("hipFuncSetAttribute(k_tp_fused) failed"); attr = true; }
-    hipLaunchKernelGGL((k_tp_fused<Dual, false, TPF_THREADS_TL>), grid, dim3(TPF_THREADS_TL), TPF_NT * 16, ex.stream, a, c);
-  } else if (a.store_mid) {
-    hipLaunchKernelGGL((k_tp_fused<double, true, TPF_THREADS_NL>), grid, dim3(TPF_THREADS_NL), TPF_NT * 8, ex.stream, a, c);
-  } else {
-    hipLaunchKernelGGL((k_tp_fused<double, false, TPF_THREADS_NL>), grid, dim3(TPF_THREADS_NL), TPF_NT * 8, ex.stream, a, c);
-  }
-#endif
-  ex.mark_end();
-  ex.launches++;
+  const Rect Qr = tp_window(c.g);
+  const int nbx = tiled_blocks(Qr.i0, Qr.i1, TPF_W), nby = tiled_blocks(Qr.j0, Qr.j1, TPF_H);
+  constexpr int NL = tiled_nth(TPF_THREADS_NL), TL = tiled_nth(TPF_THREADS_TL);
+  if (traj) run_tiled<TpFusedBlk<double, false, NL, true>>(ex, "TpFusedTraj", ".nl", 0., Qr, nbx, nby, a, c);
+  else if (mode == MODE_TL) run_tiled<TpFusedBlk<Dual, false, TL>>(ex, "TpFused", ".tl", tpf_bytes(a, c.g, mode), Qr, nbx, nby, a, c);
+  else if (a.store_mid) run_tiled<TpFusedBlk<double, true, NL>>(ex, "TpFused", ".nl", tpf_bytes(a, c.g, mode), Qr, nbx, nby, a, c);
+  else run_tiled<TpFusedBlk<double, false, NL>>(ex, "TpFused", ".nl", tpf_bytes(a, c.g, mode), Qr, nbx, nby, a, c);
 }
 
 // =====================================================================================================================
@@ -329,14 +272,13 @@ constexpr int TPA_NT = 3 * TPA_NA + 3 * TPA_NC;                     // fxo_ad, c
 constexpr int TPA_THREADS = 512;
 
 template <int NTH>
-DEV void tp_outer_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, int by, double* lds, int tid, int nth) {
-  (void)nth;
+DEV void tp_outer_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, int by, double* lds, int tid) {
   const Geom& g = c.g;
   const int nx = g.nx, ny = g.ny;
   const bool face = g.face != 0;
   const int is = g.is(), ie = g.ie(), js = g.js(), je = g.je();      // the tile's window of the face (nx, ny: the FACE, for the edge formulas)
-  const int I0 = is + bx * TPF_W, I1 = (I0 + TPF_W - 1 < ie) ? I0 + TPF_W - 1 : ie;
-  const int J0 = js + by * TPF_H, J1 = (J0 + TPF_H - 1 < je) ? J0 + TPF_H - 1 : je;
+  const TileBlk B = tile_blk(Rect{is, ie, js, je}, bx, by, TPF_W, TPF_H);
+  const int I0 = B.I0, I1 = B.I1, J0 = B.J0, J1 = B.J1;
   const bool firstx = bx == 0, lastx = I1 == ie, firsty = by == 0, lasty = J1 == je;
   const size_t base = (size_t)(tile * a.nk + k - 1) * g.plane;
   auto at = [&](int i, int j) -> size_t { return base + g.idx(i, j); };
@@ -441,32 +383,19 @@ DEV void tp_outer_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, 
     } }
 }
 
-#ifndef FV3LM_HOST_EMUL
-__global__ void __launch_bounds__(TPA_THREADS) k_tp_outer_ad(TpFusedArgs a, Ctx c) {
-  extern __shared__ double tpa_lds[];
-  int bx = blockIdx.x, by = blockIdx.y; xcd_block(gridDim.x, gridDim.y, bx, by);
-  tp_outer_ad_block<TPA_THREADS>(a, c, blockIdx.z / a.nk, 1 + blockIdx.z % a.nk, bx, by, tpa_lds, threadIdx.x, TPA_THREADS);
-}
-#endif
+template <int N> struct TpOuterAdBlk {
+  typedef TpFusedArgs Args; static constexpr int NTH = N; static constexpr size_t LDS_BYTES = (size_t)TPA_NT * 8;
+  DEV static void block(const Args& a, const Ctx& c, const Rect&, int tile, int k, int bx, int by, double* lds, int tid) { tp_outer_ad_block<N>(a, c, tile, k, bx, by, lds, tid); }
+};
 
 FV3LM_LINK void run_tp_outer_ad(Exec& ex, const TpFusedArgs& a0, const Ctx& c) {
   TpFusedArgs a = a0;
   for (Fld* f : {&a.q, &a.crx, &a.cry, &a.xfx, &a.yfx, &a.rax, &a.ray, &a.mx, &a.my, &a.mass, &a.d2b, &a.fx, &a.fy, &a.fy2, &a.q_i, &a.fxo, &a.fx2, &a.q_j, &a.fyo}) *f = ex.sh(*f);
-  int nbx, nby; tpf_grid(c.g, nbx, nby);
+  const Rect Qr = tp_window(c.g);
   // algorithmic bytes: trajectory q_i, q_j, crx, cry, mx, my, fx2, fy2 and the adjoints fx, fy read; q_i, q_j, fx2, fy2 adjoints written;
   // crx, cry, mx, my adjoints read-modify-written
   const double cells = double(c.g.tx) * c.g.ty * c.g.ntile * a.nk;
-  ex.mark_begin("TpOuter", ".ad", 8. * cells * (8. + 2. + 4. + 8.));
-#ifdef FV3LM_HOST_EMUL
-  std::vector<double> lds((size_t)TPA_NT);
-  for (int z = 0; z < c.g.ntile * a.nk; ++z)
-    for (int by = 0; by < nby; ++by)
-      for (int bx = 0; bx < nbx; ++bx) tp_outer_ad_block<1>(a, c, z / a.nk, 1 + z % a.nk, bx, by, lds.data(), 0, 1);
-#else
-  hipLaunchKernelGGL(k_tp_outer_ad, dim3(nbx, nby, c.g.ntile * a.nk), dim3(TPA_THREADS), TPA_NT * 8, ex.stream, a, c);
-#endif
-  ex.mark_end();
-  ex.launches++;
+  run_tiled<TpOuterAdBlk<tiled_nth(TPA_THREADS)>>(ex, "TpOuter", ".ad", 8. * cells * (8. + 2. + 4. + 8.), Qr, tiled_blocks(Qr.i0, Qr.i1, TPF_W), tiled_blocks(Qr.j0, Qr.j1, TPF_H), a, c);
 }
 
 }  // namespace fv3

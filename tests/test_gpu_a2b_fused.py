@@ -8,26 +8,26 @@ pytestmark = pytest.mark.gpu
 
 def test_fused_a2b_equals_staged_periodic():
     from common import Case
-    from a2b_fused_checks import check_fused_equals_staged
-    check_fused_equals_staged(lambda: Case(nx=70, ny=20, npz=3, n_split=2, k_split=1, dt=900.0, backend="hip", oracle=False, nq=1), rtol=1e-12)
+    from fused_checks import check_fused_equals_staged
+    check_fused_equals_staged("hip/periodic", lambda: Case(nx=70, ny=20, npz=3, n_split=2, k_split=1, dt=900.0, backend="hip", oracle=False, nq=1), "FV3LM_A2B_FUSED", rtol=1e-12)
 
 
 def test_fused_a2b_equals_staged_cube():
     from common import CubeCase
-    from a2b_fused_checks import check_fused_equals_staged
-    check_fused_equals_staged(lambda: CubeCase(n=66, npz=2, n_split=1, k_split=1, dt=225.0, backend="hip", nq=1), rtol=1e-12)
+    from fused_checks import check_fused_equals_staged
+    check_fused_equals_staged("hip/cube", lambda: CubeCase(n=66, npz=2, n_split=1, k_split=1, dt=225.0, backend="hip", nq=1), "FV3LM_A2B_FUSED", rtol=1e-12)
 
 
 def test_fused_a2b_equals_staged_nonhydrostatic():
     from common import Case
-    from a2b_fused_checks import check_fused_equals_staged
-    check_fused_equals_staged(lambda: Case(nx=66, ny=18, npz=3, n_split=1, k_split=1, dt=300.0, backend="hip", oracle=False, hydrostatic=0), rtol=1e-12)
+    from fused_checks import check_fused_equals_staged
+    check_fused_equals_staged("hip/nh", lambda: Case(nx=66, ny=18, npz=3, n_split=1, k_split=1, dt=300.0, backend="hip", oracle=False, hydrostatic=0), "FV3LM_A2B_FUSED", rtol=1e-12)
 
 
 def test_fused_a2b_equals_staged_subface_windows():
     from common import CubeCase
-    from a2b_fused_checks import check_fused_equals_staged
-    check_fused_equals_staged(lambda: CubeCase(n=136, npz=2, n_split=1, k_split=1, dt=100.0, backend="hip", nq=1, layout=2), rtol=1e-12)
+    from fused_checks import check_fused_equals_staged
+    check_fused_equals_staged("hip/windows", lambda: CubeCase(n=136, npz=2, n_split=1, k_split=1, dt=100.0, backend="hip", nq=1, layout=2), "FV3LM_A2B_FUSED", rtol=1e-12)
 
 
 def test_fused_a2b_cube_step_dot_product():

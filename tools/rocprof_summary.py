@@ -13,6 +13,11 @@ import sqlite3
 import sys
 
 
+# block descriptor of a k_tiled<...> kernel -> profile name (csrc/a2b.h, d2a2c.h, tpfused.h, tp2.h, tpad.h)
+TILED = {"TpFusedBlk": "TpFused", "Tp2Blk": "TpFused", "TpAdBlk": "TpAd", "TpOuterAdBlk": "TpOuter",
+         "A2bFwd": "A2b", "A2bAd": "A2b", "D2a2cFwd": "D2a2c", "D2a2cAd": "D2a2c"}
+
+
 def short(name):
     m = re.search(r"k_stage_(nl|tl|ad_alias|ad)<fv3::([A-Za-z0-9_]+(?:<[a-z]+>)?)", name)
     if m:
@@ -27,8 +32,13 @@ def short(name):
     m = re.search(r"k_stage_ad_lds<fv3::(?:Edged<fv3::)?([A-Za-z0-9_]+?)D?(?:_?<|,)", name)
     if m:
         return "%s.ad(lds)" % m.group(1).rstrip("_")
+    m = re.search(r"k_tiled<fv3::([A-Za-z0-9]+)<(fv3::Dual|double)?", name)
+    if m:       # the hand-written LDS-tiled launches (tiled.h), named by their block descriptor; Dual = tangent, double = nonlinear, none = adjoint
+        mode = "ad" if m.group(2) is None else "tl" if "Dual" in m.group(2) else "nl"
+        return "%s.%s" % (TILED[m.group(1)], mode)
+    # kernel symbols of builds before tiled.h (the committed profiles): one kernel per launch
     m = re.search(r"k_tp_(fused|march)<(fv3::Dual|double)", name)
-    if m:       # fv_tp_2d as one launch (tpfused.h): tiled or marching form; Dual = tangent, double = nonlinear (stores the intermediates)
+    if m:       # fv_tp_2d as one launch (tpfused.h), tiled form (the marching form, k_tp_march, was removed: old profiles only); Dual = tangent, double = nonlinear
         return "%s.%s" % ("TpFused" if m.group(1) == "fused" else "TpMarch", "tl" if "Dual" in m.group(2) else "nl")
     m = re.search(r"k_tp2<(fv3::Dual|double)", name)
     if m:       # fv_tp_2d as one launch, wavefront layout (tp2.h): the same profile name as the first form
