@@ -20,6 +20,7 @@ module fv3lm_hip_mod
   public :: fv3lm_hip_traj_to_fv3, fv3lm_hip_pert_to_fv3, fv3lm_hip_fv3_to_pert
   public :: fv3lm_hip_set_tracer_damping, fv3lm_hip_tracer_damping
   public :: fv3lm_hip_set_external_damping, fv3lm_hip_external_damping
+  public :: fv3lm_hip_set_trajectory_damping_order, fv3lm_hip_trajectory_damping_order
   public :: fv3lm_hip_set_rayleigh, fv3lm_hip_rayleigh_profile
   public :: fv3lm_hip_turbulence_create, fv3lm_hip_turbulence_set_diagonals, fv3lm_hip_turbulence_set_simple
   public :: fv3lm_hip_turbulence, fv3lm_hip_turbulence_get
@@ -136,6 +137,18 @@ module fv3lm_hip_mod
       import :: c_ptr, c_int, c_double
       type(c_ptr), value :: h
       real(c_double), intent(out) :: d_ext
+      integer(c_int) :: rc
+    end function
+    function c_set_trajectory_damping_order(h, nord) bind(C, name="fv3lm_set_trajectory_damping_order") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), value :: nord
+      integer(c_int) :: rc
+    end function
+    function c_trajectory_damping_order(h, nord) bind(C, name="fv3lm_trajectory_damping_order") result(rc)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: h
+      integer(c_int), intent(out) :: nord
       integer(c_int) :: rc
     end function
     function c_set_exchange(h, kind, rows, nrows) bind(C, name="fv3lm_set_exchange") result(rc)
@@ -442,6 +455,22 @@ contains
     real(c_double), intent(out) :: d_ext
     call check(c_external_damping(self%handle, d_ext), 'external_damping')
   end subroutine fv3lm_hip_external_damping
+
+  !> The trajectory's divergence-damping order FV_Atm(1)%flagstruct%nord after create (include/fv3lm.h).  A non-hydrostatic host creates
+  !! with nord = min(flagstruct%nord, nord_pert) and passes flagstruct%nord here: orders 2 and 3 are reached only this way.
+  !! Call after fv3lm_hip_create, before the first step or between complete steps.
+  subroutine fv3lm_hip_set_trajectory_damping_order(self, nord)
+    type(fv3lm_hip_type), intent(inout) :: self
+    integer(c_int), intent(in) :: nord
+    call check(c_set_trajectory_damping_order(self%handle, nord), 'set_trajectory_damping_order')
+  end subroutine fv3lm_hip_set_trajectory_damping_order
+
+  !> nord as in force
+  subroutine fv3lm_hip_trajectory_damping_order(self, nord)
+    type(fv3lm_hip_type), intent(inout) :: self
+    integer(c_int), intent(out) :: nord
+    call check(c_trajectory_damping_order(self%handle, nord), 'trajectory_damping_order')
+  end subroutine fv3lm_hip_trajectory_damping_order
 
   !> One halo-exchange table (kind 0..4, include/fv3lm.h): rows(7, n) for the faces resident on this GPU, and the
   !! per-peer send/receive lists for faces held by other ranks (replaces mpp_update_domains / mpp_get_boundary).

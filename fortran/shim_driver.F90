@@ -22,7 +22,7 @@ program shim_driver
   real(c_double), allocatable :: u(:, :, :), v(:, :, :), pt(:, :, :), delp(:, :, :), q(:, :, :, :)
   real(c_double), allocatable :: up(:, :, :), vp(:, :, :), ptp(:, :, :), delpp(:, :, :), qp(:, :, :, :)
   character(len=8) :: qn
-  integer(c_int) :: nord2(2)
+  integer(c_int) :: nord2(2), nord_now
   real(c_double) :: trdm2(2), d_ext
 
   call get_command_argument(1, fin); call get_command_argument(2, fout)
@@ -52,6 +52,10 @@ program shim_driver
   call fv3lm_hip_set_external_damping(dyn, 0.0_c_double)
   call fv3lm_hip_external_damping(dyn, d_ext)
   if (d_ext /= 0.0_c_double) error stop 'fv3lm_hip_external_damping'
+  ! the trajectory's damping order, likewise: the order the handle was created with, so nothing is rebuilt
+  call fv3lm_hip_set_trajectory_damping_order(dyn, opt%nord)
+  call fv3lm_hip_trajectory_damping_order(dyn, nord_now)
+  if (nord_now /= opt%nord) error stop 'fv3lm_hip_trajectory_damping_order'
   open(12, file=trim(fout), access='stream', form='unformatted', status='replace')
   ! ---- step_tl: trajectory and perturbation in, both advanced
   call put_all(0, u, v, pt, delp, q); call put_all(1, up, vp, ptp, delpp, qp)

@@ -279,6 +279,20 @@ class Dycore:
         self._chk(self.lib.L.fv3lm_external_damping(self.h, C.byref(d)))
         return d.value
 
+    # ---- the trajectory's divergence-damping order after create (flagstruct%nord) ----
+    def set_trajectory_damping_order(self, nord):
+        """fv3lm_set_trajectory_damping_order: after create, before a step or between complete steps.  Resolves every level again and,
+        when the order changed, rebuilds the acoustic program.  A non-hydrostatic handle reaches nord 2 and 3 only this way."""
+        self.lib.L.fv3lm_set_trajectory_damping_order.argtypes = [C.c_void_p, C.c_int]
+        self._chk(self.lib.L.fv3lm_set_trajectory_damping_order(self.h, int(nord)))
+
+    def trajectory_damping_order(self):
+        """-> the trajectory's nord as in force"""
+        n = C.c_int(-1)
+        self.lib.L.fv3lm_trajectory_damping_order.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        self._chk(self.lib.L.fv3lm_trajectory_damping_order(self.h, C.byref(n)))
+        return n.value
+
     # ---- linearised boundary-layer turbulence (fv3jedi_lm_turbulence_mod.F90; csrc/turbulence.h), compact arrays [ntile, npz, ny, nx] ----
     def _compact(self, a, nk=None):
         a = np.ascontiguousarray(a, dtype=np.float64)

@@ -21,6 +21,7 @@
 #include "dext.h"
 #include "a2b.h"
 #include "d2a2c.h"
+#include "del6.h"
 #include <functional>
 #include <map>
 #include <memory>
@@ -784,6 +785,22 @@ struct Dycore {
   // launches only while it is > 0; the non-hydrostatic step (beta = 0: nh_p_grad) never reads divg2
   double d_ext = 0.;
   bool dext_on() const { return !nh && d_ext > 0.; }
+  // The order-2 del-6 chain as one LDS-tiled launch (del6.h), behind its switch: FV3LM_DEL6_FUSED=1 where the programs are built turns it
+  // on; unset or 0 keeps the staged chain in every mode -- the default, because on the 48 x 48 x 72 tile, the one size measured, the tiled
+  // form did not make the step faster.  The launch takes the nonlinear and tangent modes on every tile and the
+  // adjoint on tiles without a cube corner (the periodic tile, sub-face tiles away from the corners): its adjoint is the transpose
+  // without the corner views, which the staged adjoint carries on the others
+  unsigned del6_tiled_modes() const {
+    const char* env = std::getenv("FV3LM_DEL6_FUSED");
+    if (!(env && env[0] == '1')) return 0u;
+    const bool corner = g.face && (g.is() == 1 || g.ie() == g.nx) && (g.js() == 1 || g.je() == g.ny);
+    return corner ? ((1u << MODE_NL) | (1u << MODE_TL)) : 7u;
+  }
+  void add_del6(Program& P, const char* grp, Fld q, Fld out, int nk, int sel, unsigned modes) {
+    Del6Args fa; fa.q = q; fa.out = out; fa.ro = R(g.is(), g.ie(), g.js(), g.je()); fa.nk = nk; fa.sel = sel;
+    TiledAd ad; ad.in = {q.p}; ad.in_slot = {0}; ad.out = {out.p}; ad.out_rect = {fa.ro};
+    add_tiled(P, grp, "Del6", std::make_shared<Del6Args>(fa), run_del6, modes, ad);
+  }
   void build_acoustic();
   void plan_acoustic(bool rebuild);
   void rebuild_acoustic();
@@ -891,6 +908,8 @@ inline bool Dycore::init(int nx, int ny, int npz, int ntile, int face, int nq_, 
     }
   } else {
     if (o.nord == 0 && o.nord_pert > 0) { err = "split_damp: nord = 0 with nord_pert > 0 -- c_sw computes divg_d only for the trajectory's nord > 0 (sw_core_tlm.F90: IF (nord .GT. 0) divergence_corner), the perturbation's damping would read an undefined array"; return false; }
+    // kept word for word (a pinned test).  "not built" holds for create alone: the operator is built (stages.h Del6B, del6.h) and a
+    // non-hydrostatic handle reaches nord 2, 3 through Dynamics::set_trajectory_damping_order after create
     if (nh && o.nord > 1) { err = "non-hydrostatic with a trajectory nord > 1: the w / height damping would need the tangent of del6_vt_flux with nord 2 (sw_core_tlm.F90:1713-1726), not built"; return false; }
   }
   if (nh && npz < 3) { err = "non-hydrostatic solver needs npz >= 3"; return false; }
@@ -1013,7 +1032,7 @@ inline void Dycore::plan_acoustic(bool rebuild) {
 }
 // Between complete steps only (nothing of a step in flight lives in the work arena): the program again, for the options as they are now, in
 // a work arena of its new size; the trajectory slots, which are copies of that arena, are planned anew from the memory then free.
-// The caller re-points what it keeps inside the arena (Dynamics::set_external_damping).
+// The caller re-points what it keeps inside the arena (Dynamics::rebuild_acoustic_repoint).
 inline void Dycore::rebuild_acoustic() {
   dev_sync(ex);
   for (double* q_ : traj_slot) dev_free(q_);
@@ -1324,8 +1343,21 @@ inline void Dycore::build_acoustic() {
   Fld w_m{}, dw{}, gxw{}, gyw{};
   if (nh) {   // w: damping increment and transport with the mass fluxes (sw_core_tlm.F90:3020-3062)
     Fld d6w = W("del6_w", npz); dw = W("dw", npz); gxw = W("gxw", npz); gyw = W("gyw", npz); w_m = W("w_m", npz);
-    { Del6AD s; s.in[0] = w; s.out[0] = d6w; s.orect[0] = R(is - 1, ie + 1, js - 1, je + 1); s.k1 = npz; add_face(P, "d_sw", s, 1); }
-    { DswDw s; s.in[0] = w; s.in[1] = d6w; s.out[0] = dw; s.orect[0] = R(is, ie, js, je); s.k1 = npz; add(P, "d_sw", s); }
+    bool n2 = false;       // some level damps w with nord_w = 2 (a trajectory nord of 2 or 3): the first Laplacian on a ring one wider, and a second one
+    for (int k = 0; k < npz; ++k) n2 = n2 || Del6BD::on(lev_host[k], 0);
+    const int r1 = n2 ? 2 : 1;
+    const size_t n_d6 = P.size();
+    { Del6AD s; s.in[0] = w; s.out[0] = d6w; s.orect[0] = R(is - r1, ie + r1, js - r1, je + r1); s.k1 = npz; add_face(P, "d_sw", s, 1); }
+    if (!n2) { DswDw s; s.in[0] = w; s.in[1] = d6w; s.out[0] = dw; s.orect[0] = R(is, ie, js, je); s.k1 = npz; add(P, "d_sw", s); }
+    else {
+      Fld d6bw = W("del6b_w", npz);
+      { Del6BD s; s.in[0] = d6w; s.out[0] = d6bw; s.orect[0] = R(is - 1, ie + 1, js - 1, je + 1); s.k1 = npz; s.sel = 0; add_face(P, "d_sw", s, 1); }
+      DswDwT<true> s; s.in[0] = w; s.in[1] = d6w; s.in[2] = d6bw; s.out[0] = dw; s.orect[0] = R(is, ie, js, je); s.k1 = npz; add(P, "d_sw", s);
+      // the chain as one LDS-tiled launch (del6.h): the three staged ops above then serve the modes it does not take
+      const unsigned mt = del6_tiled_modes();
+      for (size_t n = n_d6; n < P.size(); ++n) P[n].modes = 7u & ~mt;
+      if (mt) add_del6(P, "d_sw", w, dw, npz, 0, mt);
+    }
     build_tp(P, "d_sw", "tpw", w, crx, cry, xfx, yfx, rax, ray, fx, fy, Fld{}, HORD_VT, DAMP_NONE, false, gxw, gyw);
   }
   build_tp(P, "d_sw", "tpt", pt, crx, cry, xfx, yfx, rax, ray, fx, fy, delp, HORD_TM, DAMP_T, true, gx, gy);
@@ -1397,7 +1429,7 @@ inline void Dycore::build_acoustic() {
   { Del6AD s; s.in[0] = wk; s.out[0] = d6; s.orect[0] = R(is - 1, ie + 1, js - 1, je + 1); s.k1 = npz; add_face(P, "d_sw", s, 1); }
   Fld u_m = W("u_m", npz), v_m = W("v_m", npz);
   { bool n2 = false;       // the trajectory's vorticity damping with nord_v = 2 (split_damp, nord >= 2): two more Laplacians, values only
-    for (int k = 0; k < npz; ++k) n2 = n2 || (lev_host[k].nord_v == 2 && lev_host[k].damp_vt > 1.e-5);
+    for (int k = 0; k < npz; ++k) n2 = n2 || Del6BD::on(lev_host[k], 1);
     auto uv_stage = [&](auto s) { s.in[0] = u; s.in[1] = v; s.in[2] = ke2; s.in[3] = fxv; s.in[4] = fyv; s.in[5] = wk; s.in[6] = d6; s.out[0] = u_m; s.out[1] = v_m;
       s.orect[0] = R(is, ie, js, je + 1); s.orect[1] = R(is, ie + 1, js, je); s.k1 = npz; return s; };
     if (!n2) add(P, "d_sw", uv_stage(DswUpdateUV{}));
@@ -1428,9 +1460,27 @@ inline void Dycore::build_acoustic() {
       s.k1 = npz + 1; add(P, "update_dz_d", s); }
     Fld fxz = W("fxz", npz + 1), fyz = W("fyz", npz + 1), d6z = W("del6_z", npz + 1), zh_a = W("zh_a", npz + 1);
     build_tp(P, "update_dz_d", "tpz", zh, crx_e, cry_e, xfx_e, yfx_e, rax_e, ray_e, xfx_e, yfx_e, Fld{}, HORD_TM_G, DAMP_NONE, false, fxz, fyz, npz + 1);   // the global hord_tm for every interface (dyn_core_tlm.F90:1091, nh_utils_tlm.F90:496-514)
-    { Del6AD s; s.in[0] = zh; s.out[0] = d6z; s.orect[0] = R(is - 1, ie + 1, js - 1, je + 1); s.k1 = npz + 1; add_face(P, "update_dz_d", s, 1); }
-    { UpdateDzD s; s.in[0] = zh; s.in[1] = d6z; s.in[2] = fxz; s.in[3] = fyz; s.in[4] = rax_e; s.in[5] = ray_e; s.out[0] = zh_a;
-      s.orect[0] = R(is, ie, js, je); s.k1 = npz + 1; add(P, "update_dz_d", s); }
+    bool n2z = false;      // some interface damps the heights with nord_v = 2: as for w in d_sw
+    for (int k = 0; k <= npz; ++k) n2z = n2z || Del6BD::on(lev_host[k], 1);
+    const int r1 = n2z ? 2 : 1;
+    const size_t n_d6z = P.size();
+    { Del6AD s; s.in[0] = zh; s.out[0] = d6z; s.orect[0] = R(is - r1, ie + r1, js - r1, je + r1); s.k1 = npz + 1; add_face(P, "update_dz_d", s, 1); }
+    auto dz_stage = [&](auto s) { s.in[0] = zh; s.in[1] = d6z; s.in[2] = fxz; s.in[3] = fyz; s.in[4] = rax_e; s.in[5] = ray_e; s.out[0] = zh_a;
+      s.orect[0] = R(is, ie, js, je); s.k1 = npz + 1; return s; };
+    if (!n2z) add(P, "update_dz_d", dz_stage(UpdateDzD{}));
+    else {
+      Fld d6bz = W("del6b_z", npz + 1);
+      { Del6BD s; s.in[0] = d6z; s.out[0] = d6bz; s.orect[0] = R(is - 1, ie + 1, js - 1, je + 1); s.k1 = npz + 1; s.sel = 1; add_face(P, "update_dz_d", s, 1); }
+      auto s2 = dz_stage(UpdateDzDT<true>{}); s2.in[6] = d6bz; add(P, "update_dz_d", s2);
+      // as for w in d_sw: the tiled launch writes the damping term, UpdateDzDF adds it
+      const unsigned mt = del6_tiled_modes();
+      for (size_t n = n_d6z; n < P.size(); ++n) P[n].modes = 7u & ~mt;
+      if (mt) {
+        Fld dz6 = W("del6_dz", npz + 1);
+        add_del6(P, "update_dz_d", zh, dz6, npz + 1, 1, mt);
+        auto s3 = dz_stage(UpdateDzDF{}); s3.in[1] = dz6; add(P, "update_dz_d", s3); P.back().modes = mt;
+      }
+    }
     // ---- riem_solver3 + halo rings of the pressures + nh_p_grad (dyn_core_tlm.F90:2165-2400)
     Fld ppe = W("ppe", npz + 1), pk3 = W("pk3", npz + 1);
     { NhColArgs a = nh_args(dt); a.f[0] = zh_a; a.f[1] = w_m; a.f[2] = pt_o; a.f[3] = delp_o; a.f[4] = w_o; a.f[5] = delz_o; a.f[6] = zh_o; a.f[7] = ppe;

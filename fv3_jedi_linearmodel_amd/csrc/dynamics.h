@@ -154,6 +154,12 @@ struct Dynamics : Dycore {
   // External-mode divergence damping (dext.h; fv3lm_set_external_damping): the acoustic program and the trajectory-slot plan are rebuilt
   // when the damping goes on or off
   bool set_external_damping(double d_ext);
+  // The trajectory's divergence-damping order after create (fv3lm_set_trajectory_damping_order): levels resolved again, the acoustic
+  // program rebuilt when the order changed
+  bool set_trajectory_damping_order(int nord);
+  void add_pt_in();
+  void build_pt_in_rf(int kmax);
+  void rebuild_acoustic_repoint();
   RfArgs rf_args();
   void rayleigh(int mode);
   // one field between the host's compact array and the device state.  which: 0 trajectory, 1 perturbation / adjoint
@@ -264,16 +270,8 @@ inline bool Dynamics::init2(const double* ak, const double* bk) {
     set_class(c); reuse_fields = c > 0;
     build_tracer();
     for (auto& zr : tracer_zero) { auto it = tzero.find(zr.first); if (it == tzero.end() || it->second < zr.second) tzero[zr.first] = zr.second; }
-    const Rect A = R(g.is(), g.ie(), g.js(), g.je());
-    if (nh) {
-      DynPtInNh s; s.in[0] = f("pt"); s.in[1] = nq > 0 ? q[0] : Fld{}; if (!s.in[1].t) s.in[1].nk = npz; s.in[2] = f("delp"); s.in[3] = f("delz");
-      s.out[0] = f("pt_o"); s.out[1] = f("pkz"); s.orect[0] = s.orect[1] = A; s.k1 = npz; s.zvir = opt.zvir; s.akap = opt.akap;
-      s.rdg = -opt.rdgas / opt.grav; s.has_q = nq > 0; add(pt_in, "pt_in", s);
-      build_remap_nh();
-    } else {
-      DynPtIn s; s.in[0] = f("pt"); s.in[1] = nq > 0 ? q[0] : Fld{}; if (!s.in[1].t) s.in[1].nk = npz; s.in[2] = f("pkz"); s.out[0] = f("pt_o");
-      s.orect[0] = A; s.k1 = npz; s.zvir = opt.zvir; s.has_q = nq > 0; add(pt_in, "pt_in", s);
-    }
+    add_pt_in();
+    if (nh) build_remap_nh();
   }
   reuse_fields = false; set_class(-1);
   tracer_zero.assign(tzero.begin(), tzero.end());
@@ -448,18 +446,72 @@ inline bool Dynamics::set_external_damping(double d) {
   const bool was = dext_on();
   d_ext = d;
   if (dext_on() == was) return true;
-  rebuild_acoustic();
-  pt_in.c.assign(classes.size(), Program{});
+  rebuild_acoustic_repoint();
+  return true;
+}
+
+// pt_in of the class being built: T -> the acoustic step's pt_o (non-hydrostatic: and pkz from the equation of state)
+inline void Dynamics::add_pt_in() {
+  const int npz = g.npz;
+  const Rect A = R(g.is(), g.ie(), g.js(), g.je());
+  if (nh) {
+    DynPtInNh s; s.in[0] = f("pt"); s.in[1] = nq > 0 ? q[0] : Fld{}; if (!s.in[1].t) s.in[1].nk = npz; s.in[2] = f("delp"); s.in[3] = f("delz");
+    s.out[0] = f("pt_o"); s.out[1] = f("pkz"); s.orect[0] = s.orect[1] = A; s.k1 = npz; s.zvir = opt.zvir; s.akap = opt.akap;
+    s.rdg = -opt.rdgas / opt.grav; s.has_q = nq > 0; add(pt_in, "pt_in", s);
+  } else {
+    DynPtIn s; s.in[0] = f("pt"); s.in[1] = nq > 0 ? q[0] : Fld{}; if (!s.in[1].t) s.in[1].nk = npz; s.in[2] = f("pkz"); s.out[0] = f("pt_o");
+    s.orect[0] = A; s.k1 = npz; s.zvir = opt.zvir; s.has_q = nq > 0; add(pt_in, "pt_in", s);
+  }
+}
+// non-hydrostatic pt_in with the Rayleigh damping on (levels 1..kmax read the heated temperature)
+inline void Dynamics::build_pt_in_rf(int kmax) {
+  const int npz = g.npz;
+  pt_in_rf.c.assign(classes.size(), Program{}); pt_in_rf.cur = &cur_cls;
   for (int c = 0; c < (int)classes.size(); ++c) {
     set_class(c);
-    DynPtIn s; s.in[0] = f("pt"); s.in[1] = nq > 0 ? q[0] : Fld{}; if (!s.in[1].t) s.in[1].nk = g.npz; s.in[2] = f("pkz"); s.out[0] = f("pt_o");
-    s.orect[0] = R(g.is(), g.ie(), g.js(), g.je()); s.k1 = g.npz; s.zvir = opt.zvir; s.has_q = nq > 0; add(pt_in, "pt_in", s);
+    DynPtInNhRf s; s.in[0] = f("pt"); s.in[1] = nq > 0 ? q[0] : Fld{}; if (!s.in[1].t) s.in[1].nk = npz; s.in[2] = f("delp"); s.in[3] = f("delz");
+    s.in[4] = rf_pth; s.out[0] = f("pt_o"); s.out[1] = f("pkz"); s.orect[0] = s.orect[1] = R(g.is(), g.ie(), g.js(), g.je()); s.k1 = npz;
+    s.zvir = opt.zvir; s.akap = opt.akap; s.rdg = -opt.rdgas / opt.grav; s.has_q = nq > 0; s.kmax = kmax; add(pt_in_rf, "pt_in", s);
   }
   set_class(-1);
+}
+// The acoustic program again for the options as they are now (Dycore::rebuild_acoustic), and what lives in the work arena it moves:
+// pt_o as the output of pt_in (and of the Rayleigh form of a non-hydrostatic handle), the remap's column workspace in its perturbation side.
+inline void Dynamics::rebuild_acoustic_repoint() {
+  rebuild_acoustic();
+  pt_in.c.assign(classes.size(), Program{});
+  for (int c = 0; c < (int)classes.size(); ++c) { set_class(c); add_pt_in(); }
+  set_class(-1);
+  if (nh && rf_kmax > 0) build_pt_in_rf(rf_kmax);
   if (!remap_ws_own) {
     const size_t need = (size_t)remap_ws_slots(nq) * (g.npz + 2) * ntile_all * g.plane;
     remap_ws_own = need > work.cap;
     remap_ws = remap_ws_own ? (double*)dev_alloc(need * 8) : work.p;
+  }
+}
+
+// fv3lm_set_trajectory_damping_order.  The trajectory's nord alone changes; every level is resolved again (the fields of LevelParams that
+// other setters own -- tracer damping, sub-cycling, dp_ref -- are not resolve_level's and stay).  create's rules for the pair (nord,
+// nord_pert) hold; its refusal of a non-hydrostatic nord > 1 does not: the differentiated del-6 of w and of the heights is built
+// (stages.h Del6B), and a non-hydrostatic handle reaches orders 2 and 3 through this call.
+inline bool Dynamics::set_trajectory_damping_order(int nord) {
+  if (nord < 0 || nord > 3) { err = "fv3lm_set_trajectory_damping_order: nord in 0..3 only"; return false; }
+  if (!opt.split_damp && nord != opt.nord_pert) { err = "fv3lm_set_trajectory_damping_order: split_damp = 0 and nord differs from nord_pert: the trajectory's damping options are the perturbation's (run_setup_pert, fv_control_tlmadm.F90:220-229); create the handle with split_damp = 1"; return false; }
+  if (nord == 0 && opt.nord_pert > 0) { err = "fv3lm_set_trajectory_damping_order: nord = 0 with nord_pert > 0 -- c_sw computes divg_d only for the trajectory's nord > 0, the perturbation's damping would read an undefined array"; return false; }
+  if (nord == opt.nord) return true;
+  const int npz = g.npz, nord_was = opt.nord;
+  const std::vector<LevelParams> lev_was = lev_host;
+  opt.nord = nord;
+  for (int k = 1; k <= npz; ++k) resolve_level(opt, k, npz, lev_host[(size_t)k - 1]);
+  resolve_level(opt, npz, npz, lev_host[(size_t)npz]);          // interface npz+1 repeats the last layer (Dycore::init)
+  h2d(ex, lev_dev, lev_host.data(), sizeof(LevelParams) * lev_host.size());
+  rebuild_acoustic_repoint();
+  if (!sticky_error().empty()) {
+    // the rebuild failed (device memory): the order and the level table go back to what they were, so the getter tells the truth; the
+    // sticky error stays and every later call on the handle fails with it
+    opt.nord = nord_was; lev_host = lev_was;
+    h2d(ex, lev_dev, lev_host.data(), sizeof(LevelParams) * lev_host.size());
+    err = sticky_error(); return false;
   }
   return true;
 }
@@ -673,14 +725,7 @@ inline bool Dynamics::set_rayleigh(double tau, double cutoff, const double* c2l)
   rf_ck = (double*)dev_alloc((nh ? 3 : 2) * pl * kmax * 8);
   if (nh) {
     if (!rf_pth.t) { rf_pth.t = (double*)dev_alloc(n3 * 8); rf_pth.p = (double*)dev_alloc(n3 * 8); rf_pth.nk = npz; F["rf_pt"] = rf_pth; }
-    pt_in_rf.c.assign(classes.size(), Program{}); pt_in_rf.cur = &cur_cls;
-    for (int c = 0; c < (int)classes.size(); ++c) {
-      set_class(c);
-      DynPtInNhRf s; s.in[0] = f("pt"); s.in[1] = nq > 0 ? q[0] : Fld{}; if (!s.in[1].t) s.in[1].nk = npz; s.in[2] = f("delp"); s.in[3] = f("delz");
-      s.in[4] = rf_pth; s.out[0] = f("pt_o"); s.out[1] = f("pkz"); s.orect[0] = s.orect[1] = R(g.is(), g.ie(), g.js(), g.je()); s.k1 = npz;
-      s.zvir = opt.zvir; s.akap = opt.akap; s.rdg = -opt.rdgas / opt.grav; s.has_q = nq > 0; s.kmax = kmax; add(pt_in_rf, "pt_in", s);
-    }
-    set_class(-1);
+    build_pt_in_rf(kmax);
   }
   if (!sticky_error().empty()) { err = sticky_error(); return false; }
   rf_kmax = kmax;

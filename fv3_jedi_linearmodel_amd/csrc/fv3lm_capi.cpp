@@ -124,6 +124,16 @@ int fv3lm_external_damping(fv3lm_handle* h, double* d_ext) {
   *d_ext = h->d.d_ext;
   return 0;
 }
+int fv3lm_set_trajectory_damping_order(fv3lm_handle* h, int nord) {
+  if (!h) return fail("fv3lm_set_trajectory_damping_order: null handle");
+  if (!h->d.set_trajectory_damping_order(nord)) return fail(h->d.err);
+  return status(h);
+}
+int fv3lm_trajectory_damping_order(fv3lm_handle* h, int* nord) {
+  if (!h || !nord) return fail("fv3lm_trajectory_damping_order: null argument");
+  *nord = h->d.opt.nord;
+  return 0;
+}
 int fv3lm_set_exchange(fv3lm_handle* h, int kind, const int* rows, int nrows) {
   if (!rows && nrows > 0) return fail("fv3lm_set_exchange: null table");
   return h->d.set_exchange(kind, rows, nrows) ? 0 : fail(h->d.err);

@@ -1323,6 +1323,25 @@ struct Del6AD {
 };
 typedef Edged<Del6AD, false> Del6A;
 typedef Edged<Del6AD, true> Del6AE;
+// del6_vt_flux with nord = 2, the second inner Laplacian (sw_core_tlm.F90:3775-3799, n = 2): B = -L(A) of A = L(q) (Del6A on the ring
+// one wider), A's corner halo through the views as q's.  Zero where the level does not run order 2.  sel 0: w in d_sw (nord_w, damp_w),
+// 1: the interface heights in update_dz_d (nord_v, damp_vt)
+struct Del6BD {
+  STAGE_BASE("Del6B", 1, 1)   // in: d2 (A)   out: d2b (B)
+  HD static constexpr bool uses(int, int di, int dj, int) { return di == 0 || dj == 0; }
+  HD static constexpr unsigned wants(int) { return 0x1u; }
+  static constexpr int NALIAS = 2;
+  HD static constexpr int alias_box(int M) { return M; }
+  HD bool alias(const Ctx& c, int, int i, int j, int n, int& ai, int& aj) const { return corner_alias(c.g, n + 1, i, j, ai, aj); }
+  HD static constexpr Box box(int) { return Box{-1, 1, -1, 1, 0, 0}; }
+  int sel = 0;
+  HD static bool on(const LevelParams& l, int sel) { return sel == 0 ? (l.nord_w == 2 && l.damp_w > 1.e-5) : (l.nord_v == 2 && l.damp_vt > 1.e-5); }
+  template <bool EDGE, class T, class A>
+  HD void eval_e(const A& a, const Ctx& c, int tile, int i, int j, int k, T* o) const {
+    o[0] = T(0.);
+    if (on(c.lev[k - 1], sel)) o[0] = -1.0 * lap_corner<EDGE, 0, T>(a, c, tile, i, j);
+  }
+};
 // momentum update (sw_core_tlm.F90:3555-3564) + vorticity-damping fluxes, trajectory and
 // perturbation coefficients kept apart (sw_core_tlm.F90:2436-2452, :2502-2530)
 // N2: the build whose trajectory runs its vorticity damping with nord_v = 2 on some level (split_damp with nord >= 2): the twice-applied
@@ -1601,23 +1620,25 @@ struct PGradCNh {
     }
   }
 };
-// del-2 / del-4 damping increment of a cell scalar (DEL6_VT_FLUX with nord <= 1 + its divergence): dw for w in d_sw
+// del-2 / del-4 / del-6 damping increment of a cell scalar (DEL6_VT_FLUX + its divergence): dw for w in d_sw
 // (sw_core_tlm.F90:3020-3040, damp = (damp_w da_min_c)^(nord_w+1)), and the damping term of UPDATE_DZ_D (:655-667, damp raw).
-template <class T, class A>
+template <class T, int ML = 1, class A>
 HD T del6_increment(const A& a, const Ctx& c, int tile, int i, int j, int nord, double damp) {
-  // inputs: 0 = q, 1 = inner Laplacian of q (Del6A)
+  // inputs: 0 = q, ML = the last inner Laplacian of q (1: Del6A for nord = 1; the N2 stages pass Del6B's slot for nord = 2)
   T fxa, fxb, fya, fyb;
   if (nord == 0) {
     fxa = MET(del6_v, i, j) * (IN(0, i - 1, j) - IN(0, i, j)); fxb = MET(del6_v, i + 1, j) * (IN(0, i, j) - IN(0, i + 1, j));
     fya = MET(del6_u, i, j) * (IN(0, i, j - 1) - IN(0, i, j)); fyb = MET(del6_u, i, j + 1) * (IN(0, i, j) - IN(0, i, j + 1));
   } else {
-    fxa = MET(del6_v, i, j) * (IN(1, i, j) - IN(1, i - 1, j)); fxb = MET(del6_v, i + 1, j) * (IN(1, i + 1, j) - IN(1, i, j));
-    fya = MET(del6_u, i, j) * (IN(1, i, j) - IN(1, i, j - 1)); fyb = MET(del6_u, i, j + 1) * (IN(1, i, j + 1) - IN(1, i, j));
+    fxa = MET(del6_v, i, j) * (IN(ML, i, j) - IN(ML, i - 1, j)); fxb = MET(del6_v, i + 1, j) * (IN(ML, i + 1, j) - IN(ML, i, j));
+    fya = MET(del6_u, i, j) * (IN(ML, i, j) - IN(ML, i, j - 1)); fyb = MET(del6_u, i, j + 1) * (IN(ML, i, j + 1) - IN(ML, i, j));
   }
   return damp * ((fxa - fxb + (fya - fyb)) * MET(rarea, i, j));
 }
-struct DswDw {
-  STAGE_BASE("DswDw", 2, 1)   // in: w d6w   out: dw
+// N2: the build in which some level damps w with nord_w = 2 (a trajectory nord of 2 or 3): Del6B's result comes in as one more input
+template <bool N2>
+struct DswDwT {
+  STAGE_BASE(N2 ? "DswDw2" : "DswDw", N2 ? 3 : 2, 1)   // in: w d6w [d6bw]   out: dw
   STAGE_NO_ALIAS
   HD static constexpr bool uses(int, int di, int dj, int) { return di == 0 || dj == 0; }
   HD static constexpr unsigned wants(int) { return 0x1u; }
@@ -1629,9 +1650,11 @@ struct DswDw {
     if (!(l.damp_w > 1.e-5)) return;
     double d4 = l.damp_w * c.m.da_min_c;
     if (l.nord_w == 1) d4 = d4 * d4;
+    if constexpr (N2) if (l.nord_w == 2) { o[0] = del6_increment<T, 2>(a, c, tile, i, j, 2, d4 * d4 * d4); return; }
     o[0] = del6_increment<T>(a, c, tile, i, j, l.nord_w, d4);
   }
 };
+typedef DswDwT<false> DswDw;
 // w after the transport: back to velocity with the new delp, plus the damping increment (sw_core_tlm.F90:3050-3055, :3305-3330)
 struct DswUpdateW {
   STAGE_COMMON("DswUpdateW", 6, 1)   // in: w delp delp_n gx gy dw   out: w_n
@@ -1642,18 +1665,35 @@ struct DswUpdateW {
   }
 };
 // UPDATE_DZ_D, update of the interface heights from the transport fluxes + damping (nh_utils_tlm.F90:655-700)
-struct UpdateDzD {
-  STAGE_BASE("UpdateDzD", 6, 1)   // in: zh d6z fx fy ra_x ra_y (all npz+1)   out: zh_a
+// N2: the build in which some interface damps the heights with nord_v = 2: Del6B's result comes in as one more input
+template <bool N2>
+struct UpdateDzDT {
+  STAGE_BASE(N2 ? "UpdateDzD2" : "UpdateDzD", N2 ? 7 : 6, 1)   // in: zh d6z fx fy ra_x ra_y [d6bz] (all npz+1)   out: zh_a
   STAGE_NO_ALIAS
-  HD static constexpr bool uses(int M, int di, int dj, int) { return M < 2 ? (di == 0 || dj == 0) : true; }
+  HD static constexpr bool uses(int M, int di, int dj, int) { return (M < 2 || M == 6) ? (di == 0 || dj == 0) : true; }
   HD static constexpr unsigned wants(int) { return 0x1u; }
-  HD static constexpr Box box(int M) { return M < 2 ? Box{-1, 1, -1, 1, 0, 0} : M == 2 ? Box{0, 1, 0, 0, 0, 0} : M == 3 ? Box{0, 0, 0, 1, 0, 0} : Box{0, 0, 0, 0, 0, 0}; }
+  HD static constexpr Box box(int M) { return (M < 2 || M == 6) ? Box{-1, 1, -1, 1, 0, 0} : M == 2 ? Box{0, 1, 0, 0, 0, 0} : M == 3 ? Box{0, 0, 0, 1, 0, 0} : Box{0, 0, 0, 0, 0, 0}; }
   template <class T, class A>
   HD void eval(const A& a, const Ctx& c, int tile, int i, int j, int k, T* o) const {
     const LevelParams& l = c.lev[k - 1];      // entry npz+1 repeats entry npz (ndif(km+1) = ndif(km))
     const double ar = MET(area, i, j);
     T z = (IN(0, i, j) * ar + (IN(2, i, j) - IN(2, i + 1, j)) + (IN(3, i, j) - IN(3, i, j + 1))) / (IN(4, i, j) + IN(5, i, j) - ar);
+    if constexpr (N2) if (l.damp_vt > 1.e-5 && l.nord_v == 2) { o[0] = z + del6_increment<T, 6>(a, c, tile, i, j, 2, l.damp_vt); return; }
     if (l.damp_vt > 1.e-5) z = z + del6_increment<T>(a, c, tile, i, j, l.nord_v, l.damp_vt);
+    o[0] = z;
+  }
+};
+typedef UpdateDzDT<false> UpdateDzD;
+// the same with the damping term handed in (del6.h: the whole del-6 chain as one launch)
+struct UpdateDzDF {
+  STAGE_COMMON("UpdateDzDF", 6, 1)   // in: zh dz6 fx fy ra_x ra_y (all npz+1)   out: zh_a
+  HD static constexpr Box box(int M) { return M == 2 ? Box{0, 1, 0, 0, 0, 0} : M == 3 ? Box{0, 0, 0, 1, 0, 0} : Box{0, 0, 0, 0, 0, 0}; }
+  template <class T, class A>
+  HD void eval(const A& a, const Ctx& c, int tile, int i, int j, int k, T* o) const {
+    const LevelParams& l = c.lev[k - 1];
+    const double ar = MET(area, i, j);
+    T z = (IN(0, i, j) * ar + (IN(2, i, j) - IN(2, i + 1, j)) + (IN(3, i, j) - IN(3, i, j + 1))) / (IN(4, i, j) + IN(5, i, j) - ar);
+    if (l.damp_vt > 1.e-5) z = z + IN(1, i, j);
     o[0] = z;
   }
 };

@@ -20,6 +20,16 @@ def _apply_metrics_hook(hook, metrics, edge, ecorner):
     return {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in metrics.items()}, np.ascontiguousarray(edge), np.ascontiguousarray(ecorner)
 
 
+def _create_options(opt, late_nord):
+    """the options fv3lm_create gets: with late_nord a copy whose trajectory nord is nord_pert (the requested one follows through
+    fv3lm_set_trajectory_damping_order)"""
+    if not late_nord:
+        return opt
+    o = type(opt).from_buffer_copy(opt)
+    o.nord = o.nord_pert
+    return o
+
+
 def _pop_tracer_damping(optkw):
     """the nord_tr=, trdm2=, nord_tr_pert=, trdm2_pert=, split_damp_tr= keywords of a case (fv3lm_set_tracer_damping); None: never set"""
     kw = {k: optkw.pop(k) for k in ("nord_tr", "trdm2", "nord_tr_pert", "trdm2_pert", "split_damp_tr") if k in optkw}
@@ -34,6 +44,8 @@ class Case:
         tau=, rf_cutoff=: Rayleigh damping of the upper layers (fv3lm_set_rayleigh; off by default).
         nord_tr=, trdm2=, nord_tr_pert=, trdm2_pert=, split_damp_tr=: tracer damping (fv3lm_set_tracer_damping; never called by default).
         d_ext=: external-mode divergence damping (fv3lm_set_external_damping; never called by default).
+        late_nord=True: the library is created with nord = nord_pert and gets the requested nord through
+        fv3lm_set_trajectory_damping_order (the way of a non-hydrostatic host to nord 2, 3); self.opt, and with it the oracle, keep it.
         levels=(ak, bk): hybrid coefficients [npz+1] in place of grid.hybrid_levels; the state's delp follows them at the same ps.
         metrics_hook (face cases): callable(metrics, edge, ecorner) applied to the metric dict [1, pj, pi] and the a2b edge data of the
         face before the library instance (and the oracle) are created; it changes them in place or returns the three to use instead.
@@ -43,6 +55,7 @@ class Case:
         levels = optkw.pop("levels", None)
         self.tracer_damping = _pop_tracer_damping(optkw)
         self.d_ext = optkw.pop("d_ext", None)
+        self.late_nord = bool(optkw.pop("late_nord", False))
         self.opt = default_options(**optkw)
         self.face = face
         if face is None:
@@ -81,9 +94,11 @@ class Case:
             self.lib = self.dy = None
             return
         self.lib = self._load_library(backend)
-        self.dy = Dycore(self.lib, self.dims, self.opt, self.metrics, self.da_min, self.da_min_c, self.phis, self.ak, self.bk)
+        self.dy = Dycore(self.lib, self.dims, _create_options(self.opt, self.late_nord), self.metrics, self.da_min, self.da_min_c, self.phis, self.ak, self.bk)
         if face is not None:
             self.dy.set_face_data(self.edge, self.ecorner)
+        if self.late_nord:
+            self.dy.set_trajectory_damping_order(self.opt.nord)
         self._after_create(backend)
         if self.tau:
             self.dy.set_rayleigh(self.tau, self.rf_cutoff, self.c2l)
@@ -146,6 +161,7 @@ class CubeCase:
         levels = optkw.pop("levels", None)
         self.tracer_damping = _pop_tracer_damping(optkw)
         self.d_ext = optkw.pop("d_ext", None)
+        self.late_nord = bool(optkw.pop("late_nord", False))
         self.opt = default_options(**optkw)
         self.metrics, self.da_min, self.da_min_c, self.edge, self.ecorner, self.geo = cube.cubed_sphere_metrics(n, edge_forms=edge_forms)
         self.c2l = self.geo["c2l"]
@@ -197,8 +213,10 @@ class CubeCase:
             self.lib = self.dy = None
             return
         self.lib = self._load_library(backend)
-        self.dy = Dycore(self.lib, self.dims, self.opt, self.metrics, self.da_min, self.da_min_c, self.phis, self.ak, self.bk)
+        self.dy = Dycore(self.lib, self.dims, _create_options(self.opt, self.late_nord), self.metrics, self.da_min, self.da_min_c, self.phis, self.ak, self.bk)
         self.dy.set_face_data(self.edge, self.ecorner)
+        if self.late_nord:
+            self.dy.set_trajectory_damping_order(self.opt.nord)
         self._after_create(backend)
         if self.tau:
             self.dy.set_rayleigh(self.tau, self.rf_cutoff, self.c2l)

@@ -44,7 +44,8 @@ typedef struct fv3lm_options {
   int hydrostatic;
   int split_damp;   /* fv_flags_pert_type%split_damp (fv_arrays_tlmadm.F90:76; the reference's default is .true.).  1: the perturbation takes its own damping
                        (nord_pert, dddmp_pert, d2_bg_pert, d4_bg_pert, vtdm4_pert ... with the perturbation sponge rules, dyn_core_tlm.F90:835-921), the
-                       trajectory values the trajectory's (sw_core_tlm.F90:1664-1682, :1787-1803, :2341-2369); the trajectory's nord may then be 2 or 3.
+                       trajectory values the trajectory's (sw_core_tlm.F90:1664-1682, :1787-1803, :2341-2369); the trajectory's nord may then be 2 or 3
+                       (hydrostatic = 0: through fv3lm_set_trajectory_damping_order after create).
                        0: run_setup_pert has copied the perturbation's damping options onto the trajectory (fv_control_tlmadm.F90:220-229): the two sets
                        handed over must then be equal, anything else is refused. */
   double dddmp, d2_bg, d4_bg, vtdm4, d2_bg_k1, d2_bg_k2, d_con, ke_bg;
@@ -132,6 +133,23 @@ int fv3lm_tracer_damping(fv3lm_handle* h, int* nord2, double* trdm2);
 int fv3lm_set_external_damping(fv3lm_handle* h, double d_ext);
 /* d_ext as set (0 on a handle that never called the setter). */
 int fv3lm_external_damping(fv3lm_handle* h, double* d_ext);
+/* The trajectory's divergence-damping order (flagstruct%nord) after create.  It sets the trajectory's nord, resolves every level's
+ * damping orders and coefficients again (dyn_core_tlm.F90:741-921) and, when the order changed, rebuilds the acoustic program as
+ * fv3lm_set_external_damping does: the work arena and the plan of the trajectory slots of the backward sweep are made anew, so a
+ * forward sweep stored before the call does not serve an adjoint after it -- call it before the first step or between complete
+ * steps (nonlinear sweep + adjoint).  A call with the order the handle already has rebuilds nothing.
+ * Hydrostatic handle: the result is the handle fv3lm_create builds with that nord.
+ * Non-hydrostatic handle: the only way to orders 2 and 3 (fv3lm_create refuses them).  w in d_sw and the interface heights in
+ * update_dz_d are then damped by the differentiated del6_vt_flux of order min(2, nord) -- three Laplacians, tangent and adjoint
+ * (sw_core_tlm.F90:1712-1745, nh_utils_tlm.F90:489-520) -- on the levels outside the sponge, as three stage launches per field and
+ * mode (FV3LM_DEL6_FUSED=1 in the environment at that time: one LDS-tiled launch).  A host creates with
+ * nord = min(flagstruct%nord, nord_pert) and then passes flagstruct%nord here.
+ * Refused, the handle left as it was: nord outside 0..3; split_damp = 0 with nord != nord_pert; nord = 0 with nord_pert > 0.
+ * A rebuild that fails (device memory) puts the order and the level table back, but leaves the handle's error set: the getter
+ * reports the former order and every later call on the handle fails. */
+int fv3lm_set_trajectory_damping_order(fv3lm_handle* h, int nord);
+/* nord as in force (the value given to fv3lm_create on a handle that never called the setter). */
+int fv3lm_trajectory_damping_order(fv3lm_handle* h, int* nord);
 /* Halo exchange between the resident faces: replaces the FMS calls mpp_update_domains / mpp_get_boundary that the
  * reference issues from DYN_CORE_TLM (dyn_core_tlm.F90:1744-1790, :1960-1990, :2280-2300, :2418-2434) and
  * FV_DYNAMICS_TLM (fv_dynamics_tlm.F90:646-651, :708-712).  One table per kind of exchange:
