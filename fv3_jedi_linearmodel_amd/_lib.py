@@ -53,6 +53,8 @@ class Fv3LmLibrary:
         L.fv3lm_sync.argtypes = [C.c_void_p]
         L.fv3lm_launch_count.argtypes = [C.c_void_p]
         L.fv3lm_launch_count.restype = C.c_long
+        L.fv3lm_tp2_launch_count.argtypes = [C.c_void_p]
+        L.fv3lm_tp2_launch_count.restype = C.c_long
         L.fv3lm_level_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp]
         for fn in ("fv3lm_pressures", "fv3lm_tracer_2d", "fv3lm_fv_dynamics"):
             getattr(L, fn).argtypes = [C.c_void_p, C.c_int]
@@ -581,6 +583,9 @@ class Dycore:
 
     def launch_count(self):
         return self.lib.L.fv3lm_launch_count(self.h)
+
+    def tp2_launch_count(self):
+        return self.lib.L.fv3lm_tp2_launch_count(self.h)
 
     # ---- face mode (dims.face = 1) -------------------------------------------------------
     def set_face_data(self, edge, ecorner):

@@ -71,6 +71,7 @@ struct Exec {
     return r;
   }
   long launches = 0;
+  long tp2_launches = 0;      // of them, fv_tp_2d in the wavefront layout (tp2.h): which form of the routine a launch took
   bool profiling = false;
   std::vector<ProfRec> recs;
   void mark_begin(const char* name, const char* suffix, double bytes) {

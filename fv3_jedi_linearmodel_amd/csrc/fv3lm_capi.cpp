@@ -346,6 +346,7 @@ int fv3lm_fv3_to_pert(fv3lm_handle* h, double* u, double* v, double* t, double* 
 int fv3lm_zero_work_adjoint(fv3lm_handle* h) { h->d.zero_work_adjoint(); return 0; }
 int fv3lm_sync(fv3lm_handle* h) { dev_sync(h->d.ex); return status(h); }
 long fv3lm_launch_count(fv3lm_handle* h) { return h->d.ex.launches; }
+long fv3lm_tp2_launch_count(fv3lm_handle* h) { return h->d.ex.tp2_launches; }
 int fv3lm_level_params(fv3lm_handle* h, int k, int* ip, double* rp) {
   if (k < 1 || k > h->d.g.npz) return fail("level out of range");
   const LevelParams& l = h->d.lev_host[k - 1];

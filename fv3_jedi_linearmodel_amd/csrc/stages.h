@@ -210,16 +210,19 @@ HD double low_flux(int iord, double qm, double q0, double blm, double brm, doubl
 }
 HD constexpr bool hord_low(int iord) { return iord >= 3 && iord <= 7; }
 template <class Q, class D>
-HD double ppm_al7(int iord, bool face, int x, int n1, const Q& q, const D& da) {      // iord 7: edge values kept non-negative (tp_core_tlm.F90:345-349, :357-373, :382-405)
+HD double ppm_al7(int iord, bool face, bool ydir, int x, int n1, const Q& q, const D& da) {      // iord 7: edge values kept non-negative (tp_core_tlm.F90:345-349, :357-373, :382-405)
   const double al = ppm_al<double>(face, x, n1, q, da);
   if (iord != 7) return al;
   if (face && (x <= 2 || x >= n1 - 1)) return fmax(0., al);
-  return al < 0. ? 0.5 * (q(x - 1) + q(x)) : al;
+  // a negative value gives way to the mean of the cells x-1, x in xppm (:347); yppm takes the cells x, x+1 (:1063, the nonlinear model's
+  // tp_core_nlm.F90:620 alike) -- not the transpose, kept as the reference has it
+  if (!(al < 0.)) return al;
+  return ydir ? 0.5 * (q(x) + q(x + 1)) : 0.5 * (q(x - 1) + q(x));
 }
 template <class Q, class D>
-HD double ppm_flux_traj(int iord, bool face, int m, int n1, const Q& q, const D& da, double cc) {
+HD double ppm_flux_traj(int iord, bool face, bool ydir, int m, int n1, const Q& q, const D& da, double cc) {
   if (hord_low(iord)) {
-    const double alm = ppm_al7(iord, face, m - 1, n1, q, da), al0 = ppm_al7(iord, face, m, n1, q, da), alp = ppm_al7(iord, face, m + 1, n1, q, da);
+    const double alm = ppm_al7(iord, face, ydir, m - 1, n1, q, da), al0 = ppm_al7(iord, face, ydir, m, n1, q, da), alp = ppm_al7(iord, face, ydir, m + 1, n1, q, da);
     const double qm = q(m - 1), q0 = q(m);
     return low_flux(iord, qm, q0, alm - qm, al0 - qm, al0 - q0, alp - q0, cc > 0., cc);
   }

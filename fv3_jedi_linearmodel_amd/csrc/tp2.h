@@ -372,6 +372,7 @@ FV3LM_LINK void run_tp2(Exec& ex, int mode, const TpFusedArgs& a0, const Ctx& c)
   const int nbx = tiled_blocks(Qr.i0, Qr.i1, TP2_W), nby = tiled_blocks(Qr.j0, Qr.j1, TP2_H);
   if (mode == MODE_TL) run_tiled<Tp2Blk<Dual, tiled_nth(FV3LM_TP2_WAVES_TL)>>(ex, "TpFused", ".tl", tpf_bytes(a, c.g, mode), Qr, nbx, nby, a, c);
   else run_tiled<Tp2Blk<double, tiled_nth(FV3LM_TP2_WAVES_NL)>>(ex, "TpFused", ".nl", tpf_bytes(a, c.g, mode), Qr, nbx, nby, a, c);
+  ex.tp2_launches++;
 }
 
 }  // namespace fv3

@@ -99,8 +99,8 @@ DEV void tp_fused_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int
   const TpfTile<T> q{lds, I0 - 3, J0 - 3, TPF_QW}, fy2{lds + TPF_NQ, I0 - 3, J0, TPF_QW}, qi{lds + TPF_NQ + TPF_NFY2, I0 - 3, J0, TPF_QW},
       fx2{lds + TPF_NQ + TPF_NFY2 + TPF_NQI, I0, J0 - 3, TPF_W + 1}, qj{lds + TPF_NQ + TPF_NFY2 + TPF_NQI + TPF_NFX2, I0, J0 - 3, TPF_W};
   const int iord = TRAJ ? hord_traj_of(c.lev[k - 1], a.hsel) : hord_of(c.lev[k - 1], a.hsel), iord_in = (TRAJ && iord == 10) ? 8 : iord;
-  auto flux1d = [&](int io, int m, int n1, const auto& line, const auto& da, const T& cc) -> T {
-    if constexpr (TRAJ) return ppm_flux_traj(io, face, m, n1, line, da, cc); else return ppm_flux<T>(io, face, m, n1, line, da, cc);
+  auto flux1d = [&](int io, bool ydir, int m, int n1, const auto& line, const auto& da, const T& cc) -> T {
+    if constexpr (TRAJ) return ppm_flux_traj(io, face, ydir, m, n1, line, da, cc); else return ppm_flux<T>(io, face, m, n1, line, da, cc);
   };
   // flux capacitors on a split level: the first pass adds the tangents, the trajectory pass the values
   auto acc_flux = [&](const Fld& acc, size_t n, const T& f) {
@@ -146,7 +146,7 @@ DEV void tp_fused_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int
       auto line = [&](int jj) -> T { int ii = i, j2 = jj; if (face) corner_map(g, 2, ii, j2); return q.get(ii, j2); };
       const MetY da{c.m.dya, c, tile, i};
       const T cc = PRE ? cy_pre[uu] : IO::ld(a.cry, at(i, j));
-      const T f = flux1d(iord_in, j, ny + 1, line, da, cc);
+      const T f = flux1d(iord_in, true, j, ny + 1, line, da, cc);
       fy2.set(i, j, f);
       if (STORE && own_i(i) && (j <= J1 || lasty)) a.fy2.t[at(i, j)] = val(f);
       if (!TRAJ && a.do_acc && own_i(i) && (j <= J1 || lasty)) IO::st(a.acy, at(i, j), IO::ld(a.acy, at(i, j)) + cc);
@@ -160,7 +160,7 @@ DEV void tp_fused_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int
       auto line = [&](int ii) -> T { int i2 = ii, jj = j; if (face) corner_map(g, 1, i2, jj); return q.get(i2, jj); };
       const MetX da{c.m.dxa, c, tile, j};
       const T cc = PRE ? cx_pre[uu] : IO::ld(a.crx, at(i, j));
-      const T f = flux1d(iord_in, i, nx + 1, line, da, cc);
+      const T f = flux1d(iord_in, false, i, nx + 1, line, da, cc);
       fx2.set(i, j, f);
       if (STORE && own_j(j) && (i <= I1 || lastx)) a.fx2.t[at(i, j)] = val(f);
       if (!TRAJ && a.do_acc && own_j(j) && (i <= I1 || lastx)) IO::st(a.acx, at(i, j), IO::ld(a.acx, at(i, j)) + cc);
@@ -203,7 +203,7 @@ DEV void tp_fused_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int
       if (j <= J1 && (i <= I1 || lastx)) {          // fx(i,j)
         auto line = [&](int ii) -> T { return qi.get(ii, j); };
         const MetX da{c.m.dxa, c, tile, j};
-        const T fo = flux1d(iord, i, nx + 1, line, da, IO::ld(a.crx, at(i, j)));
+        const T fo = flux1d(iord, false, i, nx + 1, line, da, IO::ld(a.crx, at(i, j)));
         if (STORE && a.store_fo) a.fxo.t[at(i, j)] = val(fo);
         T f = 0.5 * (fo + fx2.get(i, j)) * IO::ld(a.mx, at(i, j));
         if (dmp) {
@@ -219,7 +219,7 @@ DEV void tp_fused_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int
       if (i <= I1 && (j <= J1 || lasty)) {          // fy(i,j)
         auto line = [&](int jj) -> T { return qj.get(i, jj); };
         const MetY da{c.m.dya, c, tile, i};
-        const T fo = flux1d(iord, j, ny + 1, line, da, IO::ld(a.cry, at(i, j)));
+        const T fo = flux1d(iord, true, j, ny + 1, line, da, IO::ld(a.cry, at(i, j)));
         if (STORE && a.store_fo) a.fyo.t[at(i, j)] = val(fo);
         T f = 0.5 * (fo + fy2.get(i, j)) * IO::ld(a.my, at(i, j));
         if (dmp) {

@@ -130,7 +130,8 @@ void ppm_line_mono(int iord, int first, int last, int np, bool any_edge, bool ed
 }
 
 template <class FQ, class FC, class FD, class FOut>
-void ppm_line_low(int iord, int first, int last, int np, bool any_edge, bool edge_lo, bool edge_hi, const FQ& q, const FC& c, const FD& da, const FOut& flux);
+void ppm_line_low(int iord, int first, int last, int np, bool any_edge, bool edge_lo, bool edge_hi, const FQ& q, const FC& c, const FD& da, const FOut& flux,
+                  bool ydir = false);
 
 inline void xppm_mono(Arr2<double>& flux, const Arr2<double>& q, const Arr2<double>& c, int iord, int is, int ie, int jfirst, int jlast,
                       const Bounds& bd, const Grid& g) {
@@ -147,7 +148,7 @@ inline void yppm_mono(Arr2<double>& flux, const Arr2<double>& q, const Arr2<doub
   for (int i = ifirst; i <= ilast; ++i)
     if (jord >= 3 && jord <= 7)
       ppm_line_low(jord, js, je, bd.npy, bd.any_edge(), bd.edge_s, bd.edge_n, [&](int j) { return q(i, j); }, [&](int j) { return c(i, j); },
-                   [&](int j) { return g.dya(i, j); }, [&](int j, double f) { flux(i, j) = f; });
+                   [&](int j) { return g.dya(i, j); }, [&](int j, double f) { flux(i, j) = f; }, true);
     else
     ppm_line_mono(jord, js, je, bd.npy, bd.any_edge(), bd.edge_s, bd.edge_n, [&](int j) { return q(i, j); }, [&](int j) { return c(i, j); },
                   [&](int j) { return g.dya(i, j); }, [&](int j, double f) { flux(i, j) = f; });
@@ -293,7 +294,7 @@ void low_fluxes(int iord, int first, int last, const FQ& q, const FC& c, const F
 
 template <class FQ, class FC, class FD, class FOut>
 void ppm_line_low(int iord, int first, int last, int np, bool any_edge, bool edge_lo, bool edge_hi, const FQ& q, const FC& c, const FD& da,
-                  const FOut& flux) {
+                  const FOut& flux, bool ydir) {
   assert(iord >= 3 && iord <= 7);
   int is1 = first - 1, ie3 = last + 2;
   if (any_edge) { is1 = std::max(3, first - 1); ie3 = std::min(np - 2, last + 2); }      // :314-330
@@ -301,7 +302,7 @@ void ppm_line_low(int iord, int first, int last, int np, bool any_edge, bool edg
   std::vector<double> al_(n, 0.);
   auto al = [&](int i) -> double& { return al_[i - lo]; };
   for (int i = is1; i <= ie3; ++i) al(i) = low_p1 * (q(i - 1) + q(i)) + low_p2 * (q(i - 2) + q(i + 1));      // :342-344
-  if (iord == 7) for (int i = is1; i <= ie3; ++i) if (al(i) < 0.) al(i) = 0.5 * (q(i - 1) + q(i));           // :345-349
+  if (iord == 7) for (int i = is1; i <= ie3; ++i) if (al(i) < 0.) al(i) = ydir ? 0.5 * (q(i) + q(i + 1)) : 0.5 * (q(i - 1) + q(i));   // :345-349; yppm :1063 takes the cells j, j+1
   auto two_sided = [&](int e) {
     return 0.5 * (((2. * da(e - 1) + da(e - 2)) * q(e - 1) - da(e - 1) * q(e - 2)) / (da(e - 2) + da(e - 1)) +
                   ((2. * da(e) + da(e + 1)) * q(e) - da(e) * q(e + 1)) / (da(e) + da(e + 1)));

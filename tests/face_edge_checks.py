@@ -1,7 +1,8 @@
 """The face-edge operators of the product, point by point, against tests/face_oracle.py: the restatement of d2a2c_vect, divergence_corner,
 the area-flux scaling of c_sw and what follows it (transport of delp, pt, kinetic energy, vorticity, wind update: c_sw_rest), the first
 loops of d_sw and what follows them (B-grid winds, xtp_u / ytp_v, kinetic energy, vorticity, divergence damping, del6_vt_flux:
-d_sw_rest, with u_m, v_m by composition), a2b_ord4 / one_grad_p and p_grad_c written from the reference's nonlinear
+d_sw_rest, with u_m, v_m by composition), the transports of d_sw through fv_tp_2d with every trajectory scheme and u_m, v_m fully
+restated (d_sw_transport, d_sw_transport_nh), a2b_ord4 / one_grad_p and p_grad_c written from the reference's nonlinear
 Fortran (whole faces: check; six faces cut into tiles: check_layout).  The library receives
 the RESTATEMENT's metrics (harness metrics_hook), with 1e30 in every entry the reference leaves undefined, so product and reference share
 the corner points and nothing else.  Values and tangent through put / run_group(TL) / get; the adjoint with seeds on the compared outputs
@@ -50,13 +51,21 @@ def restatement_hook(n, face=None, value=1.0e30):
     return hook
 
 
-def detuned(M):
+def detuned(M, lengths=False):
     """sin_sg<k>, cos_sg<k> scaled by factors of their own (1 + 0.01 k, 1 - 0.005 k).  On the gnomonic cube the two cells across a face
     edge hold the same angle, sin_sg(i, j-1, 4) = sin_sg(i, j, 2) to rounding, so which of the two a branch selects cannot show on the
     true metrics; with these factors it does.  The planes stop being a geometry, which no operator here minds: product and restatement
-    get the same numbers."""
+    get the same numbers.
+    lengths: dxa, dya as well, by the smooth factor 1 + 0.01 i - 0.007 j, symmetric across no edge: on the cube dxa(0, j) = dxa(1, j) and
+    dxa(-1, j) = dxa(2, j) to rounding, so a swap inside the two-sided edge value of xppm / yppm cannot show on the true metrics."""
     f = lambda k: (1 + 0.01 * int(k[-1])) if k.startswith("sin_sg") else (1 - 0.005 * int(k[-1])) if k.startswith("cos_sg") else 1.0
-    return {k: v * f(k) for k, v in M.items()}
+    out = {k: v * f(k) for k, v in M.items()}
+    if lengths:
+        pj = M["dxa"].shape[-1]
+        J, I = np.meshgrid(np.arange(pj) - 2.0, np.arange(pj) - 2.0, indexing="ij")
+        for k in ("dxa", "dya"):
+            out[k] = M[k] * (1 + 0.01 * I - 0.007 * J)
+    return out
 
 
 regions, region_errors = G.regions, G.region_errors
@@ -280,8 +289,9 @@ class DSwRest:
         for k in range(1, c.npz + 1):
             ks = k <= o.n_sponge_pert - 1 and o.hord_ks_pert            # model_tlmadm/dyn_core_tlm.F90:862-875
             iord = o.hord_mt_ks_pert if ks else o.hord_mt_pert
-            t = dict(fo.level_rules(o, k, c.npz), dddmp=o.dddmp, d4_bg=o.d4_bg, iord=iord)
-            q = dict(fo.level_rules_pert(o, k), dddmp=o.dddmp_pert, d4_bg=o.d4_bg_pert, iord=iord)
+            iord_t = o.hord_mt_ks_traj if (k <= o.n_sponge_pert - 1 and o.hord_ks_traj) else o.hord_mt      # the values' scheme (sw_core_tlm.F90:1987-2002, :2059-2072)
+            t = dict(fo.level_rules(o, k, c.npz), dddmp=o.dddmp, d4_bg=o.d4_bg, iord=iord, iord_t=iord_t)
+            q = dict(fo.level_rules_pert(o, k), dddmp=o.dddmp_pert, d4_bg=o.d4_bg_pert, iord=iord, iord_t=iord_t)
             if not o.split_damp:        # run_setup_pert has made the two namelists equal; the divergence damping then takes the trajectory's level rule
                 q.update(nord=t["nord"], d2_divg=t["d2_divg"], dddmp=t["dddmp"], d4_bg=t["d4_bg"])
             dy = getattr(c, "dy", None)
@@ -289,14 +299,14 @@ class DSwRest:
                 ip, rp = dy.level_params(k)
                 assert (ip[0], ip[5], ip[6], ip[9]) == (iord, t["nord"], t["nord_v"], q["nord_v"]), (k, ip, t, q)
                 assert (rp[0], rp[1], rp[5]) == (t["d2_divg"], t["damp_vt"], q["damp_vt"]), (k, rp, t, q)
-            assert iord in (1, 2) and t["nord"] in (0, 1, 2, 3) and q["nord"] in (0, 1), (t, q)
+            assert t["nord"] in (0, 1, 2, 3) and q["nord"] in (0, 1), (t, q)
             self.par.append(t); self.parp.append(q)
         self.face = c.face if isinstance(c.face, int) else None
         self._next = 0
 
     def forms(self):
         """(trajectory nord, perturbation nord, iord, trajectory nord_v) of each level, from the level parameters"""
-        return [(t["nord"], q["nord"], t["iord"], t["nord_v"]) for t, q in zip(self.par, self.parp)]
+        return [(t["nord"], q["nord"], q["iord"], t["nord_v"]) for t, q in zip(self.par, self.parp)]
 
     def levels_of(self, name):
         if name == "del6_d2":       # the reference forms the inner Laplacian where a vorticity damping with nord_v = 1 runs
@@ -337,7 +347,8 @@ class DSwRest:
 
     def apply(self, x, M, edge, ecorner, level0=0):
         """the perturbation's chain on every level (values, and the imaginary part that check() reads as tangent and adjoint); where the
-        trajectory's divergence damping differs (split_damp), the real part of ke2 from the trajectory's"""
+        trajectory's divergence damping differs (split_damp), the real part of ke2 from the trajectory's.  A trajectory hord_mt of its own
+        acts inside the level: the values of the xtp_u / ytp_v fluxes alone (fo.d_sw_rest_level)"""
         lv = []
         for l in range(x["u"].shape[-3]):
             t, q = self.par[level0 + l], self.parp[level0 + l]
@@ -417,7 +428,235 @@ class DSwRest:
         return True
 
 
-OPERATORS = {"c_sw": CSw, "one_grad_p": OneGradP, "p_grad_c": PGradC, "d_sw": DSw, "c_sw_rest": CSwRest, "d_sw_rest": DSwRest, "c_sw_rest_nh": CSwRestNh}
+# Which selectors of tests/face_oracle.py's census a trajectory scheme must have taken BOTH ways somewhere on the face (any of the three
+# transported fields, any of the four sweeps) before a draw is accepted.  al < 0 of scheme 7 cannot fire on delp or pt (positive): the
+# absolute vorticity, of both signs, covers it, and so it does the clip of the six edge values.  near_zero asks for three neighbouring
+# cells with dm = 0 EXACTLY, and dm is an exact zero at every local extremum: grid-scale noise holds runs of three extrema all over
+# the face, in the outer sweeps too (so under hord = 10, whose inner sweeps run scheme 8, the outer ones cover it).  No flat patch is
+# drawn: in an exactly flat run q_i, q_j are flat only to rounding, the last bit decides whether the cell NEXT to the run (whose
+# slopes are finite) passes near_zero, and the restatement itself then moves by 7e-7 between float64 and longdouble.
+# The schemes 8 and 11 limit by min / max alone.
+BULK_BRANCHES = {1: [], 2: [], 333: [], 3: ["smt5", "smt6", "piecewise_linear"], 4: ["smt5", "smt6"], 5: ["bl*br<0"], 6: ["|3b0|<|bl-br|"],
+                 7: ["|3b0|<|bl-br|", "al<0"], 8: [], 9: ["|3b0|>|bl-br|", "near_zero", "pd:limited"], 10: ["|3b0|>|bl-br|", "near_zero"], 11: [],
+                 12: ["|3b0|>|bl-br|", "near_zero"], 13: ["|3b0|>|bl-br|", "near_zero", "pd:limited"]}
+# xtp_u / ytp_v (hord_mt): 7 is 6, 9 limits everywhere, 11 .. 13 are unlimited; each sweep direction on its own.  PERT_PPM runs on ONE cell
+# per row next to each edge (n + 1 points): there the draw is asked for both outcomes of al ar < 0 on each side, the two sweeps together.
+MT_BRANCHES = {1: [], 2: [], 3: ["smt5", "smt6", "piecewise_linear"], 4: ["smt5", "smt6"], 5: ["bl*br<0"], 6: ["|3b0|<|bl-br|"], 7: ["|3b0|<|bl-br|"],
+               8: [], 9: [], 10: ["|dm|<near_zero", "|3b0|>|bl-br|"], 11: [], 12: [], 13: []}
+EDGE_BRANCHES = ["std:al*ar<0", "std:a6da<-da2", "std:a6da>da2"]           # PERT_PPM(iv = 1) of the two edge blocks of 8 .. 13, per sweep direction
+
+
+class DSwTransport(DSwRest):
+    """The transports of d_sw and what they feed (sw_core_nlm.F90:898-1031, :1449-1483, :1527-1539): delp, pt, u, v, uc, vc -> the fluxes
+    fx, fy of delp, gx, gy of pt, fxv, fyv of the absolute vorticity (fo.fv_tp_2d with the level's hord_dp, hord_tm, hord_vt and the
+    del-n damping nord_v / damp_v of delp, nord_t / damp_t of pt), delp_o, pt_o, and u_m, v_m fully restated (the chain of DSwRest with
+    the restated vorticity fluxes).  ua, va, divgd are data (fixed).  Where the trajectory's scheme or damping differs from the
+    perturbation's, every fv_tp_2d gives its VALUES with the trajectory's and its tangent (the imaginary part) with the perturbation's
+    (sw_core_tlm.F90:1664-1682, :1787-1803, :2407-2420), stage by stage, as the reference overwrites fx, fy after the tangent call."""
+    ins = ["delp", "pt", "u", "v", "uc", "vc"]
+    outs = [("fx", "V"), ("fy", "U"), ("gx", "V"), ("gy", "U"), ("fxv", "V"), ("fyv", "U"), ("delp_o", "A"), ("pt_o", "A"), ("u_m", "U"), ("v_m", "V")]
+    composed = []
+    seeded = ["delp_o", "pt_o", "u_m", "v_m"]
+    metrics64 = True                 # the longdouble reference runs on the float64 metrics the library is given
+    detune_dxa = True
+
+    def __init__(self, c):
+        DSwRest.__init__(self, c)
+        o, self.da_min = c.opt, c.da_min
+        self.tr, self.trp = [], []
+        for k in range(1, c.npz + 1):
+            ks = k <= o.n_sponge_pert - 1                                        # model_tlmadm/dyn_core_tlm.F90:862-875
+            t = {f: getattr(o, "hord_%s_ks_traj" % f) if (ks and o.hord_ks_traj) else getattr(o, "hord_" + f) for f in ("dp", "tm", "vt")}
+            q = {f: getattr(o, "hord_%s_ks_pert" % f) if (ks and o.hord_ks_pert) else getattr(o, "hord_%s_pert" % f) for f in ("dp", "tm", "vt")}
+            t.update(nord_t=min(2, o.nord), damp_t=o.vtdm4 if o.do_vort_damp else 0.0)                     # model/dyn_core_nlm.F90:591-594: before the sponge rules
+            q.update(nord_t=min(2, o.nord_pert), damp_t=o.vtdm4_pert if o.do_vort_damp_pert else 0.0)      # dyn_core_tlm.F90:856-859
+            dy = getattr(c, "dy", None)
+            if dy is not None:
+                ip, rp = dy.level_params(k)
+                assert (ip[1], ip[2], ip[3], ip[8]) == (q["vt"], q["tm"], q["dp"], t["nord_t"]) and rp[3] == t["damp_t"], (k, ip, rp, t, q)
+            self.tr.append(t); self.trp.append(q)
+        self.split_damp = bool(o.split_damp)
+        rng = np.random.default_rng(5)
+        shp = (c.npz, self.n + 7, self.n + 7)
+        self.fix6 = [dict(ua=noise(rng, shp, 5.0), va=noise(rng, shp, 5.0), divgd=noise(rng, shp, 1.0e-6)) for _ in range(6)]      # data, face by face
+        self._census = self._cen_mt = None
+        self._level0 = 0
+
+    def _level(self, x, l, p, M, edge, ecorner):
+        if self._cen_mt is not None:                                            # the census of xtp_u / ytp_v
+            p = dict(p, cen=self._cen_mt, tag="L%d:mt:" % (self._level0 + l))
+        return fo.d_sw_rest_level(*[x[k][..., l, :, :] for k in DSwRest.ins], M, edge, ecorner, self.n, self.dt, self.da_min_c, p)
+
+    @property
+    def fix(self):
+        return self.fix6[self.face if self.face is not None else 0]
+
+    def fixed(self, c):
+        out = dict(self.fix)
+        out.update({k: np.zeros((c.npz, c.ny + 7, c.nx + 7)) for k in ("mfx", "mfy", "cx", "cy")})
+        return out
+
+    def draw(self, c, rng):
+        """grid-scale noise: Courant numbers of either sign well inside (-1, 1); delp, pt positive over a wide range (the positive-definite
+        limiter of 9 / 13 needs cells far below their neighbours); u, v of both signs, so the absolute vorticity takes both"""
+        n, npz = self.n, self.npz
+        shp = (npz, n + 7, n + 7)
+        cw = 0.15 * (1.0e7 / n) / self.dt
+        T = dict(delp=1.0e3 * np.exp(noise(rng, shp, 0.5)), pt=300.0 * np.exp(noise(rng, shp, 0.5)), u=noise(rng, shp, 30.0), v=noise(rng, shp, 30.0),
+                 uc=noise(rng, shp, cw), vc=noise(rng, shp, cw))
+        P = dict(delp=noise(rng, shp, 10.0), pt=noise(rng, shp, 1.0), u=noise(rng, shp, 1.0), v=noise(rng, shp, 1.0), uc=noise(rng, shp, 0.03 * cw),
+                 vc=noise(rng, shp, 0.03 * cw))
+        return T, P
+
+    def _tp(self, q, o, ht, hp, kt, kp, same, M, cen, tag, **kw):
+        """one fv_tp_2d of the reference's d_sw_tlm: the values with the trajectory's scheme and damping, the tangent with the perturbation's"""
+        args = (o["crx"], o["cry"])
+        rest = (o["xfx"], o["yfx"], o["ra_x"], o["ra_y"], M, self.n)
+        a = fo.fv_tp_2d(q, *args, ht, *rest, da_min=self.da_min, cen=cen, tag=tag, **kw, **kt)
+        if same or not np.iscomplexobj(a[0]):
+            return a
+        b = fo.fv_tp_2d(q, *args, hp, *rest, da_min=self.da_min, **kw, **kp)
+        return tuple(np.real(x) + 1j * np.imag(y) for x, y in zip(a, b))
+
+    def apply(self, x, M, edge, ecorner, level0=0):
+        nl = x["u"].shape[-3]
+        census = {} if x["u"].ndim == 3 else None                               # a single evaluation, not a batch of Jacobian columns
+        fix = {k: v[level0:level0 + nl] for k, v in self.fix.items()}
+        y = dict(x, **fix)
+        self._cen_mt, self._level0 = census, level0
+        base = DSwRest.apply(self, {k: y[k] for k in DSwRest.ins}, M, edge, ecorner, level0)      # the perturbation's chain, ke2 with the trajectory's values
+        self._cen_mt = None
+        n, lv = self.n, []
+        for l in range(nl):
+            k = level0 + l
+            t, q, ht, hp = self.par[k], self.parp[k], self.tr[k], self.trp[k]
+            L_ = lambda a: a[..., l, :, :]
+            o = {f: L_(base[f]) for f in ("crx", "cry", "xfx", "yfx", "ra_x", "ra_y", "vort_abs", "ke2", "wk")}
+            cen = (lambda f: census) if census is not None else (lambda f: None)
+            sd = self.split_damp
+            delp, pt = L_(x["delp"]), L_(x["pt"])
+            fx, fy = self._tp(delp, o, ht["dp"], hp["dp"], dict(nord=t["nord_v"], damp_c=t["damp_vt"]), dict(nord=q["nord_v"], damp_c=q["damp_vt"]),
+                              ht["dp"] == hp["dp"] and not sd, M, cen("dp"), "L%d:dp:" % k)
+            gx, gy = self._tp(pt, o, ht["tm"], hp["tm"], dict(nord=ht["nord_t"], damp_c=ht["damp_t"]), dict(nord=hp["nord_t"], damp_c=hp["damp_t"]),
+                              ht["tm"] == hp["tm"] and not sd, M, cen("tm"), "L%d:tm:" % k, mfx=fx, mfy=fy, mass=delp)
+            fxv, fyv = self._tp(o["vort_abs"], o, ht["vt"], hp["vt"], {}, {}, ht["vt"] == hp["vt"], M, cen("vt"), "L%d:vt:" % k)
+            new = lambda: np.full(fx.shape, np.nan, dtype=fx.dtype)
+            delp_o, pt_o = new(), new()
+            r = (1, n, 1, n)                                                    # sw_core_nlm.F90:1018-1031
+            ra = fo.V(M["rarea"], *r)
+            fo.V(delp_o, *r)[...] = fo.V(delp, *r) + ((fo.V(fx, *r) - fo.V(fx, *r, di=1)) + (fo.V(fy, *r) - fo.V(fy, *r, dj=1))) * ra
+            fo.V(pt_o, *r)[...] = (fo.V(pt, *r) * fo.V(delp, *r) + ((fo.V(gx, *r) - fo.V(gx, *r, di=1)) + (fo.V(gy, *r) - fo.V(gy, *r, dj=1))) * ra) / fo.V(delp_o, *r)
+
+            def momentum(p):                                                    # :1474-1490, :1527-1539
+                fx2 = fy2 = None
+                if p["damp_vt"] > 1.0e-5:
+                    _, fx2, fy2 = fo.del6_vt_flux(p["nord_v"], (p["damp_vt"] * self.da_min_c) ** (p["nord_v"] + 1), o["wk"], M, n)
+                return fo.d_sw_momentum(L_(x["u"]), L_(x["v"]), o["ke2"], fxv, fyv, fx2, fy2, M, n, p["damp_vt"])
+            um, vm = momentum(t)
+            if (q["nord_v"], q["damp_vt"]) != (t["nord_v"], t["damp_vt"]) and np.iscomplexobj(um):
+                ap, bp = momentum(q)
+                um, vm = np.real(um) + 1j * np.imag(ap), np.real(vm) + 1j * np.imag(bp)
+            lv.append(dict(fx=fx, fy=fy, gx=gx, gy=gy, fxv=fxv, fyv=fyv, delp_o=delp_o, pt_o=pt_o, u_m=um, v_m=vm, crx=o["crx"], cry=o["cry"]))
+            if "w" in x:                                                        # sw_core_nlm.F90:940-961, :1236-1248
+                w, (nord_w, damp_w) = L_(x["w"]), self.wpar[k]
+                dw, w_m = new(), new()
+                fo.V(dw, *r)[...] = 0.0
+                if damp_w > 1.0e-5:
+                    _, fx2, fy2 = fo.del6_vt_flux(nord_w, (damp_w * self.da_min_c) ** (nord_w + 1), w, M, n)
+                    fo.V(dw, *r)[...] = ((fo.V(fx2, *r) - fo.V(fx2, *r, di=1)) + (fo.V(fy2, *r) - fo.V(fy2, *r, dj=1))) * ra
+                gxw, gyw = self._tp(w, o, ht["vt"], hp["vt"], {}, {}, ht["vt"] == hp["vt"], M, cen("w"), "L%d:w:" % k, mfx=fx, mfy=fy)
+                fo.V(w_m, *r)[...] = (fo.V(delp, *r) * fo.V(w, *r) + ((fo.V(gxw, *r) - fo.V(gxw, *r, di=1)) + (fo.V(gyw, *r) - fo.V(gyw, *r, dj=1))) * ra) / fo.V(delp_o, *r)
+                if damp_w > 1.0e-5:
+                    fo.V(w_m, *r)[...] = fo.V(w_m, *r) + fo.V(dw, *r)
+                lv[-1].update(dw=dw, gxw=gxw, gyw=gyw, w_m=w_m)
+        if census is not None:
+            self._census = census
+        return {k: np.stack([o_[k] for o_ in lv], axis=-3) for k in lv[0]}
+
+    def census_ok(self, cen):
+        """(b) every branch of the schemes under test taken both ways somewhere, the PERT_PPM branches of the edge blocks on each of the four
+        edges; (c) no discontinuous selector within 1e-6 (relative) of its switch, anywhere: no point is left out of the comparison"""
+        for name, (fired, margin, hard, live) in cen.items():
+            if hard and not np.all(margin[live] >= 1.0e-6):
+                return False, "near a switch: " + name
+        for k in range(self.npz):
+            for f in ("dp", "tm", "vt"):
+                h = self.tr[k][f]
+                for br in BULK_BRANCHES[h]:
+                    planes = [v[0] for nm, v in cen.items() if nm.endswith(":" + br) and nm.split(":")[0] == "L%d" % k]
+                    if not (any(p.any() for p in planes) and any((~p).any() for p in planes)):
+                        return False, "never taken both ways: L%d %s" % (k, br)
+                if h in fo.MONOTONE:
+                    for side in ("west:", "east:"):
+                        for sweep in ("in_x:", "in_y:", "out_x:", "out_y:"):
+                            for br in EDGE_BRANCHES:
+                                p = cen["L%d:%s:%s%s%s" % (k, f, sweep, side, br)][0]
+                                if not (p.any() and (~p).any()):
+                                    return False, "edge block: L%d %s %s%s%s" % (k, f, sweep, side, br)
+                if f == "dp":                                                   # xtp_u / ytp_v with the level's hord_mt
+                    hm = self.par[k]["iord_t"]
+                    for br in MT_BRANCHES[hm]:
+                        for sweep in ("x:", "y:"):
+                            p = cen["L%d:mt:%s%s" % (k, sweep, br)][0]
+                            if not (p.any() and (~p).any()):
+                                return False, "xtp_u / ytp_v: L%d %s%s" % (k, sweep, br)
+                    if hm >= 8:
+                        for side in ("west:", "east:"):
+                            ps = [cen["L%d:mt:%s%sstd:al*ar<0" % (k, sweep, side)][0] for sweep in ("x:", "y:")]
+                            if not (any(p.any() for p in ps) and any((~p).any() for p in ps)):
+                                return False, "xtp_u / ytp_v edge cell: L%d %s" % (k, side)
+                if h == 7 and f == "vt":
+                    for sweep in ("in_x:", "in_y:", "out_x:", "out_y:"):
+                        ps = [v[0] for nm, v in cen.items() if nm.startswith("L%d:vt:%sedge_al>0" % (k, sweep))]
+                        if not (any(p.any() for p in ps) and any((~p).any() for p in ps)):
+                            return False, "edge clip of scheme 7: L%d %s" % (k, sweep)
+        return True, ""
+
+    def signs_ok(self, x, M, edge, ecorner):
+        if not DSw.signs_ok(self, x, M, edge, ecorner):
+            return False
+        o, n = self.apply(x, M, edge, ecorner), self.n
+        npx = n + 1
+        rows = []
+        for i in (1, 2, npx - 1, npx):                                          # both signs of c at the four flux points the edge blocks feed
+            rows += [fo.V(o["crx"], i, i, 1, n), fo.V(o["cry"], 1, n, i, i)]
+        if not all(both_signs(np.real(r)) for r in rows):
+            return False
+        ok, why = self.census_ok(self._census)
+        self.why = why
+        return ok
+
+
+class DSwTransportNh(DSwTransport):
+    """d_sw_transport on a non-hydrostatic case: w joins the inputs; its del-n damping increment dw (del6_vt_flux with the level's nord_w,
+    damp_w, the trajectory's in values and tangent alike: sw_core_tlm.F90:1713-1741), its fluxes gxw, gyw (fv_tp_2d with hord_vt and the
+    mass fluxes of delp, :1746-1764) and w_m (sw_core_nlm.F90:956-960, :1236-1248) the outputs"""
+    ins = DSwTransport.ins + ["w"]
+    outs = DSwTransport.outs + [("dw", "A"), ("gxw", "V"), ("gyw", "U"), ("w_m", "A")]
+    seeded = DSwTransport.seeded + ["w_m"]
+
+    def __init__(self, c):
+        DSwTransport.__init__(self, c)
+        o, self.wpar = c.opt, []
+        for k in range(1, c.npz + 1):                                           # model/dyn_core_nlm.F90:591-630: nord_w, damp_w
+            r = fo.level_rules(o, k, c.npz)
+            sponge = r["nord"] == 0 and not (c.npz == 1 or o.n_sponge < 0) and (k == 1 or r["d2_divg"] != min(0.20, o.d2_bg))
+            pw = (0, r["d2_divg"]) if sponge else (min(2, o.nord), o.vtdm4 if o.do_vort_damp else 0.0)
+            dy = getattr(c, "dy", None)
+            if dy is not None:
+                ip, rp = dy.level_params(k)
+                assert (ip[7], rp[2]) == pw, (k, ip, rp, pw)
+            self.wpar.append(pw)
+
+    def draw(self, c, rng):
+        T, P = DSwTransport.draw(self, c, rng)
+        shp = T["u"].shape
+        T["w"], P["w"] = noise(rng, shp, 1.0), noise(rng, shp, 0.1)
+        return T, P
+
+
+OPERATORS = {"c_sw": CSw, "one_grad_p": OneGradP, "p_grad_c": PGradC, "d_sw": DSw, "c_sw_rest": CSwRest, "d_sw_rest": DSwRest, "c_sw_rest_nh": CSwRestNh,
+             "d_sw_transport": DSwTransport, "d_sw_transport_nh": DSwTransportNh}
 # geopk outputs, and delp, pt as c_sw receives them: the corner-halo columns hold no data (the exchange leaves them alone); NaN for the
 # restatement, 1e30 for the library
 GHOST_FREE = ("pk", "gzd", "pkc", "gz", "delp", "pt", "w")
@@ -527,8 +766,24 @@ def _print_figures(label, rows):
         print("figures %s %s %s: movement %.1e error %.1e error/bound %.2f" % (label, mode, c_, a[0], a[1], a[2]))
 
 
-def check(backend, group, n, face, npz=3, adjoint_all=True, seed=0, report=None, coloured=False, adjoint_levels=None, env=None, opt=None,
-          amplify=None, adjoint_on=None, adjoint_thin=1, detune=False):
+def check(*args, env=None, **kw):
+    """_check with the switches of `env` in the environment from the creation of the instance to the last launch: the library reads some
+    when an instance is created (FV3LM_TP_FUSED, FV3LM_TP_AD_FUSED) and some at every launch (FV3LM_TP2)"""
+    import os
+    old = {k: os.environ.get(k) for k in (env or {})}
+    os.environ.update(env or {})
+    try:
+        return _check(*args, **kw)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+
+
+def _check(backend, group, n, face, npz=3, adjoint_all=True, seed=0, report=None, coloured=False, adjoint_levels=None, opt=None,
+           amplify=None, adjoint_on=None, adjoint_thin=1, detune=False, observe=None):
     """values, tangent and adjoint of one operator on one whole face; returns [(mode, output, region, movement, bound, error)].
     adjoint_all: J^T s entry by entry at every input point; otherwise at the points within four cells of a face edge on the first
     adjoint_levels levels (None: all), and four random dot products <s, J dx> = <J^T s, dx> for all the other points.
@@ -536,38 +791,39 @@ def check(backend, group, n, face, npz=3, adjoint_all=True, seed=0, report=None,
     adjoint_thin = k > 1: of the points so chosen, entry by entry only those on every k-th offset of the coloured lattice (1 in k of the
     reference's columns); the others join the dot products.
     opt: options of the case (default_options keywords); amplify: the operator's draw amplified (DSwRest: the 0.20 cap).
-    detune: library and restatement both get the metrics with every sin_sg / cos_sg plane scaled by a factor of its own (detuned)."""
-    import os
+    detune: library and restatement both get the metrics with every sin_sg / cos_sg plane scaled by a factor of its own (detuned).
+    observe: called with (case, {mode: {kernel name: launches}}) after the last launch: which forms of the group's kernels ran."""
     from common import Case
-    old = {k: os.environ.get(k) for k in (env or {})}
-    os.environ.update(env or {})                              # switches the library reads when an instance is created
-    try:
-        hook = restatement_hook(n, face)
-        if detune:
-            plain = hook
-            hook = lambda m, e, ec: (lambda r: (detuned(r[0]), r[1], r[2]))(plain(m, e, ec))
-        c = Case(nx=n, ny=n, npz=npz, n_split=2, dt=1800.0, backend=backend, face=face, oracle=False, metrics_hook=hook, **(opt or {}))
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
+    hook = restatement_hook(n, face)
+    if detune:
+        plain = hook
+        lengths = bool(getattr(OPERATORS[group], "detune_dxa", False))
+        hook = lambda m, e, ec: (lambda r: (detuned(r[0], lengths), r[1], r[2]))(plain(m, e, ec))
+    c = Case(nx=n, ny=n, npz=npz, n_split=2, dt=1800.0, backend=backend, face=face, oracle=False, metrics_hook=hook, **(opt or {}))
     op = OPERATORS[group](c)
+    ran = {}
+
+    def run_group(mode):
+        n0 = c.dy.launch_count()
+        c.dy.profile_begin()
+        c.dy.run_group(op.group, mode)
+        ran[mode] = dict({k: v[0] for k, v in c.dy.profile_end().items()}, launches=c.dy.launch_count() - n0)
     if amplify is not None:
         op.amplify = amplify
     M64, e64, ec64 = face_metrics_of(n, face, np.float64)
     ML, eL, ecL = face_metrics_of(n, face, np.longdouble)
     if detune:
-        M64 = detuned(M64)
+        M64 = detuned(M64, bool(getattr(op, "detune_dxa", False)))
         ML = {k: v.astype(np.longdouble) for k, v in M64.items()}       # the float64 numbers the library holds, exactly
+    if getattr(op, "metrics64", False):                      # the longdouble run on the float64 metrics the library holds, exactly: what
+        ML, eL, ecL = {k: v.astype(np.longdouble) for k, v in M64.items()}, e64.astype(np.longdouble), ec64.astype(np.longdouble)      # is left is rounding
     rng = np.random.default_rng(1000 * n + 10 * face + seed)
     for _ in range(50):                                      # redraw until the trajectory takes both branches everywhere, clear of zero
         T, P = op.draw(c, rng)
         if op.signs_ok(T, M64, e64, ec64):
             break
     else:
-        raise AssertionError("no trajectory with both signs on every edge row")
+        raise AssertionError("no trajectory with both signs on every edge row " + getattr(op, "why", ""))
     Tn, Pn = _ghost_fill(c, T, np.nan), _ghost_fill(c, P, np.nan)
     rects, rows = G.rects(c), []
     composed = list(getattr(op, "composed", []))
@@ -580,6 +836,8 @@ def check(backend, group, n, face, npz=3, adjoint_all=True, seed=0, report=None,
     S = lambda a, o: a[lv[o]]                                 # the levels on which the reference forms the output
     L = lambda d: {k: v.astype(np.longdouble) for k, v in d.items()}
     ref = _tangent(op, L(Tn), L(Pn), ML, eL, ecL, np.longdouble)
+    census = getattr(op, "_census", None)                     # the branches the longdouble run took (DSwTransport)
+    moved = lambda r, d: {k: ulp_move(r, v) for k, v in d.items()}
     # ---- values and tangent
     fixed = op.fixed(c)
     for k, v in fixed.items():
@@ -587,15 +845,18 @@ def check(backend, group, n, face, npz=3, adjoint_all=True, seed=0, report=None,
     Tg, Pg = _ghost_fill(c, T, 1.0e30), _ghost_fill(c, P, 1.0e30)
     for k in op.ins:
         c.dy.put(k, Tg[k][None], 0); c.dy.put(k, Pg[k][None], 1)
-    c.dy.run_group(op.group, TL)
+    run_group(TL)
     got = {o: (c.dy.get(o, 0)[0], c.dy.get(o, 1)[0]) for o, _ in op.outs + composed}
     if composed:                                             # the product's vorticity fluxes as data of the restated last statements
         fl = {k: (c.dy.get(k, 0)[0], c.dy.get(k, 1)[0]) for k in ("fxv", "fyv")}
         ref.update(_compose(op, L(Tn), L(Pn), fl, ML, eL, ecL, np.longdouble))
     move = {}
     for d in range(3):
-        Td, Pd = {k: ulp_move(rng, v) for k, v in Tn.items()}, {k: ulp_move(rng, v) for k, v in Pn.items()}
+        Td, Pd = moved(rng, Tn), {k: ulp_move(rng, v) for k, v in Pn.items()}
         r64 = _tangent(op, Td, Pd, M64, e64, ec64, np.float64)
+        if census is not None:                                # a flipped branch must not inflate a bound
+            for nm, (fired, _, _, _) in census.items():
+                assert np.array_equal(fired, op._census[nm][0]), ("a moved draw left the reference's branch", nm)
         if composed:
             r64.update(_compose(op, Td, Pd, fl, M64, e64, ec64, np.float64))
         for o, rk in op.outs + composed:
@@ -608,7 +869,7 @@ def check(backend, group, n, face, npz=3, adjoint_all=True, seed=0, report=None,
                 mv = move[(tag, o, reg)]
                 rows.append((tag, o, reg, mv, max(8 * mv, FLOOR), e))
     # ---- adjoint: seeds on the compared outputs only
-    seeded = [o for o, _ in op.outs]
+    seeded = list(getattr(op, "seeded", [o for o, _ in op.outs]))      # an operator's true outputs, where it also compares work fields
     seeds = {}
     for o in seeded:
         on = np.zeros((c.dy.levels(o), 1, 1), bool)
@@ -618,14 +879,14 @@ def check(backend, group, n, face, npz=3, adjoint_all=True, seed=0, report=None,
         c.dy.put(k, v[None], 0)
     for k in op.ins:
         c.dy.put(k, Tg[k][None], 0)
-    c.dy.run_group(op.group, NL)
+    run_group(NL)
     c.dy.zero_work_adjoint()
     _, _, gins, gouts = G.table(c)[op.group]
     for k in set(gins) | set(op.ins) | {o for o, _ in gouts if o}:
         c.dy.put(k, np.zeros(c.dy.shape(k)), 1)
     for o, s in seeds.items():
         c.dy.put(o, s[None], 1)
-    c.dy.run_group(op.group, AD)
+    run_group(AD)
     gota = {k: c.dy.get(k, 1)[0] for k in op.ins}
     ne = near_edge(n)
     if adjoint_on is not None:
@@ -647,7 +908,7 @@ def check(backend, group, n, face, npz=3, adjoint_all=True, seed=0, report=None,
     refa = _adjoint(op, L(Tn), L(seeds), ML, eL, ecL, np.longdouble, pts, coloured=coloured)
     mva = {}
     for d in range(3):
-        r64 = _adjoint(op, {k: ulp_move(rng, v) for k, v in Tn.items()}, seeds, M64, e64, ec64, np.float64, pts, coloured=coloured)
+        r64 = _adjoint(op, moved(rng, Tn), seeds, M64, e64, ec64, np.float64, pts, coloured=coloured)
         for k in op.ins:
             for reg, e in (region_errors(r64[k][nl[k]], refa[k][nl[k]], pts[k][nl[k][0]], n, rects["full"]).items() if nl[k] else ()):
                 mva[(k, reg)] = max(mva.get((k, reg), 0.0), e)
@@ -670,6 +931,8 @@ def check(backend, group, n, face, npz=3, adjoint_all=True, seed=0, report=None,
     _print_figures("%s %s C%d face %d" % (backend, group, n, face), rows)
     bad = [r for r in rows if not r[5] <= r[4]]
     assert not bad, (group, n, face, bad[:8])
+    if observe is not None:
+        observe(c, ran)
     return rows
 
 
@@ -683,6 +946,55 @@ DSW_REST_C70 = dict(npz=2, opt=dict(n_sponge_pert=2, d2_bg_k1=0.02, d2_bg_k2=0.0
 _SPLIT = dict(split_damp=1, nord_pert=1, n_sponge_pert=1, dddmp=0.35, dddmp_pert=0.2, d4_bg=0.11, d4_bg_pert=0.15, d2_bg=0.02, d2_bg_pert=0.015,
               vtdm4=0.03, vtdm4_pert=0.0005, d2_bg_k1=0.18, d2_bg_k2=0.0)
 DSW_SPLIT = {nord: dict(npz=2, opt=dict(_SPLIT, nord=nord), forms=[(0, 0, 2, 0), (nord, 1, 2, 2)]) for nord in (2, 3)}
+
+
+def transport_opt(h, pert=2, **more):
+    """options of a d_sw_transport case: the trajectory scheme h for delp, pt and the vorticity over the perturbation scheme `pert`, the
+    sponge levels' own schemes (hord_*_ks_*) switched off so that both levels run them"""
+    o = dict(hord_ks_traj=0, hord_ks_pert=0, hord_dp=h, hord_tm=h, hord_vt=h, hord_dp_pert=pert, hord_tm_pert=pert, hord_vt_pert=pert)
+    if h != 333:                                                 # the nonlinear xtp_u / ytp_v hold no scheme 333 (sw_core_tlm.F90:4396-4406)
+        o.update(hord_mt=h, hord_mt_pert=pert if pert != 333 else 2)
+    o.update(more)
+    return o
+
+
+# level 2 off the trajectory's sponge rules: nord_v = nord_t = 1 with a coefficient well above the 1e-4 threshold, so that DELN_FLUX runs
+# its nord = 1 loop without (delp) and with (pt) the mass, beside the nord_v = 0 form of level 1
+TRANSPORT_DAMPED = dict(d2_bg_k2=0.0, d2_bg_k2_pert=0.0, vtdm4=0.03, vtdm4_pert=0.03)
+
+
+def transport_forms(env):
+    """observe of check(): the device forms of fv_tp_2d that the switches in `env` select are the ones that ran, from the names of the
+    hand-written launches in the three run_group calls, the launch counts (the staged form of one fv_tp_2d is seven launches and its
+    strips; the group holds three) and the library's count of launches in the wavefront layout (tp2.h, whose profile names are tpfused.h's)"""
+    env = env or {}
+
+    def observe(c, ran):
+        staged = lambda m: not any(k.startswith(("TpFused", "TpAd", "TpOuter")) for k in ran[m]) and ran[m]["launches"] >= 3 * 7
+        tp2 = c.dy.tp2_launch_count()
+        if env.get("FV3LM_TP_FUSED") == "0":                                    # the staged stages in every mode
+            assert staged(TL) and staged(NL) and staged(AD) and tp2 == 0, (ran, tp2)
+            return
+        assert ran[TL].get("TpFused.tl", 0) > 0 and ran[NL].get("TpFused.nl", 0) > 0 and not staged(TL) and not staged(NL), ran
+        if env.get("FV3LM_TP2") == "0":                                         # tpfused.h's own tangent / nonlinear form
+            assert tp2 == 0, tp2
+        else:
+            assert tp2 > 0, tp2
+        if env.get("FV3LM_TP_AD_FUSED") == "0":                                 # the staged adjoint
+            assert staged(AD) and "TpAd.ad" not in ran[AD] and "TpOuter.ad" not in ran[AD], ran[AD]
+        else:
+            assert ran[AD].get("TpAd.ad", 0) > 0 and not staged(AD), ran[AD]
+    return observe
+
+
+def check_transport(backend, n, face, h, pert=2, more=None, **kw):
+    """check() of d_sw_transport, npz = 2 (3 on a non-hydrostatic case, the least the library takes): values and tangent at every point; the adjoint entry by entry (one perturbed point per column of
+    the restated Jacobian: two +-3 sweeps, the Courant stencil and copy_corners reach too far for a lattice on these faces) within four
+    cells of an edge on the first level, thinned, and four dot products for the rest"""
+    kw.setdefault("adjoint_thin", 4)
+    kw.setdefault("observe", transport_forms(kw.get("env")))
+    group = "d_sw_transport_nh" if (more or {}).get("hydrostatic", 1) == 0 else "d_sw_transport"
+    return check(backend, group, n, face, npz=3 if group.endswith("nh") else 2, opt=transport_opt(h, pert, **(more or {})), adjoint_all=False, adjoint_levels=1, **kw)
 
 
 def check_d_sw_rest(backend, n, face, case=None, **kw):
@@ -706,7 +1018,7 @@ class _FaceShape:
     """what the operator classes and groups.py read of a case, for a whole face of the cube behind a tiled CubeCase"""
     def __init__(self, c):
         self.nx = self.ny = c.n
-        self.npz, self.dt_ac, self.opt, self.face, self.da_min_c = c.npz, c.dt_ac, c.opt, "cube", c.da_min_c
+        self.npz, self.dt_ac, self.opt, self.face, self.da_min_c, self.da_min = c.npz, c.dt_ac, c.opt, "cube", c.da_min_c, c.da_min
 
     def rect(self, i0, i1, j0, j1):
         return (Ellipsis, slice(j0 + 2, j1 + 3), slice(i0 + 2, i1 + 3))
@@ -723,11 +1035,17 @@ def check_layout(backend, group, n=16, layout=2, npz=3, report=None, opt=None):
     fc = _FaceShape(c)
     op = OPERATORS[group](fc)
     lv = {o: (op.levels_of(o) if hasattr(op, "levels_of") and op.levels_of(o) is not None else slice(None)) for o, _ in op.outs}
+
+    def at(f):                                                   # the operator on face f (DSwTransport: the face's data fields)
+        op.face = f
+        return op
     nt, tl = c.nt, c.tiles
     W = lambda a: cube.tile_window(a, tl, nt)                    # [6, ..., pj, pj] -> [ntile, ..., nt+7, nt+7]
     rng = np.random.default_rng(7 * n + layout)
     Ms = [face_metrics_of(n, f, np.float64) for f in range(6)]
     MLs = [face_metrics_of(n, f, np.longdouble) for f in range(6)]
+    if getattr(op, "metrics64", False):                          # as in check(): the float64 metrics the library holds, exactly
+        MLs = [({k: v.astype(np.longdouble) for k, v in m.items()}, e.astype(np.longdouble), ec.astype(np.longdouble)) for m, e, ec in Ms]
     T6, P6 = [], []
     for f in range(6):
         op.face = f                                              # (DSwRest: the face whose divgd halo and metrics the draw takes)
@@ -741,7 +1059,7 @@ def check_layout(backend, group, n=16, layout=2, npz=3, report=None, opt=None):
     stack = lambda d6, fill: {k: np.stack([_ghost_fill(fc, d, fill)[k] for d in d6]) for k in d6[0]}
     L = lambda d: {k: v.astype(np.longdouble) for k, v in d.items()}
     Tn, Pn = [_ghost_fill(fc, d, np.nan) for d in T6], [_ghost_fill(fc, d, np.nan) for d in P6]
-    ref = [_tangent(op, L(Tn[f]), L(Pn[f]), *MLs[f], np.longdouble) for f in range(6)]
+    ref = [_tangent(at(f), L(Tn[f]), L(Pn[f]), *MLs[f], np.longdouble) for f in range(6)]
     refw = {o: [W(np.stack([ref[f][o][w] for f in range(6)])) for w in (0, 1)] for o, _ in op.outs}
     # masks per tile: the tile's own rect minus the windows of the points that hold no value on the face
     rects = G.rects(c)
@@ -758,7 +1076,7 @@ def check_layout(backend, group, n=16, layout=2, npz=3, report=None, opt=None):
         if k in op.ins:
             continue
         fixed[k] = c.traj[k] if k in ("delp", "pt") else np.zeros(c.dy.shape(k)) if k in ("mfx", "mfy", "cx", "cy") else \
-            noise(frng, c.dy.shape(k), 1e-6 if k == "divgd" else 5.0)
+            W(np.stack([d[k] for d in op.fix6])) if hasattr(op, "fix6") else noise(frng, c.dy.shape(k), 1e-6 if k == "divgd" else 5.0)
     for k, v in fixed.items():
         c.dy.put(k, v, 0); c.dy.put(k, np.zeros_like(v), 1)
     Tg = {k: W(v) for k, v in stack(T6, 1.0e30).items()}; Pg = {k: W(v) for k, v in stack(P6, 1.0e30).items()}
@@ -768,7 +1086,7 @@ def check_layout(backend, group, n=16, layout=2, npz=3, report=None, opt=None):
     got = {o: (c.dy.get(o, 0), c.dy.get(o, 1)) for o, _ in op.outs}
     move, rows = {}, []
     for d in range(3):
-        r64 = [_tangent(op, {k: ulp_move(rng, v) for k, v in Tn[f].items()}, {k: ulp_move(rng, v) for k, v in Pn[f].items()}, *Ms[f], np.float64)
+        r64 = [_tangent(at(f), {k: ulp_move(rng, v) for k, v in Tn[f].items()}, {k: ulp_move(rng, v) for k, v in Pn[f].items()}, *Ms[f], np.float64)
                for f in range(6)]
         for o, rk in op.outs:
             for w, tag in ((0, "values"), (1, "tangent")):
@@ -786,7 +1104,8 @@ def check_layout(backend, group, n=16, layout=2, npz=3, report=None, opt=None):
         rows.append(k + (move[k], max(8 * move[k], FLOOR), e))
     # ---- adjoint: seeds on the compared outputs of every tile
     seeds = {}
-    for o, _ in op.outs:
+    seeded = list(getattr(op, "seeded", [o for o, _ in op.outs]))
+    for o in seeded:
         on = np.zeros((1, got[o][0].shape[1], 1, 1), bool)
         on[:, lv[o]] = True
         seeds[o] = np.where(masks[o][:, None] & on, rng.standard_normal(got[o][0].shape), 0.0)
@@ -811,9 +1130,9 @@ def check_layout(backend, group, n=16, layout=2, npz=3, report=None, opt=None):
                 if k in dx:
                     dx[k][:, g6] = 0.0
             dx6.append(dx)
-        jdx = [_tangent(op, L(Tn[f]), L(dx6[f]), *MLs[f], np.longdouble) for f in range(6)]
+        jdx = [_tangent(at(f), L(Tn[f]), L(dx6[f]), *MLs[f], np.longdouble) for f in range(6)]
         lhs = scale = 0.0
-        for o, _ in op.outs:
+        for o in seeded:
             jw = W(np.stack([jdx[f][o][1] for f in range(6)]))
             term = np.where(seeds[o] != 0, jw, 0) * seeds[o]
             lhs += float(np.sum(term)); scale += float(np.sum(np.abs(term)))

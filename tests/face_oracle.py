@@ -923,57 +923,156 @@ def _T(a):
     return np.swapaxes(a, -1, -2)
 
 
-def xtp_u(c, u, dx, rdx, n, iord):
-    """xtp_u (sw_core_nlm.F90:1970-2309) for iord = 1 and 2, whole face: the flux form of u along x at the corner points 1..npx, 1..npy
-    under the Courant number c, with the one-sided edge values next to a face edge and none at all on the rows j = 1, npy"""
+def xtp_u(c, u, dx, rdx, n, iord, cen=None, tag=""):
+    """XTP_U, the nonlinear routine inside model_tlmadm/sw_core_tlm.F90 (:4310-5042; iord = 1, 2 as sw_core_nlm.F90:1970-2309), iord = 1 .. 13,
+    whole face: the flux form of u along x at the corner points 1..npx, 1..npy under the Courant number c, with the one-sided edge values
+    next to a face edge and none at all on the rows j = 1, npy.  is3 = 3, ie3 = npx - 3 (:4385-4394).  Not XPPM: cfl = c rdx of the upwind
+    cell; scheme 7 is scheme 6 (no clip of al); 9 limits everywhere and 10 tests |dm(i)| before its neighbours (:4785-4806); 11 .. 13 are
+    unlimited (:4890-4896); the two-sided edge value is not clamped; PERT_PPM runs on the cells 2 and npx - 2 alone (:4925, :4951)."""
     npx = npy = n + 1
-    flux = np.full(np.broadcast(c, u).shape, np.nan, dtype=np.result_type(c, u))
+    shape, dt_ = np.broadcast(c, u).shape, np.result_type(c, u)
+    flux = np.full(shape, np.nan, dtype=dt_)
     r = (1, npx, 1, npy)
-    up = _pos(V(c, *r))
-    if iord == 1:                                                       # :2000-2010
+    if cen is None:
+        up = _pos(V(c, *r))
+    else:
+        up = _lt(cen, tag + "c>0", np.zeros(V(c, *r).shape), V(c, *r), hard=True, scale=np.nanmax(np.abs(np.real(V(c, *r)))))
+    if iord == 1:                                                       # :4396-4405
         V(flux, *r)[...] = np.where(up, V(u, *r, di=-1), V(u, *r))
         return flux
-    assert iord == 2
-    al, bl, br = (np.full(u.shape, np.nan, dtype=u.dtype) for _ in range(3))
-    a = (3, npx - 2, 1, npy)                                            # is3 = 3, ie3 = npx - 3: al on is3 .. ie3 + 1  :2017-2023
-    V(al, *a)[...] = P1 * (V(u, *a, di=-1) + V(u, *a)) + P2 * (V(u, *a, di=-2) + V(u, *a, di=1))
-    b = (3, npx - 3, 1, npy)
-    V(bl, *b)[...] = V(al, *b) - V(u, *b); V(br, *b)[...] = V(al, *b, di=1) - V(u, *b)
+    assert 2 <= iord <= 13, iord
+    al, bl, br = (np.full(shape, np.nan, dtype=dt_) for _ in range(3))
     col = lambda f, i, j0=1, j1=npy: V(f, i, i, j0, j1)
     U = lambda i, j0=1, j1=npy: col(u, i, j0, j1)
     D = lambda i, j0=1, j1=npy: col(dx, i, j0, j1)
-    xt = C3 * U(1) + C2 * U(2) + C1 * U(3)                              # west :2026-2044
-    col(br, 1)[...] = xt - U(1); col(bl, 2)[...] = xt - U(2); col(br, 2)[...] = col(al, 3) - U(2)
-    for j in (1, npy):
-        for (f, i) in ((bl, 0), (br, 0), (bl, 1), (br, 1)):
-            col(f, i, j, j)[...] = 0.0
     jj = (2, npy - 1)
-    col(bl, 0, *jj)[...] = C1 * U(-2, *jj) + C2 * U(-1, *jj) + C3 * U(0, *jj) - U(0, *jj)
-    xt = 0.5 * (((2 * D(0, *jj) + D(-1, *jj)) * U(0, *jj) - D(0, *jj) * U(-1, *jj)) / (D(0, *jj) + D(-1, *jj))
-                + ((2 * D(1, *jj) + D(2, *jj)) * U(1, *jj) - D(1, *jj) * U(2, *jj)) / (D(1, *jj) + D(2, *jj)))
+    x = npx
+    finite = np.isfinite(np.real(u))
+    qmax = np.max(np.abs(np.real(u[finite]))) if finite.any() else 1.0
+
+    def two_sided(e):                                                   # :4433-4435, :4456-4459, :4917-4921, :4943-4947
+        return 0.5 * (((2 * D(e - 1, *jj) + D(e - 2, *jj)) * U(e - 1, *jj) - D(e - 1, *jj) * U(e - 2, *jj)) / (D(e - 1, *jj) + D(e - 2, *jj))
+                      + ((2 * D(e, *jj) + D(e + 1, *jj)) * U(e, *jj) - D(e, *jj) * U(e + 1, *jj)) / (D(e, *jj) + D(e + 1, *jj)))
+
+    def corner_rows():                                                  # :4422-4430, :4446-4454, :4906-4914, :4932-4940
+        for j in (1, npy):
+            for (f, i) in ((bl, 0), (br, 0), (bl, 1), (br, 1), (bl, x - 1), (br, x - 1), (bl, x), (br, x)):
+                col(f, i, j, j)[...] = 0.0
+    cm, cp = V(c, *r) * V(rdx, *r, di=-1), V(c, *r) * V(rdx, *r)        # cfl of either branch
+    if iord < 8:
+        a = (3, npx - 2, 1, npy)                                        # al on is3 .. ie3 + 1  :4409-4415
+        V(al, *a)[...] = P1 * (V(u, *a, di=-1) + V(u, *a)) + P2 * (V(u, *a, di=-2) + V(u, *a, di=1))
+        b = (3, npx - 3, 1, npy)
+        V(bl, *b)[...] = V(al, *b) - V(u, *b); V(br, *b)[...] = V(al, *b, di=1) - V(u, *b)
+        xt = C3 * U(1) + C2 * U(2) + C1 * U(3)                          # west :4417-4439
+        col(br, 1)[...] = xt - U(1); col(bl, 2)[...] = xt - U(2); col(br, 2)[...] = col(al, 3) - U(2)
+        col(bl, 0, *jj)[...] = C1 * U(-2, *jj) + C2 * U(-1, *jj) + C3 * U(0, *jj) - U(0, *jj)
+        xt = two_sided(1)
+        col(br, 0, *jj)[...] = xt - U(0, *jj); col(bl, 1, *jj)[...] = xt - U(1, *jj)
+        col(bl, x - 2)[...] = col(al, x - 2) - U(x - 2)                 # east :4441-4465
+        xt = C1 * U(x - 3) + C2 * U(x - 2) + C3 * U(x - 1)
+        col(br, x - 2)[...] = xt - U(x - 2); col(bl, x - 1)[...] = xt - U(x - 1)
+        xt = two_sided(x)
+        col(br, x - 1, *jj)[...] = xt - U(x - 1, *jj); col(bl, x, *jj)[...] = xt - U(x, *jj)
+        col(br, x, *jj)[...] = C3 * U(x, *jj) + C2 * U(x + 1, *jj) + C1 * U(x + 2, *jj) - U(x, *jj)
+        corner_rows()
+        b0 = bl + br                                                    # :4468-4470
+        blm, brm, b0m, bl0, br0, b00 = V(bl, *r, di=-1), V(br, *r, di=-1), V(b0, *r, di=-1), V(bl, *r), V(br, *r), V(b0, *r)
+        um, u0 = V(u, *r, di=-1), V(u, *r)
+        if iord == 2:                                                   # :4471-4482
+            V(flux, *r)[...] = np.where(up, um + (1 - cm) * (brm - cm * b0m), u0 + (1 + cp) * (bl0 + cp * b00))
+            return flux
+        B = (0, npx, 1, npy)                                            # is - 1 .. ie + 1
+        s5f, s6f = np.zeros(shape, bool), np.zeros(shape, bool)
+        if iord in (3, 4):                                              # :4484-4497, :4552-4566
+            x0, xd = _abs(V(b0, *B)), _abs(V(bl, *B) - V(br, *B))
+            V(s5f, *B)[...] = _lt(cen, tag + "smt5", x0, xd, hard=True, qs=qmax)
+            V(s6f, *B)[...] = _lt(cen, tag + "smt6", 3.0 * x0, xd, hard=True, qs=qmax)
+        elif iord == 5:                                                 # :4585-4588
+            V(s5f, *B)[...] = _lt(cen, tag + "bl*br<0", V(bl, *B) * V(br, *B), 0.0, hard=True,
+                                  scale=np.maximum(np.abs(np.real(V(bl, *B))), np.abs(np.real(V(br, *B)))) ** 2,
+                                  live=np.minimum(np.abs(np.real(V(bl, *B))), np.abs(np.real(V(br, *B)))) > 1.0e-9 * qmax)
+        else:                                                           # 6, 7  :4590-4602
+            V(s5f, *B)[...] = _lt(cen, tag + "|3b0|<|bl-br|", _abs(3.0 * V(b0, *B)), _abs(V(bl, *B) - V(br, *B)), hard=True, qs=qmax)
+        s5m, s5, s6m, s6 = V(s5f, *r, di=-1), V(s5f, *r), V(s6f, *r, di=-1), V(s6f, *r)
+        if iord == 3:                                                   # :4498-4549
+            lin_u = _sign(_mn(_abs(blm), _abs(brm)), brm)
+            lin_d = _sign(_mn(_abs(bl0), _abs(br0)), bl0)
+            fu = np.where(s6m | s5, brm - cm * b0m, np.where(s5m, lin_u, 0.0))
+            fd = np.where(s6 | s5m, bl0 + cp * b00, np.where(s5, lin_d, 0.0))
+            if cen is not None:
+                two = np.where(up, ~(s6m | s5) & s5m, ~(s6 | s5m) & s5)
+                cen[tag + "piecewise_linear"] = (two, np.ones(two.shape), False, np.ones(two.shape, bool))
+            V(flux, *r)[...] = np.where(up, um + (1 - cm) * fu, u0 + (1 + cp) * fd)
+        elif iord == 4:                                                 # :4567-4582
+            V(flux, *r)[...] = np.where(up, um + np.where(s6m | s5, (1 - cm) * (brm - cm * b0m), 0.0), u0 + np.where(s6 | s5m, (1 + cp) * (bl0 + cp * b00), 0.0))
+        else:                                                           # :4605-4616
+            fx0 = np.where(up, (1 - cm) * (brm - cm * b0m), (1 + cp) * (bl0 + cp * b00))
+            V(flux, *r)[...] = np.where(up, um, u0) + np.where(s5m | s5, fx0, 0.0)
+        return flux
+    dm, dq = (np.full(shape, np.nan, dtype=dt_) for _ in range(2))
+    Dm = (-1, npx + 1, 1, npy)                                          # is - 2 .. ie + 2  :4622-4665
+    W = lambda rr, d=0: V(u, *rr, di=d)
+    xt = 0.25 * (W(Dm, 1) - W(Dm, -1))
+    hi = _mx(_mx(W(Dm, -1), W(Dm)), W(Dm, 1)) - W(Dm)
+    lo = W(Dm) - _mn(_mn(W(Dm, -1), W(Dm)), W(Dm, 1))
+    V(dm, *Dm)[...] = _sign(_mn(_mn(_abs(xt), hi), lo), xt)
+    Dq = (-2, npx + 1, 1, npy)                                          # is - 3 .. ie + 2  :4666-4668
+    V(dq, *Dq)[...] = W(Dq, 1) - W(Dq)
+    A = (3, npx - 2, 1, npy)                                            # :4670-4672
+    V(al, *A)[...] = 0.5 * (W(A, -1) + W(A)) + R3 * (V(dm, *A, di=-1) - V(dm, *A))
+    I = (3, npx - 3, 1, npy)
+    b_l, b_r = V(al, *I) - W(I), V(al, *I, di=1) - W(I)
+
+    def constrained():                                                  # :4712-4779, :4819-4886
+        pmp_1 = -(2.0 * V(dq, *I))
+        lac_1 = pmp_1 + 1.5 * V(dq, *I, di=1)
+        l_new = _mn(_mx(_mx(0.0 * pmp_1, pmp_1), lac_1), _mx(b_l, _mn(_mn(0.0 * pmp_1, pmp_1), lac_1)))
+        pmp_2 = 2.0 * V(dq, *I, di=-1)
+        lac_2 = pmp_2 - 1.5 * V(dq, *I, di=-2)
+        r_new = _mn(_mx(_mx(0.0 * pmp_2, pmp_2), lac_2), _mx(b_r, _mn(_mn(0.0 * pmp_2, pmp_2), lac_2)))
+        return l_new, r_new
+    if iord == 8:                                                       # :4674-4709
+        xt = 2.0 * V(dm, *I)
+        V(bl, *I)[...] = -_sign(_mn(_abs(xt), _abs(b_l)), xt)
+        V(br, *I)[...] = _sign(_mn(_abs(xt), _abs(b_r)), xt)
+    elif iord == 9:                                                     # :4710-4780
+        V(bl, *I)[...], V(br, *I)[...] = constrained()
+    elif iord == 10:                                                    # :4781-4889
+        z0 = _lt(cen, tag + "|dm|<near_zero", _abs(V(dm, *I)), NEAR_ZERO, hard=True, qs=qmax)
+        z1 = _lt(cen, tag + "near_zero", _abs(V(dm, *I, di=-1)) + _abs(V(dm, *I, di=1)), NEAR_ZERO, hard=True, qs=qmax)
+        huynh = _lt(cen, tag + "|3b0|>|bl-br|", _abs(b_l - b_r), _abs(3.0 * (b_l + b_r)), qs=qmax)
+        l_new, r_new = constrained()
+        V(bl, *I)[...] = np.where(z0, np.where(z1, 0.0, b_l), np.where(huynh, l_new, b_l))
+        V(br, *I)[...] = np.where(z0, np.where(z1, 0.0, b_r), np.where(huynh, r_new, b_r))
+    else:                                                               # 11, 12, 13  :4890-4896
+        V(bl, *I)[...], V(br, *I)[...] = b_l, b_r
+    col(br, 2)[...] = col(al, 3) - U(2)                                 # west :4901-4926
+    xt = S15 * U(1) + S11 * U(2) - S14 * col(dm, 2)
+    col(bl, 2)[...] = xt - U(2); col(br, 1)[...] = xt - U(1)
+    col(bl, 0, *jj)[...] = S14 * col(dm, -1, *jj) - S11 * col(dq, -1, *jj)
+    xt = two_sided(1)
     col(br, 0, *jj)[...] = xt - U(0, *jj); col(bl, 1, *jj)[...] = xt - U(1, *jj)
-    x = npx                                                             # east :2045-2063
-    col(bl, x - 2)[...] = col(al, x - 2) - U(x - 2)
-    xt = C1 * U(x - 3) + C2 * U(x - 2) + C3 * U(x - 1)
+    col(bl, 2)[...], col(br, 2)[...] = pert_ppm(U(2), col(bl, 2).copy(), col(br, 2).copy(), 1, cen, tag + "west:", qmax)
+    col(bl, x - 2)[...] = col(al, x - 2) - U(x - 2)                     # east :4927-4953
+    xt = S15 * U(x - 1) + S11 * U(x - 2) + S14 * col(dm, x - 2)
     col(br, x - 2)[...] = xt - U(x - 2); col(bl, x - 1)[...] = xt - U(x - 1)
-    for j in (1, npy):
-        for (f, i) in ((bl, x - 1), (br, x - 1), (bl, x), (br, x)):
-            col(f, i, j, j)[...] = 0.0
-    xt = 0.5 * (((2 * D(x - 1, *jj) + D(x - 2, *jj)) * U(x - 1, *jj) - D(x - 1, *jj) * U(x - 2, *jj)) / (D(x - 1, *jj) + D(x - 2, *jj))
-                + ((2 * D(x, *jj) + D(x + 1, *jj)) * U(x, *jj) - D(x, *jj) * U(x + 1, *jj)) / (D(x, *jj) + D(x + 1, *jj)))
+    col(br, x, *jj)[...] = S11 * col(dq, x, *jj) - S14 * col(dm, x + 1, *jj)
+    xt = two_sided(x)
     col(br, x - 1, *jj)[...] = xt - U(x - 1, *jj); col(bl, x, *jj)[...] = xt - U(x, *jj)
-    col(br, x, *jj)[...] = C3 * U(x, *jj) + C2 * U(x + 1, *jj) + C1 * U(x + 2, *jj) - U(x, *jj)
-    b0 = bl + br                                                        # :2066-2068
-    cm, cp = V(c, *r) * V(rdx, *r, di=-1), V(c, *r) * V(rdx, *r)        # :2070-2081
-    V(flux, *r)[...] = np.where(up, V(u, *r, di=-1) + (1 - cm) * (V(br, *r, di=-1) - cm * V(b0, *r, di=-1)),
-                                V(u, *r) + (1 + cp) * (V(bl, *r) + cp * V(b0, *r)))
+    col(bl, x - 2)[...], col(br, x - 2)[...] = pert_ppm(U(x - 2), col(bl, x - 2).copy(), col(br, x - 2).copy(), 1, cen, tag + "east:", qmax)
+    corner_rows()
+    blm, brm, bl0, br0 = V(bl, *r, di=-1), V(br, *r, di=-1), V(bl, *r), V(br, *r)      # :5030-5039
+    V(flux, *r)[...] = np.where(up, V(u, *r, di=-1) + (1 - cm) * (brm - cm * (blm + brm)), V(u, *r) + (1 + cp) * (bl0 + cp * (bl0 + br0)))
     return flux
 
 
-def ytp_v(c, v, dy, rdy, n, jord):
-    """ytp_v (sw_core_nlm.F90:2312-2738) for jord = 1 and 2.  Statement for statement the transpose of xtp_u (v, dy, rdy along j; the zeroed
-    edge values at the columns i = 1, npx): evaluated as such on the transposed planes."""
-    return _T(xtp_u(_T(c), _T(v), _T(dy), _T(rdy), n, jord))
+def ytp_v(c, v, dy, rdy, n, jord, cen=None, tag=""):
+    """YTP_V (sw_core_tlm.F90:5043-5865; jord = 1, 2 as sw_core_nlm.F90:2312-2738).  Read against XTP_U block by block: js3 / je3 :5118-5133
+    = :4381-4395; al, bl, br and the edge values of 2 .. 7 :5143-5207 = :4408-4467; the schemes 2 .. 7 :5208-5358 = :4468-4617; dm, dq, al and
+    the limiters of 8, 9, 10, 11 .. 13 :5361-5640 = :4620-4896; the edge blocks :5641-5700 = :4897-4953; the flux :5850-5863 = :5030-5039: the
+    transpose of xtp_u (v, dy, rdy along j; the zeroed edge values at the columns i = 1, npx), evaluated as such on the transposed planes."""
+    return _T(xtp_u(_T(c), _T(v), _T(dy), _T(rdy), n, jord, cen, tag))
 
 
 def del6_vt_flux(nord, damp, q, M, n):
@@ -1069,7 +1168,17 @@ def d_sw_rest_level(u, v, uc, vc, ua, va, divgd, M, edge, ecorner, n, dt, da_min
     for i in (1, npx):
         r = (i, i, 2, npy - 1)
         V(vb, *r)[...] = dt4 * (-V(vt, *r, di=-2) + 3.0 * (V(vt, *r, di=-1) + V(vt, *r)) - V(vt, *r, di=1))
-    ke = vb * ytp_v(vb, v, M["dy"], M["rdy"], n, p["iord"])               # :1108-1115
+    cen, tag = p.get("cen"), p.get("tag", "")
+
+    def flux_of(fn, c, w, d, rd, sweep):
+        """the flux VALUES with the trajectory's scheme iord_t, the tangent with the perturbation's iord: the reference calls xtp_u / ytp_v
+        after the tangent routine and forms ke_tl from the new values (sw_core_tlm.F90:1987-2006, :2059-2077)"""
+        it = p.get("iord_t", p["iord"])
+        a = fn(c, w, d, rd, n, it, cen, tag + sweep)
+        if it == p["iord"] or not np.iscomplexobj(a):
+            return a
+        return np.real(a) + 1j * np.imag(fn(c, w, d, rd, n, p["iord"]))
+    ke = vb * flux_of(ytp_v, vb, v, M["dy"], M["rdy"], "y:")             # :1108-1115
     # ---- ub :1131-1154
     for i in (1, npx):
         r = (i, i, 1, npy)
@@ -1079,7 +1188,7 @@ def d_sw_rest_level(u, v, uc, vc, ua, va, divgd, M, edge, ecorner, n, dt, da_min
     for j in (1, npy):
         r = (2, npx - 1, j, j)
         V(ub, *r)[...] = dt4 * (-V(ut, *r, dj=-2) + 3.0 * (V(ut, *r, dj=-1) + V(ut, *r)) - V(ut, *r, dj=1))
-    ke = 0.5 * (ke + ub * xtp_u(ub, u, M["dx"], M["rdx"], n, p["iord"]))  # :1165-1172
+    ke = 0.5 * (ke + ub * flux_of(xtp_u, ub, u, M["dx"], M["rdx"], "x:"))  # :1165-1172
     dt6 = dt / 6.0                                                      # :1178-1201
     x, y = npx, npy
     ke[..., 1 + NG - 1, 1 + NG - 1] = dt6 * ((P(ut, 1, 1) + P(ut, 1, 0)) * P(u, 1, 1) + (P(vt, 1, 1) + P(vt, 0, 1)) * P(v, 1, 1) + (P(ut, 1, 1) + P(vt, 1, 1)) * P(u, 0, 1))
@@ -1178,3 +1287,313 @@ def d_sw_momentum(u, v, ke2, fxv, fyv, fx2, fy2, M, n, damp_vt):
     if damp_vt > 1.0e-5:
         V(vo, *r)[...] = V(vo, *r) - V(fx2, *r)
     return uo, vo
+
+
+# =========================================================================================================== fv_tp_2d
+# Restated from the NONLINEAR routines inside model_tlmadm/tp_core_tlm.F90 -- the copy the linear model runs: only it has iord = 1 and
+# 333, and its iord = 7 edge clip is written out (:357-373, :382-398) -- for a whole face (is = js = 1, ie = je = n, not nested,
+# grid_type < 3).  Every selector that compares trajectory values acts on the real part, so a complex step follows the trajectory's
+# branches.  Each routine can fill a CENSUS: {selector: (fired, margin, discontinuous, live)} with a boolean plane of where the selector held,
+# a plane of its relative margin (the distance from the switch over the larger operand, or over the given scale) and whether the
+# routine's value jumps across it (the schemes 3 .. 7, near_zero, c > 0) or merely kinks (the min / max clamps of the monotone schemes),
+# and a plane `live`: False where both operands are rounding noise of the field (under 1e-9 of its largest value) -- in an exactly flat
+# run every slope is zero to rounding, whichever branch is taken the flux is the cell value to rounding, and the branch is decided by
+# the last bit (q_i of a flat q is flat only to rounding: near_zero of an outer sweep there is a coin toss in any precision).
+NEAR_ZERO, PPM_FAC, R3 = 1.0e-25, 1.5, 1.0 / 3.0    # tp_core_tlm.F90:35-37
+S11, S14, S15 = 11.0 / 14.0, 4.0 / 7.0, 3.0 / 14.0   # :57
+MONOTONE = (8, 9, 10, 11, 12, 13)
+
+
+def _lt(cen, name, a, b, hard=False, scale=None, qs=None, live=None):
+    """real(a) < real(b), recorded in the census; qs: the field's largest value (live: the larger operand above 1e-9 qs, unless given)"""
+    ar, br = np.real(a), np.real(b)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        f = ar < br
+        if cen is not None:
+            big = np.maximum(np.abs(ar), np.abs(br))
+            s = big if scale is None else np.broadcast_to(scale, f.shape)
+            m = np.where(s > 0, np.abs(ar - br) / np.where(s > 0, s, 1), 0.0)
+            if live is None:
+                live = np.ones(f.shape, bool) if qs is None else big > 1.0e-9 * qs
+            cen[name] = (f, m.astype(np.float64), hard, np.broadcast_to(live, f.shape))
+    return f
+
+
+def _mn(a, b):        # IF (a .GT. b) THEN b ELSE a
+    return np.where(np.real(a) > np.real(b), b, a)
+
+
+def _mx(a, b):        # IF (a .LT. b) THEN b ELSE a
+    return np.where(np.real(a) < np.real(b), b, a)
+
+
+def _sign(a, b):      # SIGN(a, b)
+    return np.where(np.real(b) >= 0, _abs(a), -_abs(a))
+
+
+def pert_ppm(a0, al, ar, iv, cen=None, tag="", qs=None):
+    """PERT_PPM (tp_core_tlm.F90:1853-1917): returns the limited al, ar.  iv = 0 the positive-definite constraint (:1868-1896), otherwise the
+    standard PPM constraint (:1897-1916)"""
+    zero = np.zeros_like(al)
+    one = np.ones(zero.shape)
+    lv = None if qs is None else np.maximum(np.abs(np.real(al)), np.abs(np.real(ar))) > 1.0e-9 * qs       # slopes that are not rounding noise
+    both_live = None if qs is None else np.minimum(np.abs(np.real(al)), np.abs(np.real(ar))) > 1.0e-9 * qs
+    if iv == 0:
+        nonpos = ~_lt(cen, tag + "pd:a0>0", 0.0, a0 + zero)                      # a0 <= 0  :1871
+        a4 = -(3.0 * (ar + al))
+        da1 = ar - al
+        t1 = _lt(cen, tag + "pd:|da1|<-a4", _abs(da1), -a4, live=lv)             # :1882
+        safe = np.where(np.real(a4) == 0, 1.0, a4)
+        fmin = a0 + 0.25 / safe * da1 ** 2 + a4 * (1.0 / 12.0)
+        t2 = _lt(cen, tag + "pd:fmin<0", fmin, 0.0, scale=np.abs(np.real(a0 + zero)), live=lv)   # :1884
+        both = (np.real(ar) > 0) & (np.real(al) > 0)                             # :1885
+        d1 = np.real(da1) > 0                                                    # :1888
+        hit = t1 & t2 & ~nonpos
+        if cen is not None:
+            cen[tag + "pd:limited"] = (hit, one, False, one > 0 if lv is None else lv)
+            cen[tag + "pd:both>0"] = (hit & both, one, False, one > 0 if lv is None else lv)
+        nar = np.where(nonpos, zero, np.where(hit, np.where(both, zero, np.where(d1, -(2.0 * al), ar)), ar))
+        nal = np.where(nonpos, zero, np.where(hit, np.where(both, zero, np.where(d1, al, -(2.0 * ar))), al))
+        return nal, nar
+    opp = _lt(cen, tag + "std:al*ar<0", al * ar, 0.0, scale=np.maximum(np.abs(np.real(al)), np.abs(np.real(ar))) ** 2, live=both_live)      # :1900
+    da1 = al - ar
+    da2 = da1 ** 2
+    a6da = 3.0 * (al + ar) * da1
+    A = _lt(cen, tag + "std:a6da<-da2", a6da, -da2, live=both_live) & opp          # :1905
+    B = _lt(cen, tag + "std:a6da>da2", da2, a6da, live=both_live) & opp & ~A       # :1907
+    nar = np.where(opp, np.where(A, -(2.0 * al), ar), zero)
+    nal = np.where(opp, np.where(B, -(2.0 * ar), al), zero)
+    return nal, nar
+
+
+def xppm(q, c, iord, dxa, n, j0, j1, cen=None, tag="", yform=False):
+    """XPPM (tp_core_tlm.F90:237-956) on the rows j0 .. j1 of a whole face, iord = 1 .. 13 and 333: the flux-form value at the faces
+    i = 1 .. npx (NaN elsewhere), with is1 = 3, ie3 = npx - 2, ie1 = npx - 3 (:314-329), both edge blocks and PERT_PPM with iv = 0
+    (9, 13) and iv = 1 (the edge blocks of 8 .. 13).  yform: the ONE statement in which YPPM is not the transpose (see yppm)."""
+    npx = n + 1
+    rows = slice(j0 + NG - 1, j1 + NG)
+    flux_full = np.full(np.broadcast(q, c).shape, np.nan, dtype=np.result_type(q, c))
+    q, c, dxa = q[..., rows, :], c[..., rows, :], dxa[..., rows, :]
+    shape, dt_ = np.broadcast(q, c).shape, np.result_type(q, c)
+    new = lambda: np.full(shape, np.nan, dtype=dt_)
+    X = lambda a, i0, i1, d=0: a[..., i0 + d + NG - 1:i1 + d + NG]
+    Q = lambda i0, i1, d=0: X(q, i0, i1, d)
+    col = lambda a, i: a[..., i + NG - 1]
+    D = lambda i: dxa[..., i + NG - 1]
+    qc = lambda i: col(q, i)
+    qmax = np.max(np.abs(np.real(q[np.isfinite(np.real(q))]))) if np.isfinite(np.real(q)).any() else 1.0
+    F = (1, npx)
+    cF = X(c, *F)
+    up = _lt(cen, tag + "c>0", np.zeros(shape[:-1] + (npx,)), cF, hard=True, scale=np.nanmax(np.abs(np.real(cF))))
+    flux = new()
+
+    def edge_value(i):      # the two-sided value at the face edge between the cells i - 1 and i  :353-355, :377-380, :832-834, :891-894
+        return 0.5 * (((2.0 * D(i - 1) + D(i - 2)) * qc(i - 1) - D(i - 1) * qc(i - 2)) / (D(i - 2) + D(i - 1))
+                      + ((2.0 * D(i) + D(i + 1)) * qc(i) - D(i) * qc(i + 1)) / (D(i) + D(i + 1)))
+    if iord < 8 or iord == 333:
+        al = new()
+        A = (3, npx - 2)                                                          # :342-344
+        X(al, *A)[...] = P1 * (Q(*A, -1) + Q(*A)) + P2 * (Q(*A, -2) + Q(*A, 1))
+        if iord == 7:                                                             # :345-349 (YPPM :1060-1066 takes q(j) + q(j+1))
+            neg = _lt(cen, tag + "al<0", X(al, *A), 0.0, hard=True, scale=qmax, qs=qmax)
+            X(al, *A)[...] = np.where(neg, 0.5 * ((Q(*A) + Q(*A, 1)) if yform else (Q(*A, -1) + Q(*A))), X(al, *A))
+        col(al, 0)[...] = C1 * qc(-2) + C2 * qc(-1) + C3 * qc(0)                   # :352-356
+        col(al, 1)[...] = edge_value(1)
+        col(al, 2)[...] = C3 * qc(1) + C2 * qc(2) + C1 * qc(3)
+        col(al, npx - 1)[...] = C1 * qc(npx - 3) + C2 * qc(npx - 2) + C3 * qc(npx - 1)    # :376-381
+        col(al, npx)[...] = edge_value(npx)
+        col(al, npx + 1)[...] = C3 * qc(npx) + C2 * qc(npx + 1) + C1 * qc(npx + 2)
+        if iord == 7:                                                             # :357-373, :382-398
+            for i in (0, 1, 2, npx - 1, npx, npx + 1):
+                pos = _lt(cen, tag + "edge_al>0:%s%d" % (("w", i) if i < 3 else ("e", i - npx)), 0.0, col(al, i) + 0, hard=True, scale=qmax, qs=qmax)
+                col(al, i)[...] = np.where(pos, col(al, i), 0.0)
+        xt = cF
+        if iord == 1:                                                             # :401-408
+            X(flux, *F)[...] = np.where(up, Q(*F, -1), Q(*F))
+        elif iord == 2:                                                           # :409-424
+            qm, q0 = Q(*F, -1), Q(*F)
+            X(flux, *F)[...] = np.where(up, qm + (1.0 - xt) * (X(al, *F) - qm - xt * (X(al, *F, -1) + X(al, *F) - (qm + qm))),
+                                        q0 + (1.0 + xt) * (X(al, *F) - q0 + xt * (X(al, *F) + X(al, *F, 1) - (q0 + q0))))
+        elif iord == 333:                                                         # :425-441
+            X(flux, *F)[...] = np.where(up, (2.0 * Q(*F) + 5.0 * Q(*F, -1) - Q(*F, -2)) / 6.0 - 0.5 * xt * (Q(*F) - Q(*F, -1))
+                                        + xt * xt / 6.0 * (Q(*F) - 2.0 * Q(*F, -1) + Q(*F, -2)),
+                                        (2.0 * Q(*F, -1) + 5.0 * Q(*F) - Q(*F, 1)) / 6.0 - 0.5 * xt * (Q(*F) - Q(*F, -1))
+                                        + xt * xt / 6.0 * (Q(*F, 1) - 2.0 * Q(*F) + Q(*F, -1)))
+        else:
+            B = (0, npx)                                                          # is - 1 .. ie + 1
+            bl, br, b0 = new(), new(), new()
+            X(bl, *B)[...] = X(al, *B) - Q(*B)
+            X(br, *B)[...] = X(al, *B, 1) - Q(*B)
+            X(b0, *B)[...] = X(bl, *B) + X(br, *B)
+            s5f, s6f = np.zeros(shape, bool), np.zeros(shape, bool)
+            if iord in (3, 4):                                                    # :443-459, :519-535
+                x0, xd = _abs(X(b0, *B)), _abs(X(bl, *B) - X(br, *B))
+                X(s5f, *B)[...] = _lt(cen, tag + "smt5", x0, xd, hard=True, qs=qmax)
+                X(s6f, *B)[...] = _lt(cen, tag + "smt6", 3.0 * x0, xd, hard=True, qs=qmax)
+            elif iord == 5:                                                       # :555-560
+                X(s5f, *B)[...] = _lt(cen, tag + "bl*br<0", X(bl, *B) * X(br, *B), 0.0, hard=True,
+                                      scale=np.maximum(np.abs(np.real(X(bl, *B))), np.abs(np.real(X(br, *B)))) ** 2,
+                                      live=np.minimum(np.abs(np.real(X(bl, *B))), np.abs(np.real(X(br, *B)))) > 1.0e-9 * qmax)
+            else:                                                                 # 6, 7  :562-577
+                X(s5f, *B)[...] = _lt(cen, tag + "|3b0|<|bl-br|", _abs(3.0 * X(b0, *B)), _abs(X(bl, *B) - X(br, *B)), hard=True, qs=qmax)
+            s5m, s5, s6m, s6 = X(s5f, *F, -1), X(s5f, *F), X(s6f, *F, -1), X(s6f, *F)
+            blm, brm, b0m, bl0, br0, b00 = X(bl, *F, -1), X(br, *F, -1), X(b0, *F, -1), X(bl, *F), X(br, *F), X(b0, *F)
+            if iord == 3:                                                         # :460-517
+                lin_u = _sign(_mn(_abs(blm), _abs(brm)), brm)
+                lin_d = _sign(_mn(_abs(bl0), _abs(br0)), bl0)
+                fu = np.where(s6m | s5, brm - xt * b0m, np.where(s5m, lin_u, 0.0))
+                fd = np.where(s6 | s5m, bl0 + xt * b00, np.where(s5, lin_d, 0.0))
+                if cen is not None:
+                    two = np.where(up, ~(s6m | s5) & s5m, ~(s6 | s5m) & s5)
+                    cen[tag + "piecewise_linear"] = (two, np.ones(two.shape), False, np.ones(two.shape, bool))
+                X(flux, *F)[...] = np.where(up, Q(*F, -1), Q(*F)) + (1.0 - _abs(xt)) * np.where(up, fu, fd)
+            elif iord == 4:                                                       # :536-551
+                fu = np.where(s6m | s5, (1.0 - xt) * (brm - xt * b0m), 0.0)
+                fd = np.where(s6 | s5m, (1.0 + xt) * (bl0 + xt * b00), 0.0)
+                X(flux, *F)[...] = np.where(up, Q(*F, -1), Q(*F)) + np.where(up, fu, fd)
+            else:                                                                 # :580-589
+                fx1 = np.where(up, (1.0 - xt) * (brm - xt * b0m), (1.0 + xt) * (bl0 + xt * b00))
+                X(flux, *F)[...] = np.where(up, Q(*F, -1), Q(*F)) + np.where(s5m | s5, fx1, 0.0)
+    else:
+        assert iord in MONOTONE, iord
+        dm, al, bl, br = new(), new(), new(), new()
+        Dm = (-1, npx + 1)                                                        # is - 2 .. ie + 2  :596-639
+        xt = 0.25 * (Q(*Dm, 1) - Q(*Dm, -1))
+        hi = _mx(_mx(Q(*Dm, -1), Q(*Dm)), Q(*Dm, 1)) - Q(*Dm)
+        lo = Q(*Dm) - _mn(_mn(Q(*Dm, -1), Q(*Dm)), Q(*Dm, 1))
+        X(dm, *Dm)[...] = _sign(_mn(_mn(_abs(xt), hi), lo), xt)
+        A = (3, npx - 2)                                                          # is1 .. ie1 + 1  :640-642
+        X(al, *A)[...] = 0.5 * (Q(*A, -1) + Q(*A)) + R3 * (X(dm, *A, -1) - X(dm, *A))
+        I = (3, npx - 3)                                                          # is1 .. ie1
+        if iord in (8, 11):                                                       # :643-678, :679-715
+            xt = (2.0 if iord == 8 else PPM_FAC) * X(dm, *I)
+            X(bl, *I)[...] = -_sign(_mn(_abs(xt), _abs(X(al, *I) - Q(*I))), xt)
+            X(br, *I)[...] = _sign(_mn(_abs(xt), _abs(X(al, *I, 1) - Q(*I))), xt)
+        else:                                                                     # 9, 10, 12, 13  :716-823
+            dq = new()
+            Dq = (1, npx - 2)                                                     # is1 - 2 .. ie1 + 1
+            X(dq, *Dq)[...] = 2.0 * (Q(*Dq, 1) - Q(*Dq))
+            b_l, b_r = X(al, *I) - Q(*I), X(al, *I, 1) - Q(*I)
+            nz = _lt(cen, tag + "near_zero", _abs(X(dm, *I, -1)) + _abs(X(dm, *I)) + _abs(X(dm, *I, 1)), NEAR_ZERO, hard=True, qs=qmax)
+            huynh = _lt(cen, tag + "|3b0|>|bl-br|", _abs(b_l - b_r), _abs(3.0 * (b_l + b_r)), qs=qmax)
+            pmp_2 = X(dq, *I, -1)
+            lac_2 = pmp_2 - 0.75 * X(dq, *I, -2)
+            r_new = _mn(_mx(_mx(0.0 * pmp_2, pmp_2), lac_2), _mx(b_r, _mn(_mn(0.0 * pmp_2, pmp_2), lac_2)))
+            pmp_1 = -X(dq, *I)
+            lac_1 = pmp_1 + 0.75 * X(dq, *I, 1)
+            l_new = _mn(_mx(_mx(0.0 * pmp_1, pmp_1), lac_1), _mx(b_l, _mn(_mn(0.0 * pmp_1, pmp_1), lac_1)))
+            X(bl, *I)[...] = np.where(nz, 0.0, np.where(huynh, l_new, b_l))
+            X(br, *I)[...] = np.where(nz, 0.0, np.where(huynh, r_new, b_r))
+        if iord in (9, 13):                                                       # :826-828
+            X(bl, *I)[...], X(br, *I)[...] = pert_ppm(Q(*I), X(bl, *I).copy(), X(br, *I).copy(), 0, cen, tag, qmax)
+        # west :830-885
+        col(bl, 0)[...] = S14 * col(dm, -1) + S11 * (qc(-1) - qc(0))
+        xt = edge_value(1)
+        xt = _mx(xt, _mn(_mn(qc(-1), qc(0)), _mn(qc(1), qc(2))))
+        xt = _mn(xt, _mx(_mx(qc(-1), qc(0)), _mx(qc(1), qc(2))))
+        col(br, 0)[...] = xt - qc(0)
+        col(bl, 1)[...] = xt - qc(1)
+        xt = S15 * qc(1) + S11 * qc(2) - S14 * col(dm, 2)
+        col(br, 1)[...] = xt - qc(1)
+        col(bl, 2)[...] = xt - qc(2)
+        col(br, 2)[...] = col(al, 3) - qc(2)
+        W = (0, 2)
+        X(bl, *W)[...], X(br, *W)[...] = pert_ppm(Q(*W), X(bl, *W).copy(), X(br, *W).copy(), 1, cen, tag + "west:", qmax)
+        # east :886-943
+        col(bl, npx - 2)[...] = col(al, npx - 2) - qc(npx - 2)
+        xt = S15 * qc(npx - 1) + S11 * qc(npx - 2) + S14 * col(dm, npx - 2)
+        col(br, npx - 2)[...] = xt - qc(npx - 2)
+        col(bl, npx - 1)[...] = xt - qc(npx - 1)
+        xt = edge_value(npx)
+        xt = _mx(xt, _mn(_mn(qc(npx - 2), qc(npx - 1)), _mn(qc(npx), qc(npx + 1))))
+        xt = _mn(xt, _mx(_mx(qc(npx - 2), qc(npx - 1)), _mx(qc(npx), qc(npx + 1))))
+        col(br, npx - 1)[...] = xt - qc(npx - 1)
+        col(bl, npx)[...] = xt - qc(npx)
+        col(br, npx)[...] = S11 * (qc(npx + 1) - qc(npx)) - S14 * col(dm, npx + 1)
+        E = (npx - 2, npx)
+        X(bl, *E)[...], X(br, *E)[...] = pert_ppm(Q(*E), X(bl, *E).copy(), X(br, *E).copy(), 1, cen, tag + "east:", qmax)
+        cc = cF                                                                   # :945-953
+        X(flux, *F)[...] = np.where(up, Q(*F, -1) + (1.0 - cc) * (X(br, *F, -1) - cc * (X(bl, *F, -1) + X(br, *F, -1))),
+                                    Q(*F) + (1.0 + cc) * (X(bl, *F) + cc * (X(bl, *F) + X(br, *F))))
+    flux_full[..., rows, :] = flux
+    return flux_full
+
+
+def yppm(q, c, jord, dya, n, i0, i1, cen=None, tag=""):
+    """YPPM (tp_core_tlm.F90:957-1723) on the columns i0 .. i1.  Read line by line against XPPM: js1 / je3 / je1 :1032-1053 = :314-334; al and
+    its edge values :1055-1127 = :342-400; the schemes 1, 2, 333, 3, 4, 5, 6 / 7 :1128-1336 = :401-590; dm, al, the limiters of 8, 11 and of
+    9 / 10 / 12 / 13 :1342-1581 = :596-824; PERT_PPM :1582-1588 = :826-828; the edge blocks :1589-1710 = :829-944 (PERT_PPM over the three rows
+    at once, which works cell by cell); the flux :1711-1721 = :945-953 -- all the exact transpose (j for i, dya for dxa), with ONE
+    exception: the scheme-7 replacement of a negative al, :1063, takes 0.5 (q(i, j) + q(i, j+1)) where XPPM :347 takes
+    0.5 (q1(i-1) + q1(i)).  Restated as written (yform) and evaluated on the transposed planes."""
+    return _T(xppm(_T(q), _T(c), jord, _T(dya), n, i0, i1, cen, tag, yform=True))
+
+
+def deln_flux(nord, damp, q, fx, fy, M, n, mass=None):
+    """DELN_FLUX (tp_core_tlm.F90:1918-2043): returns fx, fy with the del-n fluxes of q added, weighted by the mass where it is given"""
+    d2, fx2, fy2 = (np.full(q.shape, np.nan, dtype=q.dtype) for _ in range(3))
+    r = (-nord, n + 1 + nord, -nord, n + 1 + nord)                               # :1948-1964
+    V(d2, *r)[...] = V(q, *r) if mass is not None else damp * V(q, *r)
+    if nord > 0:
+        copy_corners(d2, 1, n)
+    r = (1 - nord, n + nord + 1, 1 - nord, n + nord)                            # :1969-1973
+    V(fx2, *r)[...] = V(M["del6_v"], *r) * (V(d2, *r, di=-1) - V(d2, *r))
+    if nord > 0:
+        copy_corners(d2, 2, n)
+    r = (1 - nord, n + nord, 1 - nord, n + nord + 1)                            # :1978-1982
+    V(fy2, *r)[...] = V(M["del6_u"], *r) * (V(d2, *r, dj=-1) - V(d2, *r))
+    for m in range(1, nord + 1):                                                # :1987-2011
+        nt = nord - m
+        r = (-nt, n + nt + 1, -nt, n + nt + 1)
+        V(d2, *r)[...] = (V(fx2, *r) - V(fx2, *r, di=1) + V(fy2, *r) - V(fy2, *r, dj=1)) * V(M["rarea"], *r)
+        copy_corners(d2, 1, n)
+        r = (1 - nt, n + nt + 1, 1 - nt, n + nt)
+        V(fx2, *r)[...] = V(M["del6_v"], *r) * (V(d2, *r) - V(d2, *r, di=-1))
+        copy_corners(d2, 2, n)
+        r = (1 - nt, n + nt, 1 - nt, n + nt + 1)
+        V(fy2, *r)[...] = V(M["del6_u"], *r) * (V(d2, *r) - V(d2, *r, dj=-1))
+    fx, fy = fx.copy(), fy.copy()
+    rx, ry = (1, n + 1, 1, n), (1, n, 1, n + 1)
+    if mass is not None:                                                        # :2016-2030
+        damp2 = 0.5 * damp
+        V(fx, *rx)[...] = V(fx, *rx) + damp2 * (V(mass, *rx, di=-1) + V(mass, *rx)) * V(fx2, *rx)
+        V(fy, *ry)[...] = V(fy, *ry) + damp2 * (V(mass, *ry, dj=-1) + V(mass, *ry)) * V(fy2, *ry)
+    else:                                                                       # :2032-2041
+        V(fx, *rx)[...] = V(fx, *rx) + V(fx2, *rx)
+        V(fy, *ry)[...] = V(fy, *ry) + V(fy2, *ry)
+    return fx, fy
+
+
+def fv_tp_2d(q, crx, cry, hord, xfx, yfx, ra_x, ra_y, M, n, mfx=None, mfy=None, mass=None, nord=None, damp_c=None, da_min=None, cen=None, tag=""):
+    """FV_TP_2D (tp_core_tlm.F90:83-236) on a whole face: returns fx on (1 .. npx, 1 .. n) and fy on (1 .. n, 1 .. npy).  ord_in = 8 under
+    hord = 10 (:136-140); copy_corners with 2 before the inner y sweep, with 1 before the inner x sweep (:142, :165); the flux averaging
+    with the mass fluxes (:189-211) or the area fluxes (:212-234), DELN_FLUX with and without the mass."""
+    npx = npy = n + 1
+    isd, ied, jsd, jed = 1 - NG, n + NG, 1 - NG, n + NG
+    ord_in = 8 if hord == 10 else hord
+    shape, dtype = np.broadcast(q, crx, cry).shape, np.result_type(q, crx, cry, xfx)
+    new = lambda: np.full(shape, np.nan, dtype=dtype)
+    q = np.array(np.broadcast_to(q, shape), dtype=dtype)
+    copy_corners(q, 2, n)
+    fy2 = yppm(q, cry, ord_in, M["dya"], n, isd, ied, cen, tag + "in_y:")            # :148-150
+    fyy = yfx * fy2
+    q_i = new()
+    r = (isd, ied, 1, n)                                                        # :156-161
+    V(q_i, *r)[...] = (V(q, *r) * V(M["area"], *r) + V(fyy, *r) - V(fyy, *r, dj=1)) / V(ra_y, *r)
+    fx = xppm(q_i, crx, hord, M["dxa"], n, 1, n, cen, tag + "out_x:")                # :162-164
+    copy_corners(q, 1, n)
+    fx2 = xppm(q, crx, ord_in, M["dxa"], n, jsd, jed, cen, tag + "in_x:")            # :171-173
+    fx1 = xfx * fx2
+    q_j = new()
+    r = (1, n, jsd, jed)                                                        # :174-182
+    V(q_j, *r)[...] = (V(q, *r) * V(M["area"], *r) + V(fx1, *r) - V(fx1, *r, di=1)) / V(ra_x, *r)
+    fy = yppm(q_j, cry, hord, M["dya"], n, 1, n, cen, tag + "out_y:")                # :183-185
+    wx, wy = (mfx, mfy) if mfx is not None and mfy is not None else (xfx, yfx)
+    ox, oy = new(), new()
+    rx, ry = (1, npx, 1, n), (1, n, 1, npy)
+    V(ox, *rx)[...] = 0.5 * (V(fx, *rx) + V(fx2, *rx)) * V(wx, *rx)             # :193-202, :216-225
+    V(oy, *ry)[...] = 0.5 * (V(fy, *ry) + V(fy2, *ry)) * V(wy, *ry)
+    with_mass = mfx is not None and mfy is not None
+    if nord is not None and damp_c is not None and (mass is not None or not with_mass) and damp_c > 1.0e-4:      # :203-211, :226-234
+        ox, oy = deln_flux(nord, (damp_c * da_min) ** (nord + 1), q, ox, oy, M, n, mass=mass if with_mass else None)
+    return ox, oy
