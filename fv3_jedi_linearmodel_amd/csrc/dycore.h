@@ -502,27 +502,108 @@ struct Dycore {
   }
   std::vector<std::pair<double*, size_t>> acoustic_zero;     // plan_adjoint(acoustic, work)
 
-  // fv_tp_2d as a stage sequence (tp_core_tlm.F90:83-236): q -> fx, fy.  mx/my = xfx/yfx or mass fluxes.
+  // fv_tp_2d (tp_core_tlm.F90:83-236): q -> fx, fy.  mx/my = xfx/yfx or mass fluxes.  Two forms, chosen here: the LDS-tiled launches
+  // (default) and the seven staged stages with their strips in every mode (FV3LM_TP_FUSED=0) -- the two agree bit for bit in the
+  // nonlinear and tangent modes.
   void build_tp(Program& P, const char* grp, const std::string& pre, Fld q, Fld crx, Fld cry, Fld xfx, Fld yfx, Fld rax,
                 Fld ray, Fld mx, Fld my, Fld mass, int hsel, int dsel, bool use_mass, Fld fx, Fld fy, int nk = 0, const Fld* acc4 = nullptr) {
-    const int is = g.is(), ie = g.ie(), js = g.js(), je = g.je(), isd = g.isd(), ied = g.ied(), jsd = g.jsd(), jed = g.jed(), npz = nk ? nk : g.npz;
-    // nonlinear and tangent modes: the whole routine as one LDS-tiled launch (tpfused.h); the staged launches below then serve the
-    // adjoint only (FV3LM_TP_FUSED=0 runs them in every mode -- the two forms agree bit for bit)
-    const bool fused = switch_on("FV3LM_TP_FUSED");
-    // The outer fluxes fxo, fyo are trajectory arrays of their own only while something reads them: the staged flux assembly.  With the
-    // hand-written outer adjoint (which re-evaluates them from q_i, q_j in passing) they are neither stored by the nonlinear launch nor
-    // part of a trajectory slot; the names then alias fx2 / fy2 for the staged ops that never run.
-    const char* aenv = std::getenv("FV3LM_TP_AD_FUSED");
-    // 2: the whole adjoint as one launch (tpad.h; faces, sub-face tiles and the periodic tile); 1: outer half fused, inner half staged; 0: staged
-    const int adf = !fused ? 0 : aenv ? (aenv[0] == '0' ? 0 : aenv[0] == '1' ? 1 : 2) : 2;
-    const bool own_fo = adf == 0, own_mid = adf < 2;
-    // the inner fluxes and the intermediate fields are trajectory arrays of their own only while a staged adjoint launch reads them; the
-    // fused adjoint recomputes them in LDS, so neither the nonlinear launch stores them nor a trajectory slot holds them -- the names then
-    // alias fx / fy for the staged ops that never run
-    Fld fy2 = own_mid ? W((pre + "_fy2").c_str(), npz) : fy, q_i = own_mid ? W((pre + "_qi").c_str(), npz) : fx;
-    Fld fx2 = own_mid ? W((pre + "_fx2").c_str(), npz) : fx, q_j = own_mid ? W((pre + "_qj").c_str(), npz) : fy;
-    Fld fxo = own_fo ? W((pre + "_fxo").c_str(), npz) : fx2, fyo = own_fo ? W((pre + "_fyo").c_str(), npz) : fy2;
-    const size_t first_op = P.size();
+    const int is = g.is(), ie = g.ie(), js = g.js(), je = g.je(), npz = nk ? nk : g.npz;
+    // the tracers' damping (DAMP_TR) acts in the first sub-step of tracer_2d only: its stages launch nothing in the later ones, and a
+    // damping Laplacian exists only where some level's order asks for one (need_d2: the chain the tangent / adjoint is taken of,
+    // need_d2t: the trajectory pass of split levels)
+    bool need_d2 = dsel != DAMP_NONE, need_d2t = need_d2;
+    if (dsel == DAMP_TR) {
+      need_d2 = need_d2t = false;
+      for (int k = 0; k < npz && k < (int)lev_host.size(); ++k) {
+        const bool sp = level_split(lev_host[k], hsel, dsel);
+        int n_; double d_; damp_of(lev_host[k], dsel, n_, d_, sp); need_d2 = need_d2 || (n_ >= 1 && d_ > 1.e-4);
+        if (sp) { damp_of(lev_host[k], dsel, n_, d_, false); need_d2t = need_d2t || (n_ >= 1 && d_ > 1.e-4); }
+      }
+    }
+    Ctx* gate_ctx = &ctx;
+    auto first_substep_only = [&](size_t n0) {
+      if (dsel != DAMP_TR) return;
+      for (size_t n = n0; n < P.size(); ++n) { auto f = P[n].fn; P[n].fn = [f, gate_ctx](Exec& e, int m) { if (gate_ctx->tr_it == 1) f(e, m); }; }
+    };
+    // the damping Laplacian (TpD2) is a stage of its own in both forms and every mode
+    auto add_d2 = [&]() -> Fld {
+      if (!need_d2) return Fld{};
+      const size_t n0 = P.size();
+      Fld d2b = W((pre + "_d2b").c_str(), npz);
+      TpD2D h; h.in[0] = q; h.out[0] = d2b; h.orect[0] = R(is - 1, ie + 1, js - 1, je + 1); h.k1 = npz; h.dsel = dsel; h.use_mass = use_mass; h.hsel = hsel;
+      add_face(P, grp, h, 1);
+      first_substep_only(n0);
+      return d2b;
+    };
+    // split_hord: some level runs this transport with a trajectory scheme other than the scheme the tangent / adjoint is taken of
+    bool any_split = false;
+    for (int k = 0; k < npz && k < (int)lev_host.size(); ++k) any_split = any_split || level_split(lev_host[k], hsel, dsel);
+    if (!switch_on("FV3LM_TP_FUSED")) {
+      build_tp_staged(P, grp, pre, q, crx, cry, xfx, yfx, rax, ray, mx, my, mass, hsel, dsel, use_mass, fx, fy, npz, add_d2);
+      if (any_split) set_sticky("split_hord / split_damp need the fused fv_tp_2d (unset FV3LM_TP_FUSED)");
+      return;
+    }
+    // ---- the tiled form: nonlinear and tangent as one launch (tp2.h), the values-only trajectory pass of split levels (tpfused.h), the
+    // adjoint as one launch (tpad.h) that recomputes every intermediate in LDS; the damping part of the flux keeps a (small) adjoint
+    // stage of its own (TpDamp)
+    const Fld d2b = add_d2();
+    TpFusedArgs a; a.q = q; a.crx = crx; a.cry = cry; a.xfx = xfx; a.yfx = yfx; a.rax = rax; a.ray = ray; a.mx = mx; a.my = my;
+    a.mass = use_mass ? mass : Fld{}; a.d2b = d2b; a.fx = fx; a.fy = fy;
+    a.hsel = hsel; a.dsel = dsel; a.use_mass = use_mass ? 1 : 0; a.nk = npz; a.do_acc = 0;
+    if (acc4) { a.acx = acc4[0]; a.acy = acc4[1]; a.amfx = acc4[2]; a.amfy = acc4[3]; }
+    const unsigned fwd = (1u << MODE_NL) | (1u << MODE_TL);
+    // what the launch reads / writes (add_halo_async looks for the last op that touches a field; plan_adjoint skips this op: not an adjoint op)
+    TiledAd io;
+    for (const Fld* f_ : {&a.q, &a.crx, &a.cry, &a.xfx, &a.yfx, &a.rax, &a.ray, &a.mx, &a.my, &a.mass, &a.d2b}) if (f_->p) io.in.push_back(f_->p);
+    for (const Fld* f_ : {&a.fx, &a.fy, &a.acx, &a.acy, &a.amfx, &a.amfy}) if (f_->p) io.out.push_back(f_->p);
+    add_tiled(P, grp, "TpFused", std::make_shared<TpFusedArgs>(a), run_tp2, fwd, io);
+    if (any_split) {       // the trajectory pass of the split levels: its own damping Laplacian (run as a nonlinear launch in the tangent mode too), then the chain
+      if (need_d2t) {
+        Fld d2t = W((pre + "_d2t").c_str(), npz);
+        // a trajectory nord of 2 (split_damp, nord >= 2): two Laplacians, the first into a scratch array on the range widened by one
+        bool nord2 = false;
+        for (int k = 0; k < npz && k < (int)lev_host.size(); ++k) { int n_; double d_; damp_of(lev_host[k], dsel, n_, d_, false); nord2 = nord2 || (n_ == 2 && d_ > 1.e-4 && level_split(lev_host[k], hsel, dsel)); }
+        const size_t n0 = P.size();
+        TpD2D h; h.in[0] = q; h.out[0] = d2t; h.orect[0] = R(is - 1, ie + 1, js - 1, je + 1); h.k1 = npz; h.dsel = dsel; h.use_mass = use_mass; h.hsel = hsel; h.traj = 1;
+        if (nord2) {
+          Fld d2a = W((pre + "_d2a").c_str(), npz);
+          TpD2D h1 = h; h1.out[0] = d2a; h1.orect[0] = R(is - 2, ie + 2, js - 2, je + 2); h1.pass = 1;
+          add_face(P, grp, h1, 2);
+          h.in[0] = d2a;
+        }
+        add_face(P, grp, h, 1);
+        for (size_t n = n0; n < P.size(); ++n) {
+          auto f = P[n].fn;
+          P[n].fn = [f](Exec& e, int) { f(e, MODE_NL); };
+          P[n].modes = fwd; P[n].ad_in.clear(); P[n].ad_in_slot.clear(); P[n].ad_out.clear(); P[n].ad_out_rect.clear(); P[n].set_wmask = nullptr;
+        }
+        first_substep_only(n0);
+        a.d2b_t = d2t;
+      }
+      add_tiled(P, grp, "TpFusedTraj", std::make_shared<TpFusedArgs>(a), [](Exec& e, int, const TpFusedArgs& a_, const Ctx& c_) { run_tp_traj(e, a_, c_); }, fwd);
+    }
+    if (dsel != DAMP_NONE) {
+      TpDamp dm; dm.in[0] = q; dm.in[1] = d2b; dm.in[2] = use_mass ? mass : Fld{};
+      for (int n = 1; n < 3; ++n) if (!dm.in[n].t) dm.in[n].nk = npz;
+      dm.out[0] = fx; dm.out[1] = fy; dm.orect[0] = R(is, ie + 1, js, je); dm.orect[1] = R(is, ie, js, je + 1); dm.k1 = npz;
+      dm.dsel = dsel; dm.use_mass = use_mass; dm.hsel = hsel;
+      const size_t n0 = P.size();
+      add(P, grp, dm); P.back().modes = 1u << MODE_AD;
+      first_substep_only(n0);
+    }
+    TiledAd ad; ad.out = {fx.p, fy.p}; ad.out_rect = {R(is, ie + 1, js, je), R(is, ie, js, je + 1)};
+    ad.in = {q.p, crx.p, cry.p, xfx.p, yfx.p, rax.p, ray.p, mx.p, my.p};
+    add_tiled(P, grp, "TpAd", std::make_shared<TpFusedArgs>(a), [](Exec& e, int, const TpFusedArgs& a_, const Ctx& c_) { run_tp_ad(e, a_, c_); }, 1u << MODE_AD, ad);
+  }
+  // the staged form of fv_tp_2d: seven stage launches -- inner y-sweep, q_i, outer x-sweep, inner x-sweep, q_j, outer y-sweep, flux
+  // assembly -- in every mode, every intermediate a work array; add_d2 appends the damping Laplacian and returns its field
+  template <class AddD2>
+  void build_tp_staged(Program& P, const char* grp, const std::string& pre, Fld q, Fld crx, Fld cry, Fld xfx, Fld yfx, Fld rax, Fld ray,
+                       Fld mx, Fld my, Fld mass, int hsel, int dsel, bool use_mass, Fld fx, Fld fy, int npz, const AddD2& add_d2) {
+    const int is = g.is(), ie = g.ie(), js = g.js(), je = g.je(), isd = g.isd(), ied = g.ied(), jsd = g.jsd(), jed = g.jed();
+    Fld fy2 = W((pre + "_fy2").c_str(), npz), q_i = W((pre + "_qi").c_str(), npz);
+    Fld fx2 = W((pre + "_fx2").c_str(), npz), q_j = W((pre + "_qj").c_str(), npz);
+    Fld fxo = W((pre + "_fxo").c_str(), npz), fyo = W((pre + "_fyo").c_str(), npz);
     // the four 1-D PPM sweeps; on a face each is a bulk launch (4-point edge values everywhere) plus two strips three flux
     // points wide next to the face edges (one-sided edge values, corner views of the inner sweeps)
     auto ppm_y = [&](Fld qq, Fld out, Rect r, int cdir) {
@@ -550,116 +631,18 @@ struct Dycore {
     ppm_y(q, fy2, R(isd, ied, js, je + 1), 2);
     TpQi b; b.in[0] = q; b.in[1] = fy2; b.in[2] = yfx; b.in[3] = ray; b.out[0] = q_i; b.orect[0] = R(isd, ied, js, je); b.k1 = npz;
     add(P, grp, b);
-    const size_t o1a = P.size();
     ppm_x(q_i, fxo, R(is, ie + 1, js, je), 0);
-    const size_t o1b = P.size();
     ppm_x(q, fx2, R(is, ie + 1, jsd, jed), 1);
     TpQj e; e.in[0] = q; e.in[1] = fx2; e.in[2] = xfx; e.in[3] = rax; e.out[0] = q_j; e.orect[0] = R(is, ie, jsd, jed); e.k1 = npz;
     add(P, grp, e);
-    const size_t o2a = P.size();
     ppm_y(q_j, fyo, R(is, ie, js, je + 1), 0);
-    const size_t o2b = P.size();
-    Fld d2b{};
-    // the tracers' damping (DAMP_TR) acts in the first sub-step of tracer_2d only: its stages launch nothing in the later ones, and a
-    // damping Laplacian exists only where some level's order asks for one (need_d2: the chain the tangent / adjoint is taken of,
-    // need_d2t: the trajectory pass of split levels)
-    bool need_d2 = dsel != DAMP_NONE, need_d2t = need_d2;
-    if (dsel == DAMP_TR) {
-      need_d2 = need_d2t = false;
-      for (int k = 0; k < npz && k < (int)lev_host.size(); ++k) {
-        const bool sp = level_split(lev_host[k], hsel, dsel);
-        int n_; double d_; damp_of(lev_host[k], dsel, n_, d_, sp); need_d2 = need_d2 || (n_ >= 1 && d_ > 1.e-4);
-        if (sp) { damp_of(lev_host[k], dsel, n_, d_, false); need_d2t = need_d2t || (n_ >= 1 && d_ > 1.e-4); }
-      }
-    }
-    Ctx* gate_ctx = &ctx;
-    auto first_substep_only = [&](size_t n0) {
-      if (dsel != DAMP_TR) return;
-      for (size_t n = n0; n < P.size(); ++n) { auto f = P[n].fn; P[n].fn = [f, gate_ctx](Exec& e, int m) { if (gate_ctx->tr_it == 1) f(e, m); }; }
-    };
-    if (need_d2) {
-      const size_t n0 = P.size();
-      d2b = W((pre + "_d2b").c_str(), npz);
-      TpD2D h; h.in[0] = q; h.out[0] = d2b; h.orect[0] = R(is - 1, ie + 1, js - 1, je + 1); h.k1 = npz; h.dsel = dsel; h.use_mass = use_mass; h.hsel = hsel;
-      add_face(P, grp, h, 1);
-      first_substep_only(n0);
-    }
-    // split_hord: some level runs this transport with a trajectory scheme other than the scheme the tangent / adjoint is taken of
-    bool any_split = false;
-    for (int k = 0; k < npz && k < (int)lev_host.size(); ++k) any_split = any_split || level_split(lev_host[k], hsel, dsel);
+    const Fld d2b = add_d2();
     TpFlux t; t.in[0] = fxo; t.in[1] = fx2; t.in[2] = mx; t.in[3] = fyo; t.in[4] = fy2; t.in[5] = my;
     t.in[6] = (dsel != DAMP_NONE) ? q : Fld{}; t.in[7] = d2b; t.in[8] = use_mass ? mass : Fld{};
     for (int n = 6; n < 9; ++n) if (!t.in[n].t) t.in[n].nk = npz;
     t.out[0] = fx; t.out[1] = fy; t.orect[0] = R(is, ie + 1, js, je); t.orect[1] = R(is, ie, js, je + 1); t.k1 = npz;
     t.dsel = dsel; t.use_mass = use_mass; t.hsel = hsel;
-    const size_t o3 = P.size();
     add(P, grp, t);
-    if (any_split && !fused) set_sticky("split_hord / split_damp need the fused fv_tp_2d (unset FV3LM_TP_FUSED)");
-    if (fused) {
-      size_t d2_op = P.size();      // the damping Laplacian (TpD2) stays a stage of its own in every mode
-      for (size_t n = first_op; n < P.size(); ++n) if (P[n].name == "TpD2" || P[n].name == "TpD2e") d2_op = n;
-      for (size_t n = first_op; n < P.size(); ++n) if (!(P[n].name == "TpD2" || P[n].name == "TpD2e")) P[n].modes = 1u << MODE_AD;
-      (void)d2_op;
-      TpFusedArgs a; a.q = q; a.crx = crx; a.cry = cry; a.xfx = xfx; a.yfx = yfx; a.rax = rax; a.ray = ray; a.mx = mx; a.my = my;
-      a.mass = use_mass ? mass : Fld{}; a.d2b = d2b; a.fx = fx; a.fy = fy;
-      a.fy2 = fy2; a.q_i = q_i; a.fxo = fxo; a.fx2 = fx2; a.q_j = q_j; a.fyo = fyo;
-      a.hsel = hsel; a.dsel = dsel; a.use_mass = use_mass ? 1 : 0; a.nk = npz;
-      a.do_acc = 0; a.store_fo = own_fo ? 1 : 0; a.store_mid = own_mid ? 1 : 0;
-      if (acc4) { a.acx = acc4[0]; a.acy = acc4[1]; a.amfx = acc4[2]; a.amfy = acc4[3]; }
-      const unsigned fwd = (1u << MODE_NL) | (1u << MODE_TL);
-      // what the launch reads / writes (add_halo_async looks for the last op that touches a field; plan_adjoint skips this op: not an adjoint op)
-      TiledAd io;
-      for (const Fld* f_ : {&a.q, &a.crx, &a.cry, &a.xfx, &a.yfx, &a.rax, &a.ray, &a.mx, &a.my, &a.mass, &a.d2b}) if (f_->p) io.in.push_back(f_->p);
-      for (const Fld* f_ : {&a.fx, &a.fy, &a.fy2, &a.q_i, &a.fxo, &a.fx2, &a.q_j, &a.fyo, &a.acx, &a.acy, &a.amfx, &a.amfy}) if (f_->p) io.out.push_back(f_->p);
-      add_tiled(P, grp, "TpFused", std::make_shared<TpFusedArgs>(a), [](Exec& e, int mode, const TpFusedArgs& a_, const Ctx& c_) { run_tp_fused(e, mode, a_, c_); }, fwd, io);
-      if (any_split) {       // the trajectory pass of the split levels: its own damping Laplacian (run as a nonlinear launch in the tangent mode too), then the chain
-        if (need_d2t) {
-          Fld d2t = W((pre + "_d2t").c_str(), npz);
-          // a trajectory nord of 2 (split_damp, nord >= 2): two Laplacians, the first into a scratch array on the range widened by one
-          bool nord2 = false;
-          for (int k = 0; k < npz && k < (int)lev_host.size(); ++k) { int n_; double d_; damp_of(lev_host[k], dsel, n_, d_, false); nord2 = nord2 || (n_ == 2 && d_ > 1.e-4 && level_split(lev_host[k], hsel, dsel)); }
-          const size_t n0 = P.size();
-          TpD2D h; h.in[0] = q; h.out[0] = d2t; h.orect[0] = R(is - 1, ie + 1, js - 1, je + 1); h.k1 = npz; h.dsel = dsel; h.use_mass = use_mass; h.hsel = hsel; h.traj = 1;
-          if (nord2) {
-            Fld d2a = W((pre + "_d2a").c_str(), npz);
-            TpD2D h1 = h; h1.out[0] = d2a; h1.orect[0] = R(is - 2, ie + 2, js - 2, je + 2); h1.pass = 1;
-            add_face(P, grp, h1, 2);
-            h.in[0] = d2a;
-          }
-          add_face(P, grp, h, 1);
-          for (size_t n = n0; n < P.size(); ++n) {
-            auto f = P[n].fn;
-            P[n].fn = [f](Exec& e, int) { f(e, MODE_NL); };
-            P[n].modes = (1u << MODE_NL) | (1u << MODE_TL); P[n].ad_in.clear(); P[n].ad_in_slot.clear(); P[n].ad_out.clear(); P[n].ad_out_rect.clear(); P[n].set_wmask = nullptr;
-          }
-          first_substep_only(n0);
-          a.d2b_t = d2t;
-        }
-        add_tiled(P, grp, "TpFusedTraj", std::make_shared<TpFusedArgs>(a), [](Exec& e, int mode, const TpFusedArgs& a_, const Ctx& c_) { run_tp_fused(e, mode, a_, c_, true); }, fwd);
-      }
-      // adjoint: the whole routine as ONE hand-written launch (tpad.h); the staged launches then never run, the damping part of the flux keeps a
-      // (small) stage of its own.  FV3LM_TP_AD_FUSED=1: round 2's form (outer half fused, inner half staged); =0: all staged.
-      if (adf > 0) {
-        if (adf == 2) { for (size_t n = first_op; n < o3; ++n) if (!(P[n].name == "TpD2" || P[n].name == "TpD2e")) P[n].modes = 0; }
-        else { for (size_t n = o1a; n < o1b; ++n) P[n].modes = 0; for (size_t n = o2a; n < o2b; ++n) P[n].modes = 0; }
-        P[o3].modes = 0;
-        if (dsel != DAMP_NONE) {
-          TpDamp dm; dm.in[0] = q; dm.in[1] = d2b; dm.in[2] = use_mass ? mass : Fld{};
-          for (int n = 1; n < 3; ++n) if (!dm.in[n].t) dm.in[n].nk = npz;
-          dm.out[0] = fx; dm.out[1] = fy; dm.orect[0] = R(is, ie + 1, js, je); dm.orect[1] = R(is, ie, js, je + 1); dm.k1 = npz;
-          dm.dsel = dsel; dm.use_mass = use_mass; dm.hsel = hsel;
-          const size_t n0 = P.size();
-          add(P, grp, dm); P.back().modes = 1u << MODE_AD;
-          first_substep_only(n0);
-        }
-        TiledAd ad; ad.out = {fx.p, fy.p}; ad.out_rect = {R(is, ie + 1, js, je), R(is, ie, js, je + 1)};
-        if (adf == 2) ad.in = {q.p, crx.p, cry.p, xfx.p, yfx.p, rax.p, ray.p, mx.p, my.p};
-        else { ad.store = {q_i.p, q_j.p, fx2.p, fy2.p}; ad.in = {crx.p, cry.p, mx.p, my.p}; }
-        const auto ap = std::make_shared<TpFusedArgs>(a);
-        if (adf == 2) add_tiled(P, grp, "TpAd", ap, [](Exec& e, int, const TpFusedArgs& a_, const Ctx& c_) { run_tp_ad(e, a_, c_); }, 1u << MODE_AD, ad);
-        else add_tiled(P, grp, "TpOuter", ap, [](Exec& e, int, const TpFusedArgs& a_, const Ctx& c_) { run_tp_outer_ad(e, a_, c_); }, 1u << MODE_AD, ad);
-      }
-    }
   }
   // a2b_ord4 (a2b_edge_tlm.F90:48-542): q (nk levels) -> qb on is..ie+1, js..je+1
   void build_a2b(Program& P, const char* grp, const std::string& pre, Fld q, Fld qb, int nk) {

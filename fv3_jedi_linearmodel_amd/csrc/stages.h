@@ -91,7 +91,7 @@ HD T ppm_flux(int iord, bool face, int m, int n1, const Q& q, const D& da, T cc)
 }
 
 // d flux(m) / d q(k) of the same schemes in closed form (they are linear in q for a given Courant number): the transposed sweep of
-// the hand-written outer adjoint (tpfused.h).  al(x) = sum_e w_e(x) q(x - 2 + e) with the edge-aware weights of edges.h ppm_w.
+// the hand-written adjoint (tpad.h).  al(x) = sum_e w_e(x) q(x - 2 + e) with the edge-aware weights of edges.h ppm_w.
 template <class D>
 HD double ppm_al_coef(bool face, int x, int n1, const D& da, int k) {
   const int e = k - x + 2;
@@ -945,7 +945,7 @@ struct TpFlux {
 };
 
 // The damping part of the flux assembly alone (deln_flux, tp_core_tlm.F90:1918-2043): fx, fy <- the del-2 / del-4 fluxes of q.  Used in
-// the adjoint mode only, beside the fused outer adjoint of tpfused.h (which handles 0.5 (f_outer + f_inner) m): the flux is the sum of the
+// the adjoint mode only, beside the fused adjoint of tpad.h (which handles 0.5 (f_outer + f_inner) m): the flux is the sum of the
 // two parts, so the adjoints with respect to q, d2b and mass are exactly this stage's.
 struct TpDamp {
   STAGE_BASE("TpDamp", 3, 2)   // in: q d2b mass   out: fx fy (adjoints read; never run forward)

@@ -18,11 +18,7 @@
 #else
 #define TPF_SYNC() __syncthreads()
 // constant trip count, unrolled: the global loads of a thread's elements of a phase are issued together
-#ifdef FV3LM_TPF_NOUNROLL      /* experiment: real loops, a quarter of the code */
-#define TPF_LOOP(e, n) _Pragma("nounroll") for (int e = tid; e < (n); e += NTH)
-#else
 #define TPF_LOOP(e, n) _Pragma("unroll") for (int e = tid; e < (n); e += NTH)
-#endif
 // the same with the slot index u of a per-thread register array (constant trip count E = ceil(n / NTH): static indices after unrolling)
 #define TPF_LOOPU(e, u, n, E) _Pragma("unroll") for (int u = 0; u < (E); ++u) if (const int e = tid + u * NTH; e < (n))
 #endif

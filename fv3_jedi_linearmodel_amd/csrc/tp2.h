@@ -1,6 +1,6 @@
 // fv3lm-hip: fv_tp_2d (tp_core_tlm.F90:83-236, _TLM :2123-2324), nonlinear and tangent-linear, as one LDS-tiled kernel laid out for the
-// wavefront.  Same routine, same LDS tiles and the same arithmetic as tpfused.h's tp_fused_block (which stays for the trajectory pass of
-// split schemes and for the launches that store the intermediates of the staged adjoint); what differs is the data flow:
+// wavefront.  Same routine, same LDS tiles and the same arithmetic as the first tiled kernel (the flattened-element layout that
+// tpfused.h keeps for the trajectory pass of split schemes); what differs is the data flow:
 //   * a wave owns a ROW of the block and a lane a COLUMN: no flattened element index, no division, the row of every element is a scalar,
 //     so the face-edge tests of the y-sweeps are scalar branches; the few halo columns beyond the 64 lanes are shared out afterwards;
 //   * an interface flux reads the five cells around its UPWIND cell (address selected by the sign of the Courant number) and forms the
@@ -20,9 +20,6 @@ FV3LM_LINK void run_tp2(Exec& ex, int mode, const TpFusedArgs& a0, const Ctx& c)
 namespace fv3 {
 #ifndef FV3LM_TP2_H
 #define FV3LM_TP2_H 16
-#endif
-#ifndef FV3LM_TP2_EXP
-#define FV3LM_TP2_EXP 0
 #endif
 // operands of the next phase fetched into registers before the barrier that ends the current one (0: every load where it is used)
 #ifndef FV3LM_TP2_PRE_NL
@@ -112,12 +109,7 @@ DEV T tp2_flux2(const T* p, const T& cc, bool up, const double* w0, const double
 // NWV = 1, tid = 0).
 template <class T, int NWV>
 DEV void tp2_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, int by, T* lds, int tid) {
-  // timing experiments (tools/kbench.py --group, a library built with -DFV3LM_TP2_EXP=1; results are garbage): a.exp bit 0 = fluxes without
-  // arithmetic, bit 1 = no global loads after the q tile, bit 2 = no global stores
-  struct IO {
-    DEV static T ld(const Fld& f, size_t n, int ex = 0) { if (FV3LM_TP2_EXP && (ex & 2)) return T(1.e-3 * double(n & 7)); return TpfIO<T>::ld(f, n); }
-    DEV static void st(const Fld& f, size_t n, const T& x, int ex = 0) { if (FV3LM_TP2_EXP && (ex & 4)) return; TpfIO<T>::st(f, n, x); }
-  };
+  typedef TpfIO<T> IO;
 #ifdef FV3LM_HOST_EMUL
   constexpr int NTH = 1;           // one "thread" runs every element
 #else
@@ -144,7 +136,7 @@ DEV void tp2_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, 
   auto own_i = [&](int i) { return (i >= I0 && i <= I1) || (firstx && i < I0) || (lastx && i > I1); };
   auto own_j = [&](int j) { return (j >= J0 && j <= J1) || (firsty && j < J0) || (lasty && j > J1); };
   auto acc_flux = [&](const Fld& acc, size_t n, const T& f) {
-    if (!split) IO::st(acc, n, IO::ld(acc, n, a.exp) + f, a.exp);
+    if (!split) IO::st(acc, n, IO::ld(acc, n) + f);
     else if constexpr (!std::is_same<T, double>::value) acc.p[n] += f.d;
   };
   // Global operands of the next phase are fetched into registers before the barrier that ends the current one: with one or a few blocks
@@ -160,9 +152,9 @@ DEV void tp2_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, 
   T cx3[NIH], mx3[NIH], cy3[NIH1], my3[NIH1];                                                       // outer sweeps
   if constexpr (PRE) {
     tp2_fetch<NWV, TP2_H + 1>(tid, [&](int x, int r, int it) TP2_INLINE {
-      cy1[it] = (I0 - 3 + x <= I1 + 3 && J0 + r <= J1 + 1) ? IO::ld(a.cry, base + (size_t)((r + 3) * pi + x), a.exp) : T(0.); });
+      cy1[it] = (I0 - 3 + x <= I1 + 3 && J0 + r <= J1 + 1) ? IO::ld(a.cry, base + (size_t)((r + 3) * pi + x)) : T(0.); });
     tp2_fetch<NWV, TP2_RQ>(tid, [&](int x, int r, int it) TP2_INLINE {
-      cx1[it] = (I0 + x <= I1 + 1 && J0 - 3 + r <= J1 + 3) ? IO::ld(a.crx, base + (size_t)(r * pi + x + 3), a.exp) : T(0.); });
+      cx1[it] = (I0 + x <= I1 + 1 && J0 - 3 + r <= J1 + 3) ? IO::ld(a.crx, base + (size_t)(r * pi + x + 3)) : T(0.); });
   }
   // ---- the block of q and its halo; the metric-dependent edge weights of the rows / columns of this block
   tp2_sweep<NWV, TP2_PQ, TP2_RQ>(tid, [&](int x, int r, int it) TP2_INLINE {
@@ -191,12 +183,12 @@ DEV void tp2_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, 
     tp2_fetch<NWV, TP2_H>(tid, [&](int x, int r, int it) TP2_INLINE {
       const bool in = I0 - 3 + x <= I1 + 3 && J0 + r <= J1;
       const size_t o = (size_t)((r + 3) * pi + x), n = base + o;
-      y0_2[it] = in ? IO::ld(a.yfx, n, a.exp) : T(0.); y1_2[it] = in ? IO::ld(a.yfx, n + pi, a.exp) : T(0.); ry_2[it] = in ? IO::ld(a.ray, n, a.exp) : T(1.);
+      y0_2[it] = in ? IO::ld(a.yfx, n) : T(0.); y1_2[it] = in ? IO::ld(a.yfx, n + pi) : T(0.); ry_2[it] = in ? IO::ld(a.ray, n) : T(1.);
       ai_2[it] = in ? c.m.area[mbase + o] : 0.; });
     tp2_fetch<NWV, TP2_RQ>(tid, [&](int x, int r, int it) TP2_INLINE {
       const bool in = I0 + x <= I1 && J0 - 3 + r <= J1 + 3;
       const size_t o = (size_t)(r * pi + x + 3), n = base + o;
-      x0_2[it] = in ? IO::ld(a.xfx, n, a.exp) : T(0.); x1_2[it] = in ? IO::ld(a.xfx, n + 1, a.exp) : T(0.); rx_2[it] = in ? IO::ld(a.rax, n, a.exp) : T(1.);
+      x0_2[it] = in ? IO::ld(a.xfx, n) : T(0.); x1_2[it] = in ? IO::ld(a.xfx, n + 1) : T(0.); rx_2[it] = in ? IO::ld(a.rax, n) : T(1.);
       aj_2[it] = in ? c.m.area[mbase + o] : 0.; });
   }
   const double W0[4] = {-1. / 12., 7. / 12., 7. / 12., -1. / 12.};
@@ -207,7 +199,6 @@ DEV void tp2_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, 
     const bool up = val(cc) > 0.;
     const T* p = line0 + (r3 - (up ? 1 : 0)) * S;
     if (iord == 1) return p[0];
-    if (FV3LM_TP2_EXP && (a.exp & 1)) return p[0] * cc;
     if (neary && (j <= 3 || j >= ny - 1)) {
       double w0[4], w1[4];
       const int u = j - (up ? 1 : 0);
@@ -220,7 +211,6 @@ DEV void tp2_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, 
     const bool up = val(cc) > 0.;
     const T* p = row0 + (c3 - (up ? 1 : 0));
     if (iord == 1) return p[0];
-    if (FV3LM_TP2_EXP && (a.exp & 1)) return p[0] * cc;
     if (nearx) {
       double w0[4], w1[4];
       const int u = i - (up ? 1 : 0);
@@ -234,7 +224,7 @@ DEV void tp2_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, 
     const int i = I0 - 3 + x, j = J0 + r;
     if (i > I1 + 3 || j > J1 + 1) return;
     const size_t n = base + (size_t)((r + 3) * pi + x);
-    const T cc = (PRE && it >= 0) ? cy1[it < 0 ? 0 : it] : IO::ld(a.cry, n, a.exp);
+    const T cc = (PRE && it >= 0) ? cy1[it < 0 ? 0 : it] : IO::ld(a.cry, n);
     T f;
     if (!fast || (face && (i < 1 || i > nx) && (j <= 3 || j >= ny - 1))) {       // corner columns next to a face edge: the rotated view
       auto line = [&](int jj) -> T { int ii = i, j2 = jj; if (face) corner_map(g, 2, ii, j2); return Q[(j2 - (J0 - 3)) * TP2_PQ + (ii - (I0 - 3))]; };
@@ -248,13 +238,13 @@ DEV void tp2_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, 
       if (val(f_) != val(f)) std::fprintf(stderr, "FY2 i %d j %d: %.17g vs %.17g (c %g)\n", i, j, val(f), val(f_), val(cc)); }
 #endif
     FY2[r * TP2_PQ + x] = f;
-    if (a.do_acc && own_i(i) && (j <= J1 || lasty)) IO::st(a.acy, n, IO::ld(a.acy, n, a.exp) + cc, a.exp);
+    if (a.do_acc && own_i(i) && (j <= J1 || lasty)) IO::st(a.acy, n, IO::ld(a.acy, n) + cc);
   });
   tp2_sweep<NWV, TP2_PX, TP2_RQ>(tid, [&](int x, int r, int it) TP2_INLINE {
     const int i = I0 + x, j = J0 - 3 + r;
     if (i > I1 + 1 || j > J1 + 3) return;
     const size_t n = base + (size_t)(r * pi + x + 3);
-    const T cc = (PRE && it >= 0) ? cx1[it < 0 ? 0 : it] : IO::ld(a.crx, n, a.exp);
+    const T cc = (PRE && it >= 0) ? cx1[it < 0 ? 0 : it] : IO::ld(a.crx, n);
     T f;
     if (!fast || (face && (j < 1 || j > ny) && (i <= 3 || i >= nx - 1))) {
       auto line = [&](int ii) -> T { int i2 = ii, jj = j; if (face) corner_map(g, 1, i2, jj); return Q[(jj - (J0 - 3)) * TP2_PQ + (i2 - (I0 - 3))]; };
@@ -268,18 +258,18 @@ DEV void tp2_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, 
       if (val(f_) != val(f)) std::fprintf(stderr, "FX2 i %d j %d: %.17g vs %.17g (c %g)\n", i, j, val(f), val(f_), val(cc)); }
 #endif
     FX2[r * TP2_PX + x] = f;
-    if (a.do_acc && own_j(j) && (i <= I1 || lastx)) IO::st(a.acx, n, IO::ld(a.acx, n, a.exp) + cc, a.exp);
+    if (a.do_acc && own_j(j) && (i <= I1 || lastx)) IO::st(a.acx, n, IO::ld(a.acx, n) + cc);
   });
   TPF_SYNC();
   if constexpr (PRE) {
     tp2_fetch<NWV, TP2_H>(tid, [&](int x, int r, int it) TP2_INLINE {
       const int i = I0 + x; const bool in = J0 + r <= J1 && (i <= I1 || (lastx && i == I1 + 1));
       const size_t n = base + (size_t)((r + 3) * pi + x + 3);
-      cx3[it] = in ? IO::ld(a.crx, n, a.exp) : T(0.); mx3[it] = in ? IO::ld(a.mx, n, a.exp) : T(0.); });
+      cx3[it] = in ? IO::ld(a.crx, n) : T(0.); mx3[it] = in ? IO::ld(a.mx, n) : T(0.); });
     tp2_fetch<NWV, TP2_H + 1>(tid, [&](int x, int r, int it) TP2_INLINE {
       const int j = J0 + r; const bool in = I0 + x <= I1 && (j <= J1 || (lasty && j == J1 + 1));
       const size_t n = base + (size_t)((r + 3) * pi + x + 3);
-      cy3[it] = in ? IO::ld(a.cry, n, a.exp) : T(0.); my3[it] = in ? IO::ld(a.my, n, a.exp) : T(0.); });
+      cy3[it] = in ? IO::ld(a.cry, n) : T(0.); my3[it] = in ? IO::ld(a.my, n) : T(0.); });
   }
   // ---- q_i, q_j: the field advanced by the inner fluxes (tp_core_tlm.F90:149-159, :173-181)
   tp2_sweep<NWV, TP2_PQ, TP2_H>(tid, [&](int x, int r, int it) TP2_INLINE {
@@ -287,16 +277,16 @@ DEV void tp2_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, 
     if (i > I1 + 3 || j > J1) return;
     const size_t o = (size_t)((r + 3) * pi + x), n = base + o;
     const bool pf = PRE && it >= 0; const int u = it < 0 ? 0 : it;
-    const T f0 = (pf ? y0_2[u] : IO::ld(a.yfx, n, a.exp)) * FY2[r * TP2_PQ + x], f1 = (pf ? y1_2[u] : IO::ld(a.yfx, n + pi, a.exp)) * FY2[(r + 1) * TP2_PQ + x];
-    QI[r * TP2_PQ + x] = (Q[(r + 3) * TP2_PQ + x] * (pf ? ai_2[u] : c.m.area[mbase + o]) + f0 - f1) / (pf ? ry_2[u] : IO::ld(a.ray, n, a.exp));
+    const T f0 = (pf ? y0_2[u] : IO::ld(a.yfx, n)) * FY2[r * TP2_PQ + x], f1 = (pf ? y1_2[u] : IO::ld(a.yfx, n + pi)) * FY2[(r + 1) * TP2_PQ + x];
+    QI[r * TP2_PQ + x] = (Q[(r + 3) * TP2_PQ + x] * (pf ? ai_2[u] : c.m.area[mbase + o]) + f0 - f1) / (pf ? ry_2[u] : IO::ld(a.ray, n));
   });
   tp2_sweep<NWV, TP2_W, TP2_RQ>(tid, [&](int x, int r, int it) TP2_INLINE {
     const int i = I0 + x, j = J0 - 3 + r;
     if (i > I1 || j > J1 + 3) return;
     const size_t o = (size_t)(r * pi + x + 3), n = base + o;
     const bool pf = PRE && it >= 0; const int u = it < 0 ? 0 : it;
-    const T f0 = (pf ? x0_2[u] : IO::ld(a.xfx, n, a.exp)) * FX2[r * TP2_PX + x], f1 = (pf ? x1_2[u] : IO::ld(a.xfx, n + 1, a.exp)) * FX2[r * TP2_PX + x + 1];
-    QJ[r * TP2_W + x] = (Q[r * TP2_PQ + x + 3] * (pf ? aj_2[u] : c.m.area[mbase + o]) + f0 - f1) / (pf ? rx_2[u] : IO::ld(a.rax, n, a.exp));
+    const T f0 = (pf ? x0_2[u] : IO::ld(a.xfx, n)) * FX2[r * TP2_PX + x], f1 = (pf ? x1_2[u] : IO::ld(a.xfx, n + 1)) * FX2[r * TP2_PX + x + 1];
+    QJ[r * TP2_W + x] = (Q[r * TP2_PQ + x + 3] * (pf ? aj_2[u] : c.m.area[mbase + o]) + f0 - f1) / (pf ? rx_2[u] : IO::ld(a.rax, n));
   });
   TPF_SYNC();
   // ---- outer sweeps and flux assembly (tp_core_tlm.F90:187-234; deln_flux :1918-2043 as in stages.h TpFlux)
@@ -310,22 +300,22 @@ DEV void tp2_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, 
     if (j > J1 || i > I1 + 1 || !(i <= I1 || lastx)) return;
     const size_t o = (size_t)((r + 3) * pi + x + 3), n = base + o;
     const bool pf = PRE && it >= 0; const int u = it < 0 ? 0 : it;
-    const T cc = pf ? cx3[u] : IO::ld(a.crx, n, a.exp);
+    const T cc = pf ? cx3[u] : IO::ld(a.crx, n);
     T fo;
     if (!fast) {
       auto line = [&](int ii) -> T { return QI[r * TP2_PQ + (ii - (I0 - 3))]; };
       const MetX da{c.m.dxa, c, tile, j};
       fo = ppm_flux<T>(iord, face, i, nx + 1, line, da, cc);
     } else fo = xflux(QI + r * TP2_PQ, x + 3, i, r + 3, cc);
-    T f = 0.5 * (fo + FX2[(r + 3) * TP2_PX + x]) * (pf ? mx3[u] : IO::ld(a.mx, n, a.exp));
+    T f = 0.5 * (fo + FX2[(r + 3) * TP2_PX + x]) * (pf ? mx3[u] : IO::ld(a.mx, n));
     if (dmp) {
       T f2;
       if (nord == 0) { f2 = c.m.del6_v[mbase + o] * (Q[(r + 3) * TP2_PQ + x + 2] - Q[(r + 3) * TP2_PQ + x + 3]); if (!a.use_mass) f2 = damp * f2; }
-      else f2 = c.m.del6_v[mbase + o] * (IO::ld(d2, n, a.exp) - IO::ld(d2, n - 1, a.exp));
-      if (a.use_mass) f = f + (0.5 * damp) * (IO::ld(a.mass, n - 1, a.exp) + IO::ld(a.mass, n, a.exp)) * f2;
+      else f2 = c.m.del6_v[mbase + o] * (IO::ld(d2, n) - IO::ld(d2, n - 1));
+      if (a.use_mass) f = f + (0.5 * damp) * (IO::ld(a.mass, n - 1) + IO::ld(a.mass, n)) * f2;
       else f = f + f2;
     }
-    IO::st(a.fx, n, f, a.exp);
+    IO::st(a.fx, n, f);
     if (a.do_acc) acc_flux(a.amfx, n, f);
   });
   tp2_sweep<NWV, TP2_W, TP2_H + 1>(tid, [&](int x, int r, int it) TP2_INLINE {       // fy(i, j)
@@ -333,22 +323,22 @@ DEV void tp2_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx, 
     if (i > I1 || j > J1 + 1 || !(j <= J1 || lasty)) return;
     const size_t o = (size_t)((r + 3) * pi + x + 3), n = base + o;
     const bool pf = PRE && it >= 0; const int u = it < 0 ? 0 : it;
-    const T cc = pf ? cy3[u] : IO::ld(a.cry, n, a.exp);
+    const T cc = pf ? cy3[u] : IO::ld(a.cry, n);
     T fo;
     if (!fast) {
       auto line = [&](int jj) -> T { return QJ[(jj - (J0 - 3)) * TP2_W + x]; };
       const MetY da{c.m.dya, c, tile, i};
       fo = ppm_flux<T>(iord, face, j, ny + 1, line, da, cc);
     } else fo = yflux(QJ + x, std::integral_constant<int, TP2_W>(), r + 3, j, x + 3, cc);
-    T f = 0.5 * (fo + FY2[r * TP2_PQ + x + 3]) * (pf ? my3[u] : IO::ld(a.my, n, a.exp));
+    T f = 0.5 * (fo + FY2[r * TP2_PQ + x + 3]) * (pf ? my3[u] : IO::ld(a.my, n));
     if (dmp) {
       T f2;
       if (nord == 0) { f2 = c.m.del6_u[mbase + o] * (Q[(r + 2) * TP2_PQ + x + 3] - Q[(r + 3) * TP2_PQ + x + 3]); if (!a.use_mass) f2 = damp * f2; }
-      else f2 = c.m.del6_u[mbase + o] * (IO::ld(d2, n, a.exp) - IO::ld(d2, n - pi, a.exp));
-      if (a.use_mass) f = f + (0.5 * damp) * (IO::ld(a.mass, n - pi, a.exp) + IO::ld(a.mass, n, a.exp)) * f2;
+      else f2 = c.m.del6_u[mbase + o] * (IO::ld(d2, n) - IO::ld(d2, n - pi));
+      if (a.use_mass) f = f + (0.5 * damp) * (IO::ld(a.mass, n - pi) + IO::ld(a.mass, n)) * f2;
       else f = f + f2;
     }
-    IO::st(a.fy, n, f, a.exp);
+    IO::st(a.fy, n, f);
     if (a.do_acc) acc_flux(a.amfy, n, f);
   });
 }
@@ -359,15 +349,11 @@ template <class T, int NWV> struct Tp2Blk {
   DEV static void block(const Args& a, const Ctx& c, const Rect&, int tile, int k, int bx, int by, double* lds, int tid) { tp2_block<T, NWV>(a, c, tile, k, bx, by, reinterpret_cast<T*>(lds), tid); }
 };
 
-// nonlinear (nothing stored for the staged adjoint) / tangent-linear launch; profile names as tpfused.h: it is the same routine
+// nonlinear / tangent-linear launch, profile name TpFused
 FV3LM_LINK void run_tp2(Exec& ex, int mode, const TpFusedArgs& a0, const Ctx& c) {
   TpFusedArgs a = a0;
   for (Fld* f : {&a.q, &a.crx, &a.cry, &a.xfx, &a.yfx, &a.rax, &a.ray, &a.mx, &a.my, &a.mass, &a.d2b, &a.d2b_t, &a.fx, &a.fy, &a.acx, &a.acy, &a.amfx, &a.amfy}) *f = ex.sh(*f);
   a.do_acc = (a.acx.t && !ex.skip_accum) ? 1 : 0;
-  a.store_mid = 0;
-#if FV3LM_TP2_EXP
-  if (const char* e = std::getenv("FV3LM_TP2_EXPERIMENT")) a.exp = std::atoi(e);
-#endif
   const Rect Qr = tp_window(c.g);
   const int nbx = tiled_blocks(Qr.i0, Qr.i1, TP2_W), nby = tiled_blocks(Qr.j0, Qr.j1, TP2_H);
   if (mode == MODE_TL) run_tiled<Tp2Blk<Dual, tiled_nth(FV3LM_TP2_WAVES_TL)>>(ex, "TpFused", ".tl", tpf_bytes(a, c.g, mode), Qr, nbx, nby, a, c);

@@ -1,7 +1,7 @@
 // fv3lm-hip: the ADJOINT of fv_tp_2d (FV_TP_2D_FWD / _BWD, tp_core_adm.F90:7026 / :7263; joint form FV_TP_2D_ADM :109) as ONE LDS-tiled
 // kernel -- flux assembly, the two outer sweeps, the two intermediate updates and the two inner sweeps, transposed in closed form.
 //
-// Round 2 ran it as one hand-written launch for the outer half (tp_outer_ad_block) + six staged gather launches, their strips and corner
+// Round 2 ran it as one hand-written launch for the outer half + six staged gather launches, their strips and corner
 // launches for the inner half, with the adjoints of q_i, q_j, fx2, fy2 and the trajectory of the same four making round trips through
 // HBM.  Here a workgroup owns a 64 x 16 block of cells of one level and GATHERS everything that block owns:
 //
@@ -47,9 +47,6 @@ namespace fv3 {
 // operands of the next phase fetched into registers before the barrier that ends the current one (0: every load where it is used)
 #ifndef FV3LM_TPD_PREFETCH
 #define FV3LM_TPD_PREFETCH 1
-#endif
-#ifndef FV3LM_TPD_EXP          /* timing experiments (tools/kbench.py --group; results are garbage): a.exp bits switch phases off */
-#define FV3LM_TPD_EXP 0
 #endif
 #ifndef FV3LM_TPD_THREADS
 #define FV3LM_TPD_THREADS 1024
@@ -201,7 +198,6 @@ DEV void tp_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx
         if (i > I1 + 3 || j > J1 + 1) continue;
         auto line = [&](int jj) -> double { int ii = i, j2 = jj; if (face) corner_map(g, 2, ii, j2); return Q[qe(ii, j2)]; };
         const MetY da{c.m.dya, c, tile, i};
-        if (FV3LM_TPD_EXP && (a.exp & 1)) { F2[f2e(i, j)] = line(j) * TPD_PF(cv, u, a.cry.t[at(i, j)]); continue; }
         const double cc = TPD_PF(cv, u, a.cry.t[at(i, j)]);
         if (iord == 2 && !(face && (i < 1 || i > nx) && (j <= 3 || j >= ny - 1))) { double v_, d_; tpd_flux2<TPD_QW>(face, j, ny + 1, Q + qe(i, j), cc, da, v_, d_); F2[f2e(i, j)] = v_; }
         else F2[f2e(i, j)] = ppm_flux<double>(iord, face, j, ny + 1, line, da, cc);
@@ -229,7 +225,6 @@ DEV void tp_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx
         if (j > J1 || !(i <= I1 || (lastx && i == I1 + 1))) continue;
         const double fo = FX(i, j), fxad = TPD_PF(fx3, u, a.fx.p[at(i, j)]);
         if (fo == 0. && fxad == 0.) continue;
-        if (FV3LM_TPD_EXP && (a.exp & 2)) continue;
         auto line = [&](int ii) -> Dual { return Dual(QG[qe(ii, j)], 0.); };
         const MetX da{c.m.dxa, c, tile, j};
         Dual fl;
@@ -238,7 +233,7 @@ DEV void tp_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx
         a.crx.p[at(i, j)] += fl.d * fo;
         a.mx.p[at(i, j)] += 0.5 * fl.v * fxad;
       } }
-    if (iord == 2 && !(FV3LM_TPD_EXP && (a.exp & 4))) {                                // edge-value adjoints of the outer sweep, columns I0-4 .. I1+5
+    if (iord == 2) {                                // edge-value adjoints of the outer sweep, columns I0-4 .. I1+5
       constexpr int n = TPD_AW * TPD_QH;
       TPD_LOOP(e, n) {
         const int x = I0 - 6 + e % TPD_AW, j = J0 - 3 + e / TPD_AW;
@@ -267,7 +262,7 @@ DEV void tp_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx
             s = tps_q333(face, i, nx + 1, f, cc, da);
           } else {
             const double al[4] = {AL[b0 - 1], AL[b0], AL[b0 + 1], AL[b0 + 2]};
-            if (!(FV3LM_TPD_EXP && (a.exp & 8))) s = tps_q(iord, face, i, nx + 1, FA[b0], FA[b0 + 1], CT[b0], CT[b0 + 1], al, da);
+            s = tps_q(iord, face, i, nx + 1, FA[b0], FA[b0 + 1], CT[b0], CT[b0 + 1], al, da);
           }
           s = s / ry;
           if (own) { a.ray.p[at(i, j)] = rold - QG[e] * s; acc = ar * s; }
@@ -303,7 +298,7 @@ DEV void tp_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx
       TPD_LOOPU(e, u, n, E_QA) CT[e] = TPD_PF(cyt, u, load_cy(e)); }
     TPF_SYNC();
     auto FY2 = [&](int i, int m) { return (m >= J0 - 2 && m <= J1 + 3) ? F2[f2e(i, m)] : 0.; };
-    if (iord == 2 && !(FV3LM_TPD_EXP && (a.exp & 4))) {                                // edge-value adjoints of the inner sweep, rows J0-4 .. J1+5 of the owned columns
+    if (iord == 2) {                                // edge-value adjoints of the inner sweep, rows J0-4 .. J1+5 of the owned columns
       constexpr int n = TPD_QW * TPD_AH;
       TPD_LOOP(e, n) {
         const int i = I0 - 3 + e % TPD_QW, x = J0 - 5 + e / TPD_QW;
@@ -328,7 +323,7 @@ DEV void tp_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx
         } else {
           const int b0 = ale(i, j);
           const double al[4] = {AL[b0 - TPD_QW], AL[b0], AL[b0 + TPD_QW], AL[b0 + 2 * TPD_QW]};
-          if (!(FV3LM_TPD_EXP && (a.exp & 8))) s = tps_q(iord, face, j, ny + 1, FY2(i, j), FY2(i, j + 1), CT[cb], CT[cb + TPD_QW], al, da);
+          s = tps_q(iord, face, j, ny + 1, FY2(i, j), FY2(i, j + 1), CT[cb], CT[cb + TPD_QW], al, da);
         }
         a.q.p[at(i, j)] = qold + (acc + s);
       } }
@@ -338,7 +333,6 @@ DEV void tp_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx
         if (i < GI0 || i > GI1 || !(m <= J1 || (lasty && m == J1 + 1))) continue;
         const double f = F2[f2e(i, m)];
         if (f == 0.) continue;
-        if (FV3LM_TPD_EXP && (a.exp & 2)) continue;
         auto line = [&](int jj) -> Dual { int ii = i, j2 = jj; if (face) corner_map(g, 2, ii, j2); return Dual(Q[qe(ii, j2)], 0.); };
         const MetY da{c.m.dya, c, tile, i};
         double v_, d_;
@@ -370,7 +364,6 @@ DEV void tp_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx
         if (i > I1 + 1 || j > J1 + 3) continue;
         auto line = [&](int ii) -> double { int i2 = ii, jj = j; if (face) corner_map(g, 1, i2, jj); return Q[qe(i2, jj)]; };
         const MetX da{c.m.dxa, c, tile, j};
-        if (FV3LM_TPD_EXP && (a.exp & 1)) { F2[f2e(i, j)] = line(i) * a.crx.t[at(i, j)]; continue; }
         const double cc = a.crx.t[at(i, j)];
         if (iord == 2 && !(face && (j < 1 || j > ny) && (i <= 3 || i >= nx - 1))) { double v_, d_; tpd_flux2<1>(face, i, nx + 1, Q + qe(i, j), cc, da, v_, d_); F2[f2e(i, j)] = v_; }
         else F2[f2e(i, j)] = ppm_flux<double>(iord, face, i, nx + 1, line, da, cc);
@@ -398,7 +391,6 @@ DEV void tp_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx
         if (i > I1 || !(j <= J1 || (lasty && j == J1 + 1))) continue;
         const double fo = FY(i, j), fyad = TPD_PF(fy3, u, a.fy.p[at(i, j)]);
         if (fo == 0. && fyad == 0.) continue;
-        if (FV3LM_TPD_EXP && (a.exp & 2)) continue;
         auto line = [&](int jj) -> Dual { return Dual(QG[qe(i, jj)], 0.); };
         const MetY da{c.m.dya, c, tile, i};
         Dual fl;
@@ -407,7 +399,7 @@ DEV void tp_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx
         a.cry.p[at(i, j)] += fl.d * fo;
         a.my.p[at(i, j)] += 0.5 * fl.v * fyad;
       } }
-    if (iord == 2 && !(FV3LM_TPD_EXP && (a.exp & 4))) {                                // edge-value adjoints of the outer sweep, rows J0-4 .. J1+5
+    if (iord == 2) {                                // edge-value adjoints of the outer sweep, rows J0-4 .. J1+5
       constexpr int n = TPD_QW * TPD_AH;
       TPD_LOOP(e, n) {
         const int i = I0 - 3 + e % TPD_QW, x = J0 - 6 + e / TPD_QW;
@@ -436,7 +428,7 @@ DEV void tp_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx
             s = tps_q333(face, j, ny + 1, f, cc, da);
           } else {
             const double al[4] = {AL[b0 - TPD_QW], AL[b0], AL[b0 + TPD_QW], AL[b0 + 2 * TPD_QW]};
-            if (!(FV3LM_TPD_EXP && (a.exp & 8))) s = tps_q(iord, face, j, ny + 1, FA[b0], FA[b0 + TPD_QW], CT[b0], CT[b0 + TPD_QW], al, da);
+            s = tps_q(iord, face, j, ny + 1, FA[b0], FA[b0 + TPD_QW], CT[b0], CT[b0 + TPD_QW], al, da);
           }
           s = s / rx;
           if (own) { a.rax.p[at(i, j)] = rold - QG[e] * s; acc = ar * s; }
@@ -472,7 +464,7 @@ DEV void tp_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx
       TPD_LOOPU(e, u, n, E_AQ) CT[e] = TPD_PF(cxt, u, load_cx(e)); }
     TPF_SYNC();
     auto FX2 = [&](int m, int j) { return (m >= I0 - 2 && m <= I1 + 3) ? F2[f2e(m, j)] : 0.; };
-    if (iord == 2 && !(FV3LM_TPD_EXP && (a.exp & 4))) {                                // edge-value adjoints of the inner sweep, columns I0-4 .. I1+5 of the owned rows
+    if (iord == 2) {                                // edge-value adjoints of the inner sweep, columns I0-4 .. I1+5 of the owned rows
       constexpr int n = TPD_AW * TPD_QH;
       TPD_LOOP(e, n) {
         const int x = I0 - 5 + e % TPD_AW, j = J0 - 3 + e / TPD_AW;
@@ -497,7 +489,7 @@ DEV void tp_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx
         } else {
           const int b0 = ale(i, j);
           const double al[4] = {AL[b0 - 1], AL[b0], AL[b0 + 1], AL[b0 + 2]};
-          if (!(FV3LM_TPD_EXP && (a.exp & 8))) s = tps_q(iord, face, i, nx + 1, FX2(i, j), FX2(i + 1, j), CT[cb], CT[cb + 1], al, da);
+          s = tps_q(iord, face, i, nx + 1, FX2(i, j), FX2(i + 1, j), CT[cb], CT[cb + 1], al, da);
         }
         a.q.p[at(i, j)] = qold + (acc + s);
       } }
@@ -507,7 +499,6 @@ DEV void tp_ad_block(const TpFusedArgs& a, const Ctx& c, int tile, int k, int bx
         if (j < GJ0 || j > GJ1 || j > J1 + 3 || !(m <= I1 || (lastx && m == I1 + 1))) continue;
         const double f = F2[f2e(m, j)];
         if (f == 0.) continue;
-        if (FV3LM_TPD_EXP && (a.exp & 2)) continue;
         auto line = [&](int ii) -> Dual { int i2 = ii, jj = j; if (face) corner_map(g, 1, i2, jj); return Dual(Q[qe(i2, jj)], 0.); };
         const MetX da{c.m.dxa, c, tile, j};
         double v_, d_;
@@ -602,9 +593,6 @@ FV3LM_LINK void run_tp_ad(Exec& ex, const TpFusedArgs& a0, const Ctx& c) {
   TpFusedArgs a = a0;
   for (Fld* f : {&a.q, &a.crx, &a.cry, &a.xfx, &a.yfx, &a.rax, &a.ray, &a.mx, &a.my, &a.fx, &a.fy}) *f = ex.sh(*f);
   const Rect Qr = tp_window(c.g);
-#if FV3LM_TPD_EXP
-  if (const char* e = std::getenv("FV3LM_TP2_EXPERIMENT")) a.exp = std::atoi(e);
-#endif
   // algorithmic bytes: trajectory q, crx, cry, xfx, yfx, ra_x, ra_y, mx, my and the adjoints fx, fy read; the nine input adjoints read-modify-written
   const double cells = double(c.g.tx) * c.g.ty * c.g.ntile * a.nk;
   run_tiled<TpAdBlk<tiled_nth(TPD_THREADS)>>(ex, "TpAd", ".ad", 8. * cells * (9. + 2. + 18.), Qr, tiled_blocks(Qr.i0, Qr.i1, TPD_W), tiled_blocks(Qr.j0, Qr.j1, TPD_H), a, c);

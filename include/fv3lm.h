@@ -417,7 +417,7 @@ int fv3lm_state_restore(fv3lm_handle* h);
 int fv3lm_zero_work_adjoint(fv3lm_handle* h);
 int fv3lm_sync(fv3lm_handle* h);
 long fv3lm_launch_count(fv3lm_handle* h);
-long fv3lm_tp2_launch_count(fv3lm_handle* h);  /* of them, fv_tp_2d launches in the wavefront layout (FV3LM_TP2, read per launch) */
+long fv3lm_tp2_launch_count(fv3lm_handle* h);  /* of them, fv_tp_2d launches in the wavefront layout */
 int fv3lm_level_params(fv3lm_handle* h, int k, int* iparams10, double* rparams6);
 
 #ifdef __cplusplus

@@ -767,8 +767,8 @@ def _print_figures(label, rows):
 
 
 def check(*args, env=None, **kw):
-    """_check with the switches of `env` in the environment from the creation of the instance to the last launch: the library reads some
-    when an instance is created (FV3LM_TP_FUSED, FV3LM_TP_AD_FUSED) and some at every launch (FV3LM_TP2)"""
+    """_check with the switches of `env` in the environment from the creation of the instance to the last launch: the library reads
+    FV3LM_TP_FUSED, the one switch of fv_tp_2d, where the programs of an instance are built"""
     import os
     old = {k: os.environ.get(k) for k in (env or {})}
     os.environ.update(env or {})
@@ -964,26 +964,21 @@ TRANSPORT_DAMPED = dict(d2_bg_k2=0.0, d2_bg_k2_pert=0.0, vtdm4=0.03, vtdm4_pert=
 
 
 def transport_forms(env):
-    """observe of check(): the device forms of fv_tp_2d that the switches in `env` select are the ones that ran, from the names of the
-    hand-written launches in the three run_group calls, the launch counts (the staged form of one fv_tp_2d is seven launches and its
-    strips; the group holds three) and the library's count of launches in the wavefront layout (tp2.h, whose profile names are tpfused.h's)"""
+    """observe of check(): the device form of fv_tp_2d that `env` selects is the one that ran, from the names of the hand-written launches
+    in the three run_group calls, the launch counts (the staged form of one fv_tp_2d is seven launches and its strips; the group holds
+    three) and the library's count of launches in the wavefront layout (tp2.h, whose profile name is TpFused).  Two forms: the staged
+    stages in every mode under FV3LM_TP_FUSED=0, the tiled launches (tp2.h, tpad.h) otherwise; the half-fused adjoint TpOuter is gone."""
     env = env or {}
 
     def observe(c, ran):
         staged = lambda m: not any(k.startswith(("TpFused", "TpAd", "TpOuter")) for k in ran[m]) and ran[m]["launches"] >= 3 * 7
         tp2 = c.dy.tp2_launch_count()
+        assert not any(k.startswith("TpOuter") for m in (NL, TL, AD) for k in ran[m]), ran
         if env.get("FV3LM_TP_FUSED") == "0":                                    # the staged stages in every mode
             assert staged(TL) and staged(NL) and staged(AD) and tp2 == 0, (ran, tp2)
             return
-        assert ran[TL].get("TpFused.tl", 0) > 0 and ran[NL].get("TpFused.nl", 0) > 0 and not staged(TL) and not staged(NL), ran
-        if env.get("FV3LM_TP2") == "0":                                         # tpfused.h's own tangent / nonlinear form
-            assert tp2 == 0, tp2
-        else:
-            assert tp2 > 0, tp2
-        if env.get("FV3LM_TP_AD_FUSED") == "0":                                 # the staged adjoint
-            assert staged(AD) and "TpAd.ad" not in ran[AD] and "TpOuter.ad" not in ran[AD], ran[AD]
-        else:
-            assert ran[AD].get("TpAd.ad", 0) > 0 and not staged(AD), ran[AD]
+        assert ran[TL].get("TpFused.tl", 0) > 0 and ran[NL].get("TpFused.nl", 0) > 0 and ran[AD].get("TpAd.ad", 0) > 0, ran
+        assert not staged(TL) and not staged(NL) and not staged(AD) and tp2 > 0, (ran, tp2)
     return observe
 
 

@@ -1,7 +1,8 @@
 """A hand-written LDS-tiled launch (csrc/tiled.h) against the staged launches it replaces.  Each has a switch that is read where the
 programs are built; set to 0 it brings the staged form back:
 
-FV3LM_TP_FUSED=0         fv_tp_2d as its seven stage launches + edge strips in every mode (csrc/tpfused.h, tp2.h, tpad.h otherwise).
+FV3LM_TP_FUSED=0         fv_tp_2d as its seven stage launches + edge strips in every mode -- one of its two forms; the other, the default, is
+                         csrc/tp2.h (nonlinear, tangent), the trajectory pass of csrc/tpfused.h (split levels) and csrc/tpad.h (adjoint).
 FV3LM_A2B_FUSED=0        the bulk of a2b_ord4 as A2bA + A2bB (qx, qy through memory) instead of the one launch of csrc/a2b.h.
 FV3LM_D2A2C_FUSED=0      the bulk of d2a2c_vect as CswInterpA + CswInterpC (utmp, vtmp through memory) instead of the one of csrc/d2a2c.h.
 

@@ -6,8 +6,6 @@ guard's message names the launch and "LDS".  No GPU test: the guard does not exi
 from common import Case, CubeCase
 from fused_checks import SWITCHES, _names_and_state
 
-ALL_SWITCHES = SWITCHES + ("FV3LM_TP2", "FV3LM_TP_AD_FUSED")
-
 
 def _sweeps_are_clean(c):
     L, h = c.dy.lib.L, c.dy.h
@@ -22,12 +20,12 @@ def _sweeps_are_clean(c):
 
 
 def test_lds_guard_silent_periodic_tile(monkeypatch):
-    for s in ALL_SWITCHES:
+    for s in SWITCHES:
         monkeypatch.delenv(s, raising=False)
     _sweeps_are_clean(Case(nx=70, ny=20, npz=3, n_split=2, k_split=1, dt=900.0, backend="emul", oracle=False, nq=1))
 
 
 def test_lds_guard_silent_cube_faces(monkeypatch):
-    for s in ALL_SWITCHES:
+    for s in SWITCHES:
         monkeypatch.delenv(s, raising=False)
     _sweeps_are_clean(CubeCase(n=66, npz=2, n_split=1, k_split=1, dt=225.0, backend="emul", nq=1))

@@ -30,9 +30,9 @@ def test_face_edge_operator_c16_cut_2x2(group):
 @pytest.mark.parametrize("face", range(6))
 @pytest.mark.parametrize("n", [8, 12])
 def test_d_sw_first_loops(n, face, fused):
-    """crx, cry, xfx, yfx from uc, vc (the rows that read sin_sg(0, j <= 0, 3) and their kin), the adjoint under both
-    FV3LM_TP_AD_FUSED settings"""
-    F.check("hip", "d_sw", n, face, env={"FV3LM_TP_AD_FUSED": fused})
+    """crx, cry, xfx, yfx from uc, vc (the rows that read sin_sg(0, j <= 0, 3) and their kin), under both forms of fv_tp_2d: the staged
+    stages (fused = "0": FV3LM_TP_FUSED=0) and the tiled launches of the default environment (fused = "1")"""
+    F.check("hip", "d_sw", n, face, env={"FV3LM_TP_FUSED": "0"} if fused == "0" else None)
 
 
 @pytest.mark.parametrize("face", range(6))

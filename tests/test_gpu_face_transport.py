@@ -25,17 +25,14 @@ def test_all_six_faces(h, n, face):
     F.check_transport("hip", n, face, h)
 
 
-@pytest.mark.parametrize("switch", ["FV3LM_TP_FUSED", "FV3LM_TP2", "FV3LM_TP_AD_FUSED"])
+@pytest.mark.parametrize("switch", ["FV3LM_TP_FUSED"])
 @pytest.mark.parametrize("h", [5, 10])
 def test_kernel_forms(h, switch):
-    """the other device forms of the same arithmetic, one switch off at a time.  The staged forward stages (FV3LM_TP_FUSED=0) hold no
-    trajectory pass: the library refuses a split scheme under them, which is kept on record here, and test_staged_forward_unsplit runs them"""
-    if switch == "FV3LM_TP_FUSED":
-        from fv3_jedi_linearmodel_amd._lib import Fv3LmError
-        with pytest.raises(Fv3LmError, match="need the fused fv_tp_2d"):
-            F.check_transport("hip", 12, 3, h, env={switch: "0"})
-        return
-    F.check_transport("hip", 12, 3, h, env={switch: "0"})
+    """the other device form of the same arithmetic.  The staged stages (FV3LM_TP_FUSED=0) hold no trajectory pass: the library refuses a
+    split scheme under them, which is kept on record here, and test_staged_forward_unsplit runs them"""
+    from fv3_jedi_linearmodel_amd._lib import Fv3LmError
+    with pytest.raises(Fv3LmError, match="need the fused fv_tp_2d"):
+        F.check_transport("hip", 12, 3, h, env={switch: "0"})
 
 
 @pytest.mark.parametrize("h", [1, 2, 333])

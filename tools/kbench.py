@@ -25,7 +25,6 @@ def main():
     ap.add_argument("--d-ext", type=float, default=0.0, help="external-mode divergence damping coefficient (0: the setter is never called)")
     ap.add_argument("--group", default="", help="after one ordinary step: time this kernel group alone (TL and NL), e.g. d_sw")
     ap.add_argument("--ad", action="store_true", help="group mode: time the adjoint of the group instead of TL + NL")
-    ap.add_argument("--experiment", default="", help="comma list of FV3LM_TP2_EXPERIMENT values to time the group with (experiment builds only)")
     args = ap.parse_args()
     if args.lib:
         os.environ["FV3LM_LIB"] = os.path.abspath(args.lib)
@@ -49,21 +48,19 @@ def main():
         c.dy.state_restore(); c.dy.step_tl(); c.dy.state_restore(); c.dy.step_nl(); c.dy.step_ad()
     step(); c.dy.sync()
     if args.group:
-        for ex_ in [e for e in (args.experiment.split(",") if args.experiment else ["0"])]:
-            os.environ["FV3LM_TP2_EXPERIMENT"] = ex_
-            modes = (2,) if args.ad else (1, 0)
+        modes = (2,) if args.ad else (1, 0)
+        for m_ in modes:
+            c.dy.run_group(args.group, m_)
+        c.dy.sync()
+        c.dy.profile_begin()
+        for _ in range(3):
             for m_ in modes:
                 c.dy.run_group(args.group, m_)
-            c.dy.sync()
-            c.dy.profile_begin()
-            for _ in range(3):
-                for m_ in modes:
-                    c.dy.run_group(args.group, m_)
-            prof = c.dy.profile_end()
-            print("group %s, experiment %s:" % (args.group, ex_))
-            for k, (n_, m_, b_) in sorted(prof.items(), key=lambda kv: -kv[1][1]):
-                if not args.grep or any(g in k for g in args.grep.split(",")):
-                    print("  %-22s %5d %10.3f ms %8.4f ms/launch %9.1f GB/s" % (k, n_, m_, m_ / n_, (b_ / 1e9) / (m_ * 1e-3) if m_ > 0 else 0))
+        prof = c.dy.profile_end()
+        print("group %s:" % args.group)
+        for k, (n_, m_, b_) in sorted(prof.items(), key=lambda kv: -kv[1][1]):
+            if not args.grep or any(g in k for g in args.grep.split(",")):
+                print("  %-22s %5d %10.3f ms %8.4f ms/launch %9.1f GB/s" % (k, n_, m_, m_ / n_, (b_ / 1e9) / (m_ * 1e-3) if m_ > 0 else 0))
         return
     t0 = time.perf_counter(); step(); step(); c.dy.sync(); dt = (time.perf_counter() - t0) / 2
     c.dy.profile_begin(); step(); prof = c.dy.profile_end()

@@ -14,7 +14,7 @@ import sys
 
 
 # block descriptor of a k_tiled<...> kernel -> profile name (csrc/a2b.h, d2a2c.h, tpfused.h, tp2.h, tpad.h)
-TILED = {"TpFusedBlk": "TpFused", "Tp2Blk": "TpFused", "TpAdBlk": "TpAd", "TpOuterAdBlk": "TpOuter",
+TILED = {"Tp2Blk": "TpFused", "TpTrajBlk": "TpFusedTraj", "TpAdBlk": "TpAd",
          "A2bFwd": "A2b", "A2bAd": "A2b", "D2a2cFwd": "D2a2c", "D2a2cAd": "D2a2c"}
 
 
@@ -35,6 +35,8 @@ def short(name):
     m = re.search(r"k_tiled<fv3::([A-Za-z0-9]+)<(fv3::Dual|double)?", name)
     if m:       # the hand-written LDS-tiled launches (tiled.h), named by their block descriptor; Dual = tangent, double = nonlinear, none = adjoint
         mode = "ad" if m.group(2) is None else "tl" if "Dual" in m.group(2) else "nl"
+        if m.group(1) == "TpTrajBlk":      # the values-only trajectory pass of split levels (tpfused.h): no type argument
+            mode = "nl"
         return "%s.%s" % (TILED[m.group(1)], mode)
     # kernel symbols of builds before tiled.h (the committed profiles): one kernel per launch
     m = re.search(r"k_tp_(fused|march)<(fv3::Dual|double)", name)
@@ -61,7 +63,7 @@ def short(name):
         return "TpAd.ad_corner"
     if "k_tp_ad" in name:          # the whole adjoint of fv_tp_2d as one launch (tpad.h)
         return "TpAd.ad"
-    if "k_tp_outer_ad" in name:    # hand-written adjoint of the outer sweeps + flux assembly of fv_tp_2d (tpfused.h)
+    if "k_tp_outer_ad" in name:    # round 2's half-fused adjoint of fv_tp_2d (removed: old profiles only)
         return "TpOuter.ad"
     m = re.search(r"k_points<fv3::([A-Za-z0-9_]+(?:<[^>]*>)?)", name)
     if m:
