@@ -35,69 +35,129 @@ constexpr double R3 = 1. / 3., R23 = 2. / 3.;
 // ---------------------------------------------------------------- forward column map
 // cs_profile (|kord|>16, iv != -2; fv_mapz_tlm.F90:8592-8666) + map1_ppm/map_scalar/map1_q2 loop
 // (:7980-8045).  pe1, q1, pe2: functors k -> T (1-based); out(k, value).  Workspace slots used
-// (in units of T): SG = gam, SE = edge values qe.
-template <class T, class FP1, class FQ1, class FP2, class FOut>
-HD void map_col(int km, const FP1& pe1, const FQ1& q1, const FP2& pe2, const FOut& out, const ColWs& ws, int SG, int SE) {
+// (in units of T): SG = gam, SE = edge values qe, SA = the layer means.
+// Every source level is loaded once per sweep: the elimination carries pe1(k+1) and the layer means to the next level, the mapping
+// loop keeps the one open source layer in registers (SrcWindow) and only ever moves down.
+
+// The layer mean of level k for the elimination sweep.  The sweep asks for k = 1, 2, .., km, once each and in that order, and hands over
+// the two interfaces it holds: a functor q1(k, pe1(k), pe1(k+1)) builds on them and may carry state from call to call (the T map: T_v
+// from pt, pk and the log p it is mapped in, pk of the lower interface kept for the next level).  A plain q1(k) is taken as it is.
+template <class T, class FQ1>
+HD T layer_mean(const FQ1& q1, int k, const T& p_k, const T& p_k1) {
+  if constexpr (std::is_invocable_v<const FQ1&, int, const T&, const T&>) return q1(k, p_k, p_k1);
+  else return q1(k);
+}
+// edge values by the tridiagonal solve -> SE (gam -> SG); sa(k, a1(k)) receives the layer means on the way
+template <class T, class FP1, class FQ1, class FSA>
+HD void edge_solve(int km, const FP1& pe1, const FQ1& q1, const FSA& sa, const ColWs& ws, int SG, int SE) {
   typedef WsIO<T> W;
-  // edge values by the tridiagonal solve
-  T dpa = pe1(2) - pe1(1), dpb = pe1(3) - pe1(2);
+  const T p_1 = pe1(1);
+  T p_k = pe1(2), p_k1 = pe1(3);
+  T dpa = p_k - p_1, dpb = p_k1 - p_k;
   T grat = dpb / dpa;
   T bet = grat * (grat + 0.5);
-  T qf = ((grat + grat) * (grat + 1.) * q1(1) + q1(2)) / bet;
+  T a_pp = layer_mean<T>(q1, 1, p_1, p_k), ak_ = layer_mean<T>(q1, 2, p_k, p_k1);      // a_pp: the mean two levels up
+  sa(1, a_pp); sa(2, ak_);
+  T qf = ((grat + grat) * (grat + 1.) * a_pp + ak_) / bet;
   T gam = (1. + grat * (grat + 1.5)) / bet;
   W::set(ws, SE, 1, qf); W::set(ws, SG, 1, gam);
-  T d4 = grat, a_prev = q1(1), dp_prev = dpa;
+  T d4 = grat, a_prev = a_pp, dp_prev = dpa;
+#pragma unroll 1      // RemapWindFn<MODE_TL>: 80 VGPRs and the parent's 6 waves per SIMD with it, 82 and 5 without (metadata table)
   for (int k = 2; k <= km; ++k) {
-    T dpk = pe1(k + 1) - pe1(k);
-    T ak_ = q1(k);
+    if (k > 2) { p_k = p_k1; p_k1 = pe1(k + 1); ak_ = layer_mean<T>(q1, k, p_k, p_k1); sa(k, ak_); }
+    T dpk = p_k1 - p_k;
     d4 = dp_prev / dpk;
     bet = 2. + d4 + d4 - gam;
     qf = (3. * (a_prev + d4 * ak_) - qf) / bet;
     gam = d4 / bet;
     W::set(ws, SE, k, qf); W::set(ws, SG, k, gam);
-    a_prev = ak_; dp_prev = dpk;
+    a_pp = a_prev; a_prev = ak_; dp_prev = dpk;
   }
   T a_bot = 1. + d4 * (d4 + 1.5);
-  T qe = (2. * d4 * (d4 + 1.) * q1(km) + q1(km - 1) - a_bot * qf) / (d4 * (d4 + 0.5) - a_bot * gam);
+  T qe = (2. * d4 * (d4 + 1.) * a_prev + a_pp - a_bot * qf) / (d4 * (d4 + 0.5) - a_bot * gam);
   W::set(ws, SE, km + 1, qe);
+#pragma unroll 1
   for (int k = km; k >= 1; --k) {
     qe = W::get(ws, SE, k) - W::get(ws, SG, k) * qe;
     W::set(ws, SE, k, qe);
   }
-  // conservative mapping
+}
+// The open source layer l of the mapping loop as named scalars: its interfaces, its mean and the edge values at them.  advance() is
+// the one place the loop loads a source level: pe1(l+2), a1(l+1), qe(l+2).
+template <class T, class FP1, class FA1, class FE>
+struct SrcWindow {
+  const FP1& pe1; const FA1& a1; const FE& qe;
+  int l; T p_l, p_r, a_l, e_l, e_r;
+  HD void load(int k) { l = k; p_l = pe1(k); p_r = pe1(k + 1); a_l = a1(k); e_l = qe(k); e_r = qe(k + 1); }
+  HD void advance() { ++l; p_l = p_r; e_l = e_r; p_r = pe1(l + 1); a_l = a1(l); e_r = qe(l + 1); }
+};
+// conservative mapping: the loop of map1_ppm / map_scalar / map1_q2.  prof(w, a2, a3, a4): the parabola of the window's layer.
+// The search, the sum over the source layers wholly inside a target and the layer a target ends in all stream through the window; when
+// a target is done the window sits on the layer the next search starts from (k0).  Not found, or no source layer holds the target's
+// lower interface: k0 stays, the last qsum is written (as the reference does; never for ordered pressures) and the window goes back to k0.
+template <class T, class FP1, class FA1, class FE, class FP2, class FProf, class FOut>
+HD void map_loop(int km, const FP1& pe1, const FA1& a1, const FE& qe, const FP2& pe2, const FProf& prof, const FOut& out) {
+  SrcWindow<T, FP1, FA1, FE> w{pe1, a1, qe};
+  w.load(1);
   int k0 = 1;
   T qsum = T(0.);
   for (int k = 1; k <= km; ++k) {
     const T p2t = pe2(k), p2b = pe2(k + 1);
-    int l; bool found = false;
-    for (l = k0; l <= km; ++l)
-      if (val(p2t) >= val(pe1(l)) && val(p2t) <= val(pe1(l + 1))) { found = true; break; }
+    bool found = false;
+    for (;;) {
+      if (val(p2t) >= val(w.p_l) && val(p2t) <= val(w.p_r)) { found = true; break; }
+      if (w.l == km) break;
+      w.advance();
+    }
     if (found) {
-      const T p1l = pe1(l), p1r = pe1(l + 1), dpl = p1r - p1l;
-      const T a1 = q1(l), a2 = W::get(ws, SE, l), a3 = W::get(ws, SE, l + 1), a4 = 3. * (2. * a1 - (a2 + a3));
+      const T p1l = w.p_l, p1r = w.p_r, dpl = p1r - p1l;
+      T a2, a3, a4; prof(w, a2, a3, a4);
       const T pl = (p2t - p1l) / dpl;
       if (val(p2b) <= val(p1r)) {
         const T pr = (p2b - p1l) / dpl;
         out(k, a2 + 0.5 * (a4 + a3 - a2) * (pr + pl) - a4 * R3 * (pr * (pr + pl) + pl * pl));
-        k0 = l;
+        k0 = w.l;
         continue;
       }
       qsum = (p1r - p2t) * (a2 + 0.5 * (a4 + a3 - a2) * (1. + pl) - a4 * (R3 * (1. + pl * (1. + pl))));
-      int m; bool bottom = false;
-      for (m = l + 1; m <= km; ++m) {
-        if (val(p2b) > val(pe1(m + 1))) qsum = qsum + (pe1(m + 1) - pe1(m)) * q1(m);
+      bool bottom = false;
+      while (w.l < km) {
+        w.advance();
+        if (val(p2b) > val(w.p_r)) qsum = qsum + (w.p_r - w.p_l) * w.a_l;
         else { bottom = true; break; }
       }
       if (bottom) {
-        const T p1m = pe1(m), dpm = pe1(m + 1) - p1m;
-        const T b1 = q1(m), b2 = W::get(ws, SE, m), b3 = W::get(ws, SE, m + 1), b4 = 3. * (2. * b1 - (b2 + b3));
+        const T p1m = w.p_l, dpm = w.p_r - p1m;
+        T b2, b3, b4; prof(w, b2, b3, b4);
         const T dp = p2b - p1m, esl = dp / dpm;
         qsum = qsum + dp * (b2 + 0.5 * esl * (b3 - b2 + b4 * (1. - R23 * esl)));
-        k0 = m;
+        k0 = w.l;
       }
     }
+    if (w.l != k0) w.load(k0);
     out(k, qsum / (p2b - p2t));
   }
+}
+// sa(k, x) takes the layer means from the elimination, a1(k) gives them to the mapping loop
+template <class T, class FP1, class FQ1, class FP2, class FOut, class FSA, class FA1>
+HD void map_col_a(int km, const FP1& pe1, const FQ1& q1, const FP2& pe2, const FOut& out, const ColWs& ws, int SG, int SE, const FSA& sa, const FA1& a1) {
+  typedef WsIO<T> W;
+  edge_solve<T>(km, pe1, q1, sa, ws, SG, SE);
+  map_loop<T>(km, pe1, a1, [&](int k) { return W::get(ws, SE, k); }, pe2,
+              [](const auto& w, T& a2, T& a3, T& a4) { const T a1_ = w.a_l; a2 = w.e_l; a3 = w.e_r; a4 = 3. * (2. * a1_ - (a2 + a3)); }, out);
+}
+// The layer means go through slot SA, so q1 is not read after the elimination sweep: out may store over what q1 reads (the field is
+// remapped in place), and a q1 that costs several loads (T_v) is evaluated once per level.
+template <class T, class FP1, class FQ1, class FP2, class FOut>
+HD void map_col(int km, const FP1& pe1, const FQ1& q1, const FP2& pe2, const FOut& out, const ColWs& ws, int SG, int SE, int SA) {
+  typedef WsIO<T> W;
+  map_col_a<T>(km, pe1, q1, pe2, out, ws, SG, SE, [&](int k, const T& x) { W::set(ws, SA, k, x); }, [&](int k) { return W::get(ws, SA, k); });
+}
+// Without the slot: the mapping loop reads q1(k) a second time, and out must not store to what q1 reads.
+template <class T, class FP1, class FQ1, class FP2, class FOut>
+HD void map_col(int km, const FP1& pe1, const FQ1& q1, const FP2& pe2, const FOut& out, const ColWs& ws, int SG, int SE) {
+  static_assert(std::is_invocable_v<const FQ1&, int>, "without the slot SA the mapping loop calls q1(k) at any k: a plain functor, not the elimination's q1(k, pe1(k), pe1(k+1))");
+  map_col_a<T>(km, pe1, q1, pe2, out, ws, SG, SE, [](int, const T&) {}, q1);
 }
 
 // ---------------------------------------------------------------- limited profiles of the nonlinear remap (split_kord)
@@ -204,70 +264,26 @@ HD void lim_layer(const LimProfile& P, int k, int km, const FA& a1, const FE& qe
   }
   if (iv == 0) cs_limiters(ex, a, a2, a3, a4, 0);
 }
-// the mapping loop of map_scalar / map1_ppm / map1_q2 (fv_mapz_tlm.F90:2832-3239) on the limited profile: qe(k) = the unlimited edge values
+// the mapping loop of map_scalar / map1_ppm / map1_q2 (fv_mapz_tlm.F90:2832-3239) on the limited profile: qe(k) = the unlimited edge values.
+// pe1 and q1 stream through the window of map_loop; lim_layer reads its neighbourhood (a1 of k-2 .. k+2, qe of k, k+1) by itself.
 template <class FP1, class FQ1, class FP2, class FE, class FOut>
 HD void map_loop_lim(const LimProfile& P, int km, const FP1& pe1, const FQ1& q1, const FP2& pe2, const FE& qe, const FOut& out) {
-  int k0 = 1;
-  double qsum = 0.;
-  for (int k = 1; k <= km; ++k) {
-    const double p2t = pe2(k), p2b = pe2(k + 1);
-    int l; bool found = false;
-    for (l = k0; l <= km; ++l)
-      if (p2t >= pe1(l) && p2t <= pe1(l + 1)) { found = true; break; }
-    if (found) {
-      const double p1l = pe1(l), p1r = pe1(l + 1), dpl = p1r - p1l;
-      double a2, a3, a4; lim_layer(P, l, km, q1, qe, a2, a3, a4);
-      const double pl = (p2t - p1l) / dpl;
-      if (p2b <= p1r) {
-        const double pr = (p2b - p1l) / dpl;
-        out(k, a2 + 0.5 * (a4 + a3 - a2) * (pr + pl) - a4 * R3 * (pr * (pr + pl) + pl * pl));
-        k0 = l;
-        continue;
-      }
-      qsum = (p1r - p2t) * (a2 + 0.5 * (a4 + a3 - a2) * (1. + pl) - a4 * (R3 * (1. + pl * (1. + pl))));
-      int m; bool bottom = false;
-      for (m = l + 1; m <= km; ++m) {
-        if (p2b > pe1(m + 1)) qsum = qsum + (pe1(m + 1) - pe1(m)) * q1(m);
-        else { bottom = true; break; }
-      }
-      if (bottom) {
-        const double p1m = pe1(m), dpm = pe1(m + 1) - p1m;
-        double b2, b3, b4; lim_layer(P, m, km, q1, qe, b2, b3, b4);
-        const double dp = p2b - p1m, esl = dp / dpm;
-        qsum = qsum + dp * (b2 + 0.5 * esl * (b3 - b2 + b4 * (1. - R23 * esl)));
-        k0 = m;
-      }
-    }
-    out(k, qsum / (p2b - p2t));
-  }
+  map_loop<double>(km, pe1, q1, [](int) { return 0.; }, pe2,
+                   [&](const auto& w, double& a2, double& a3, double& a4) { lim_layer(P, w.l, km, q1, qe, a2, a3, a4); }, out);
 }
 
 // map_col on double with the limited profile: the same tridiagonal solve (edge values into slot SE), then the mapping loop with
-// lim_layer's (a2, a3, a4).  Slots SG, SE in units of double.
+// lim_layer's (a2, a3, a4).  Slots SG, SE, SA in units of double; with and without SA as map_col.
+template <class FP1, class FQ1, class FP2, class FOut>
+HD void map_col_lim(const LimProfile& P, int km, const FP1& pe1, const FQ1& q1, const FP2& pe2, const FOut& out, const ColWs& ws, int SG, int SE, int SA) {
+  edge_solve<double>(km, pe1, q1, [&](int k, double x) { ws.at(SA, k) = x; }, ws, SG, SE);
+  map_loop_lim(P, km, pe1, [&](int k) { return ws.at(SA, k); }, pe2, [&](int k) { return ws.at(SE, k); }, out);
+}
 template <class FP1, class FQ1, class FP2, class FOut>
 HD void map_col_lim(const LimProfile& P, int km, const FP1& pe1, const FQ1& q1, const FP2& pe2, const FOut& out, const ColWs& ws, int SG, int SE) {
-  {
-    double dpa = pe1(2) - pe1(1), dpb = pe1(3) - pe1(2);
-    double grat = dpb / dpa, bet = grat * (grat + 0.5);
-    double qf = ((grat + grat) * (grat + 1.) * q1(1) + q1(2)) / bet, gam = (1. + grat * (grat + 1.5)) / bet;
-    ws.at(SE, 1) = qf; ws.at(SG, 1) = gam;
-    double d4 = grat, a_prev = q1(1), dp_prev = dpa;
-    for (int k = 2; k <= km; ++k) {
-      const double dpk = pe1(k + 1) - pe1(k), ak_ = q1(k);
-      d4 = dp_prev / dpk;
-      bet = 2. + d4 + d4 - gam;
-      qf = (3. * (a_prev + d4 * ak_) - qf) / bet;
-      gam = d4 / bet;
-      ws.at(SE, k) = qf; ws.at(SG, k) = gam;
-      a_prev = ak_; dp_prev = dpk;
-    }
-    const double a_bot = 1. + d4 * (d4 + 1.5);
-    double qe = (2. * d4 * (d4 + 1.) * q1(km) + q1(km - 1) - a_bot * qf) / (d4 * (d4 + 0.5) - a_bot * gam);
-    ws.at(SE, km + 1) = qe;
-    for (int k = km; k >= 1; --k) { qe = ws.at(SE, k) - ws.at(SG, k) * qe; ws.at(SE, k) = qe; }
-  }
-  auto qe = [&](int k) { return ws.at(SE, k); };
-  map_loop_lim(P, km, pe1, q1, pe2, qe, out);
+  static_assert(std::is_invocable_v<const FQ1&, int>, "without the slot SA the mapping loop and lim_layer call q1(k) at any k: a plain functor");
+  edge_solve<double>(km, pe1, q1, [](int, double) {}, ws, SG, SE);
+  map_loop_lim(P, km, pe1, q1, pe2, [&](int k) { return ws.at(SE, k); }, out);
 }
 HD bool kord_limited(int kord) { return (kord < 0 ? -kord : kord) <= 16; }
 
@@ -413,27 +429,33 @@ HD void map_col_ad_iv(int km, const FP1& pe1, const FQ1& q1, const FP2& pe2, con
 //                  through q1out / p1out, once per level.
 // SQ / SP may be the very vectors q1out / p1out store to.
 struct MapAdWs { int SG, SF, SE, SFA, SGA, SQ, SP; };
+// Each sweep loads pe1(k) and q1(k) once per level: A and D carry the neighbouring levels in registers, C holds the open level b as a
+// window (pe1(b), pe1(b+1), q1(b), SE(b), SE(b+1), SG(b)) that the search, the found branch, the sum over the layers inside a target and
+// the closing of a level all use; closing a level is what moves it.
 template <class FP1, class FQ1, class FP2, class FAd, class OQ1, class OP1, class OP2>
 HD void map_col_ad_s(int km, const FP1& pe1, const FQ1& q1, const FP2& pe2, const FAd& q2_ad, const ColWs& ws, const MapAdWs& S,
                      const OQ1& q1out, const OP1& p1out, const OP2& p2out) {
-  const double dp1_1 = pe1(2) - pe1(1), dp1_2 = pe1(3) - pe1(2);
+  const double p_1 = pe1(1), p_2 = pe1(2), p_3 = pe1(3);
+  const double dp1_1 = p_2 - p_1, dp1_2 = p_3 - p_2;
   const double grat = dp1_2 / dp1_1, bet1 = grat * (grat + 0.5);
   double qbot;
   {   // ---- A
-    double qf = ((grat + grat) * (grat + 1.) * q1(1) + q1(2)) / bet1, gam = (1. + grat * (grat + 1.5)) / bet1;
+    double a_pp = q1(1), ak_ = q1(2);      // a_pp: the mean two levels up
+    double qf = ((grat + grat) * (grat + 1.) * a_pp + ak_) / bet1, gam = (1. + grat * (grat + 1.5)) / bet1;
     ws.at(S.SF, 1) = qf; ws.at(S.SG, 1) = gam;
-    double d4 = grat, a_prev = q1(1), dp_prev = dp1_1;
+    double d4 = grat, a_prev = a_pp, dp_prev = dp1_1, p_k = p_2, p_k1 = p_3;
     for (int k = 2; k <= km; ++k) {
-      const double dpk = pe1(k + 1) - pe1(k), ak_ = q1(k);
+      if (k > 2) { p_k = p_k1; p_k1 = pe1(k + 1); ak_ = q1(k); }
+      const double dpk = p_k1 - p_k;
       d4 = dp_prev / dpk;
       const double bet = 2. + d4 + d4 - gam;
       qf = (3. * (a_prev + d4 * ak_) - qf) / bet;
       gam = d4 / bet;
       ws.at(S.SF, k) = qf; ws.at(S.SG, k) = gam;
-      a_prev = ak_; dp_prev = dpk;
+      a_pp = a_prev; a_prev = ak_; dp_prev = dpk;
     }
     const double a_bot = 1. + d4 * (d4 + 1.5), den = d4 * (d4 + 0.5) - a_bot * gam;
-    qbot = (2. * d4 * (d4 + 1.) * q1(km) + q1(km - 1) - a_bot * qf) / den;
+    qbot = (2. * d4 * (d4 + 1.) * a_prev + a_pp - a_bot * qf) / den;
   }
   {   // ---- B
     double qe = qbot;
@@ -443,19 +465,19 @@ HD void map_col_ad_s(int km, const FP1& pe1, const FQ1& q1, const FP2& pe2, cons
   double fa_bot;
   {   // ---- C
     int b = 1;                                          // the open source level
+    double wp = p_1, wpn = p_2, wq = q1(1), we = ws.at(S.SE, 1), wen = ws.at(S.SE, 2), wg = ws.at(S.SG, 1);   // its window (b <= km)
     double aQ = 0., aD = 0., aP = 0., aPn = 0., aE = 0., aEn = 0.;   // q1_ad(b), dp1_ad(b), pe1_ad(b), pe1_ad(b+1), qe_ad(b), qe_ad(b+1)
     double ecarry = 0., dprev = 0.;                     // back-substitution carry into qe_ad(b); dp1_ad(b-1)
-    // close levels b .. nb-1; the levels strictly between lo and hi lie wholly inside the current target (weight qsa)
-    auto close_to = [&](int nb, int lo, int hi, double qsa) {
-      while (b < nb) {
-        const double e = aE + ecarry;
-        ws.at(S.SFA, b) = e; ws.at(S.SGA, b) = -ws.at(S.SE, b + 1) * e; ecarry = -ws.at(S.SG, b) * e;
-        ws.at(S.SQ, b) = aQ; ws.at(S.SP, b) = aP - aD + dprev; dprev = aD;
-        ++b;
-        const bool in = b > lo && b < hi;
-        aQ = in ? (pe1(b + 1) - pe1(b)) * qsa : 0.; aD = in ? q1(b) * qsa : 0.;
-        aP = aPn; aE = aEn; aPn = 0.; aEn = 0.;
-      }
+    // close level b and open b+1, with nothing accumulated on it yet
+    auto close = [&]() {
+      const double e = aE + ecarry;
+      ws.at(S.SFA, b) = e; ws.at(S.SGA, b) = -wen * e; ecarry = -wg * e;
+      ws.at(S.SQ, b) = aQ; ws.at(S.SP, b) = aP - aD + dprev; dprev = aD;
+      ++b;
+      aQ = 0.; aD = 0.;
+      aP = aPn; aE = aEn; aPn = 0.; aEn = 0.;
+      wp = wpn; we = wen;
+      if (b <= km) { wpn = pe1(b + 1); wq = q1(b); wen = ws.at(S.SE, b + 1); wg = ws.at(S.SG, b); }
     };
     auto addq = [&](double a2_ad, double a3_ad, double a4_ad) {   // a4 = 3 (2 a1 - a2 - a3) of the open level
       aQ += 6. * a4_ad; aE += a2_ad - 3. * a4_ad; aEn += a3_ad - 3. * a4_ad;
@@ -466,13 +488,19 @@ HD void map_col_ad_s(int km, const FP1& pe1, const FQ1& q1, const FP2& pe2, cons
       p2k = p2k1; p2k1 = 0.;
       const double g = q2_ad(k);
       const double p2t = pe2(k), p2b = pe2(k + 1);
-      int l; bool found = false;
-      for (l = b; l <= km; ++l)
-        if (p2t >= pe1(l) && p2t <= pe1(l + 1)) { found = true; break; }
+      int l = b; bool found = b <= km && p2t >= wp && p2t <= wpn;
+      if (!found) {      // look ahead without closing anything (ordered pressures find the open level: the targets start where the last one ended)
+        double pa = wpn;
+        for (l = b + 1; l <= km; ++l) {
+          const double pb = pe1(l + 1);
+          if (p2t >= pa && p2t <= pb) { found = true; break; }
+          pa = pb;
+        }
+      }
       if (!found) continue;   // (stale-qsum path of the reference: never taken for ordered pressures)
-      close_to(l, 0, 0, 0.);
-      const double p1l = pe1(l), p1r = pe1(l + 1), dpl = p1r - p1l;
-      const double a1 = q1(l), a2 = ws.at(S.SE, l), a3 = ws.at(S.SE, l + 1), a4 = 3. * (2. * a1 - (a2 + a3)), Sm = a4 + a3 - a2;
+      while (b < l) close();
+      const double p1l = wp, p1r = wpn, dpl = p1r - p1l;
+      const double a1 = wq, a2 = we, a3 = wen, a4 = 3. * (2. * a1 - (a2 + a3)), Sm = a4 + a3 - a2;
       const double pl = (p2t - p1l) / dpl;
       if (p2b <= p1r) {
         const double pr = (p2b - p1l) / dpl, s = pr + pl, w = pr * s + pl * pl;
@@ -485,28 +513,33 @@ HD void map_col_ad_s(int km, const FP1& pe1, const FQ1& q1, const FP2& pe2, cons
       const double D = p2b - p2t;
       const double E = a2 + 0.5 * Sm * (1. + pl) - a4 * (R3 * (1. + pl * (1. + pl)));
       double qsum = (p1r - p2t) * E;
-      int m; bool bottom = false;
-      for (m = l + 1; m <= km; ++m) {
-        if (p2b > pe1(m + 1)) qsum += (pe1(m + 1) - pe1(m)) * q1(m);
+      // what level l receives does not depend on qsum, so it is accumulated before the window leaves l; pe2_ad waits (below) to keep its order of summation
+      const double qs_ad = g / D;
+      const double W_ad = E * qs_ad, E_ad = (p1r - p2t) * qs_ad;
+      aPn += W_ad;
+      addq((1. - 0.5 * (1. + pl)) * E_ad, 0.5 * (1. + pl) * E_ad, (0.5 * (1. + pl) - R3 * (1. + pl * (1. + pl))) * E_ad);
+      const double pl_ad = (0.5 * Sm - a4 * R3 * (1. + 2. * pl)) * E_ad;
+      aP -= pl_ad / dpl; aD -= pl * pl_ad / dpl;
+      // the levels wholly inside the target (weight qs_ad), closed one by one as the window passes them
+      bool bottom = false;
+      while (b < km) {
+        close();
+        if (p2b > wpn) { qsum += (wpn - wp) * wq; aQ = (wpn - wp) * qs_ad; aD = wq * qs_ad; }
         else { bottom = true; break; }
       }
       double dp = 0., esl = 0., Fm = 0., b2 = 0., b3 = 0., b4 = 0., dpm = 1.;
       if (bottom) {
-        const double p1m = pe1(m); dpm = pe1(m + 1) - p1m;
-        const double b1 = q1(m); b2 = ws.at(S.SE, m); b3 = ws.at(S.SE, m + 1); b4 = 3. * (2. * b1 - (b2 + b3));
+        const double p1m = wp; dpm = wpn - p1m;
+        const double b1 = wq; b2 = we; b3 = wen; b4 = 3. * (2. * b1 - (b2 + b3));
         dp = p2b - p1m; esl = dp / dpm;
         Fm = b2 + 0.5 * esl * (b3 - b2 + b4 * (1. - R23 * esl));
         qsum += dp * Fm;
       }
-      const double q2v = qsum / D, qs_ad = g / D, D_ad = -q2v * g / D;
+      const double q2v = qsum / D, D_ad = -q2v * g / D;
       p2k1 += D_ad; p2k -= D_ad;
-      const double W_ad = E * qs_ad, E_ad = (p1r - p2t) * qs_ad;
-      aPn += W_ad; p2k -= W_ad;
-      addq((1. - 0.5 * (1. + pl)) * E_ad, 0.5 * (1. + pl) * E_ad, (0.5 * (1. + pl) - R3 * (1. + pl * (1. + pl))) * E_ad);
-      const double pl_ad = (0.5 * Sm - a4 * R3 * (1. + 2. * pl)) * E_ad;
-      p2k += pl_ad / dpl; aP -= pl_ad / dpl; aD -= pl * pl_ad / dpl;
+      p2k -= W_ad;
+      p2k += pl_ad / dpl;
       if (bottom) {
-        close_to(m, l, m, qs_ad);
         double dp_ad = Fm * qs_ad;
         const double F_ad = dp * qs_ad;
         addq((1. - 0.5 * esl) * F_ad, 0.5 * esl * F_ad, 0.5 * esl * (1. - R23 * esl) * F_ad);
@@ -514,23 +547,24 @@ HD void map_col_ad_s(int km, const FP1& pe1, const FQ1& q1, const FP2& pe2, cons
         dp_ad += esl_ad / dpm; aD -= esl * esl_ad / dpm;
         p2k1 += dp_ad; aP -= dp_ad;
       } else {
-        close_to(km + 1, l, km + 1, qs_ad);     // the target reaches below the last source layer: nothing further is found
+        close();     // the target reaches below the last source layer: level km is closed too, nothing further is found
       }
     }
     p2out(km, p2k); p2out(km + 1, p2k1);
-    close_to(km + 1, 0, 0, 0.);
+    while (b < km + 1) close();
     fa_bot = aE + ecarry;                   // adjoint of the bottom edge value
     ws.at(S.SP, km + 1) = aP + dprev;
   }
   {   // ---- D
-    double dpk = pe1(km + 1) - pe1(km), dpm1 = pe1(km) - pe1(km - 1);
+    double p_lo = pe1(km + 1), p_k = pe1(km), p_hi = pe1(km - 1), qk1 = q1(km);      // pe1(k+1), pe1(k), pe1(k-1), q1(k) of the level the sweep is on
+    double dpk = p_lo - p_k, dpm1 = p_k - p_hi;
     double d4 = dpm1 / dpk, gam_k = ws.at(S.SG, km);
     double sfa, sga, sda, qpk, qpkm1, dpend = 0., dnext = 0., q2hold = 0., d2loop = 0.;
     {
       const double d = d4, qfk = ws.at(S.SF, km);
       const double a_bot = 1. + d * (d + 1.5), den = d * (d + 0.5) - a_bot * gam_k;
       const double numb_ad = fa_bot / den, den_ad = -qbot * fa_bot / den;
-      double d_ad = 2. * (2. * d + 1.) * q1(km) * numb_ad + (2. * d + 0.5) * den_ad;
+      double d_ad = 2. * (2. * d + 1.) * qk1 * numb_ad + (2. * d + 0.5) * den_ad;
       qpk = 2. * d * (d + 1.) * numb_ad; qpkm1 = numb_ad;
       const double abot_ad = -qfk * numb_ad - gam_k * den_ad;
       sfa = ws.at(S.SFA, km) - a_bot * numb_ad;
@@ -548,7 +582,7 @@ HD void map_col_ad_s(int km, const FP1& pe1, const FQ1& q1, const FP2& pe2, cons
       const double qk = ws.at(S.SQ, k) + qpk + 3. * d4 * t;
       if (k > 2) q1out(k, qk); else q2hold = qk;
       qpk = qpkm1 + 3. * t; qpkm1 = 0.;
-      d4_ad += 3. * q1(k) * t;
+      d4_ad += 3. * qk1 * t;
       bet_ad -= qf * t;
       d4_ad += 2. * bet_ad;
       sfa = ws.at(S.SFA, k - 1) - t;
@@ -558,7 +592,8 @@ HD void map_col_ad_s(int km, const FP1& pe1, const FQ1& q1, const FP2& pe2, cons
       dpend = d4_ad / dpk;
       if (k > 2) { p1out(k + 1, ws.at(S.SP, k + 1) + dk - dnext); dnext = dk; } else d2loop = dk;
       dpk = dpm1;
-      if (k > 2) { dpm1 = pe1(k - 1) - pe1(k - 2); d4 = dpm1 / dpk; }
+      qk1 = q1(k - 1);
+      if (k > 2) { const double p_up = pe1(k - 2); dpm1 = p_hi - p_up; p_hi = p_up; d4 = dpm1 / dpk; }
     }
     {
       const double gam1 = gam_k, qf1 = ws.at(S.SF, 1);
@@ -566,7 +601,7 @@ HD void map_col_ad_s(int km, const FP1& pe1, const FQ1& q1, const FP2& pe2, cons
       double bet_ad = -gam1 * sga / bet1;
       const double t = sfa / bet1;
       bet_ad -= qf1 * t;
-      grat_ad += 2. * (2. * grat + 1.) * q1(1) * t;
+      grat_ad += 2. * (2. * grat + 1.) * qk1 * t;
       q1out(2, q2hold + t);
       q1out(1, ws.at(S.SQ, 1) + qpk + 2. * grat * (grat + 1.) * t);
       grat_ad += (2. * grat + 0.5) * bet_ad;
@@ -601,44 +636,67 @@ HD size_t fidx(const Geom& g, const Fld& f, int tile, int i, int j, int k) { ret
 // scalars: T (log p), tracers, delp, pk, peln, pkz, final pt (fv_mapz_tlm.F90:1586-1835, :2203-2250).
 // Two launches: (1) one thread per (column, field) — field 0 maps T_v in log p, field n tracer n in p — each with its own
 // workspace slots; (2) one thread per column for the new pressures and the final temperature conversion.
+// The field is remapped in place: the elimination sweep leaves its layer means (for T the computed T_v) in slot SA, nothing reads the
+// field after that sweep, and the mapping loop stores straight into it.
 // LIM: the build of the kernels for a trajectory with limited profiles (split_kord); the default kernels carry none of that code
 template <class T, bool LIM = false>
 HD void remap_field_col(const RemapArgs& a, int field, int i, int j, int tile, size_t col) {
   const Geom& g = a.g; const int km = g.npz;
   const ColWs ws{a.ws + col, a.ws_stride, km + 2};
   typedef FIO<T> IO; typedef WsIO<T> W;
-  const int SG = 3 * field, SE = 3 * field + 1, SO = 3 * field + 2;      // in units of T (x2 slots for Dual)
+  const int SG = 3 * field, SE = 3 * field + 1, SA = 3 * field + 2;      // in units of T (x2 slots for Dual)
   auto pe1 = [&](int k) { return IO::ld(a.pe, fidx(g, a.pe, tile, i, j, k)); };
   auto pn1 = [&](int k) { return IO::ld(a.peln, fidx(g, a.peln, tile, i, j, k)); };
   auto pk1 = [&](int k) { return IO::ld(a.pk, fidx(g, a.pk, tile, i, j, k)); };
   const T ps = pe1(km + 1);
   auto pe2 = [&](int k) -> T { return k == 1 ? T(a.ptop) : (k == km + 1 ? ps : a.ak[k - 1] + a.bk[k - 1] * ps); };
-  auto outw = [&](int k, const T& x) { W::set(ws, SO, k, x); };
+  // With a limited trajectory profile the values come from map_col_lim, which runs second and reads the field again: the tangent map
+  // before it then stores the tangents only (st_tan) and leaves the values where they are.
+  auto st_tan = [&](const Fld& f, size_t n, const T& x) { if constexpr (W::W == 2) f.p[n] = x.d; };
   if (field == 0) {
     auto pn2 = [&](int k) -> T { return (k == 1 || k == km + 1) ? pn1(k) : dlog(pe2(k)); };
-    auto tv = [&](int k) -> T { return IO::ld(a.pt, fidx(g, a.pt, tile, i, j, k)) * (pk1(k + 1) - pk1(k)) / (a.akap * (pn1(k + 1) - pn1(k))); };
-    if (!(LIM && kord_limited(a.kord_tm) && W::W == 1)) map_col<T>(km, pn1, tv, pn2, outw, ws, SG, SE);
+    // T_v of the level the elimination sweep is on (layer_mean), from the log p it holds; pk of the lower interface stays for the next level
+    T pk_hi = pk1(1);
+    auto tv = [&](int k, const T& pn_k, const T& pn_k1) -> T {
+      const T pk_lo = pk1(k + 1);
+      const T t = IO::ld(a.pt, fidx(g, a.pt, tile, i, j, k)) * (pk_lo - pk_hi) / (a.akap * (pn_k1 - pn_k));
+      pk_hi = pk_lo;
+      return t;
+    };
+    const bool lim = LIM && kord_limited(a.kord_tm);
+    auto out = [&](int k, const T& x) {      // T_v on the new levels
+      if (lim) st_tan(a.pt, fidx(g, a.pt, tile, i, j, k), x); else IO::st(a.pt, fidx(g, a.pt, tile, i, j, k), x);
+    };
+    if (!(lim && W::W == 1)) map_col<T>(km, pn1, tv, pn2, out, ws, SG, SE, SA);
     if constexpr (LIM) if (kord_limited(a.kord_tm)) {      // the values by the trajectory's limited profile (map_scalar, iv = 1, t_min = 184: fv_mapz_tlm.F90:494-509)
       auto pn1d = [&](int k) { return a.peln.t[fidx(g, a.peln, tile, i, j, k)]; };
       auto pk1d = [&](int k) { return a.pk.t[fidx(g, a.pk, tile, i, j, k)]; };
       const double psd = a.pe.t[fidx(g, a.pe, tile, i, j, km + 1)];
       auto pn2d = [&](int k) -> double { return (k == 1 || k == km + 1) ? pn1d(k) : log(k == 1 ? a.ptop : a.ak[k - 1] + a.bk[k - 1] * psd); };
-      auto tvd = [&](int k) -> double { return a.pt.t[fidx(g, a.pt, tile, i, j, k)] * (pk1d(k + 1) - pk1d(k)) / (a.akap * (pn1d(k + 1) - pn1d(k))); };
-      map_col_lim(LimProfile{a.kord_tm, 1, true, 184.}, km, pn1d, tvd, pn2d, [&](int k, double x) { ws.at(W::W * SO, k) = x; }, ws, W::W * SG, W::W * SE);
+      auto outd = [&](int k, double x) { a.pt.t[fidx(g, a.pt, tile, i, j, k)] = x; };
+      double pkd_hi = pk1d(1);
+      auto tvd = [&](int k, const double& pn_k, const double& pn_k1) -> double {
+        const double pk_lo = pk1d(k + 1);
+        const double t = a.pt.t[fidx(g, a.pt, tile, i, j, k)] * (pk_lo - pkd_hi) / (a.akap * (pn_k1 - pn_k));
+        pkd_hi = pk_lo;
+        return t;
+      };
+      map_col_lim(LimProfile{a.kord_tm, 1, true, 184.}, km, pn1d, tvd, pn2d, outd, ws, W::W * SG, W::W * SE, W::W * SA);
     }
-    for (int k = 1; k <= km; ++k) IO::st(a.pt, fidx(g, a.pt, tile, i, j, k), W::get(ws, SO, k));   // T_v on the new levels
   } else {
     const Fld& qf = a.q[field - 1];
     auto q1 = [&](int k) { return IO::ld(qf, fidx(g, qf, tile, i, j, k)); };
-    if (!(LIM && kord_limited(a.kord_tr) && W::W == 1)) map_col<T>(km, pe1, q1, pe2, outw, ws, SG, SE);
+    const bool lim = LIM && kord_limited(a.kord_tr);
+    auto out = [&](int k, const T& x) { if (lim) st_tan(qf, fidx(g, qf, tile, i, j, k), x); else IO::st(qf, fidx(g, qf, tile, i, j, k), x); };
+    if (!(lim && W::W == 1)) map_col<T>(km, pe1, q1, pe2, out, ws, SG, SE, SA);
     if constexpr (LIM) if (kord_limited(a.kord_tr)) {      // map1_q2: scalar_profile, iv = 0, q_min = 0 (fv_mapz_tlm.F90:596-612)
       auto pe1d = [&](int k) { return a.pe.t[fidx(g, a.pe, tile, i, j, k)]; };
       const double psd = pe1d(km + 1);
       auto pe2d = [&](int k) -> double { return k == 1 ? a.ptop : (k == km + 1 ? psd : a.ak[k - 1] + a.bk[k - 1] * psd); };
       auto q1d = [&](int k) { return qf.t[fidx(g, qf, tile, i, j, k)]; };
-      map_col_lim(LimProfile{a.kord_tr, 0, true, 0.}, km, pe1d, q1d, pe2d, [&](int k, double x) { ws.at(W::W * SO, k) = x; }, ws, W::W * SG, W::W * SE);
+      auto outd = [&](int k, double x) { qf.t[fidx(g, qf, tile, i, j, k)] = x; };
+      map_col_lim(LimProfile{a.kord_tr, 0, true, 0.}, km, pe1d, q1d, pe2d, outd, ws, W::W * SG, W::W * SE, W::W * SA);
     }
-    for (int k = 1; k <= km; ++k) IO::st(qf, fidx(g, qf, tile, i, j, k), W::get(ws, SO, k));
   }
 }
 template <class T>
@@ -678,7 +736,7 @@ HD void remap_wind_col(const RemapArgs& a, int dir, int i, int j, int tile, size
   const Geom& g = a.g; const int km = g.npz;
   const ColWs ws{a.ws + col, a.ws_stride, km + 2};
   typedef FIO<T> IO; typedef WsIO<T> W;
-  const int SG = 0, SE = 1, SO = 2;
+  const int SG = 0, SE = 1, SA = 2;
   const int im = dir == 0 ? i : i - 1, jm = dir == 0 ? j - 1 : j;
   const Fld& wf = dir == 0 ? a.u : a.v;
   auto pe0 = [&](int k) -> T {
@@ -688,9 +746,16 @@ HD void remap_wind_col(const RemapArgs& a, int dir, int i, int j, int tile, size
   const T pss = IO::ld(a.pe, fidx(g, a.pe, tile, im, jm, km + 1)) + IO::ld(a.pe, fidx(g, a.pe, tile, i, j, km + 1));
   auto pe3 = [&](int k) -> T { return (dir == 1 && k == 1) ? T(a.ak[0]) : a.ak[k - 1] + (0.5 * a.bk[k - 1]) * pss; };
   auto q1 = [&](int k) { return IO::ld(wf, fidx(g, wf, tile, i, j, k)); };
-  auto outw = [&](int k, const T& x) { W::set(ws, SO, k, x); };
-  if (!(LIM && kord_limited(a.kord_mt) && W::W == 1)) map_col<T>(km, pe0, q1, pe3, outw, ws, SG, SE);
-  if constexpr (LIM) if (kord_limited(a.kord_mt)) {        // map1_ppm: cs_profile, iv = -1 (fv_mapz_tlm.F90:780-795, :817-830)
+  const bool lim = LIM && kord_limited(a.kord_mt);
+  auto out = [&](int k, const T& x) {      // in place: the layer means are in slot SA by then; before map_col_lim the tangents only (remap_field_col)
+    if constexpr (W::W == 2) if (lim) { wf.p[fidx(g, wf, tile, i, j, k)] = x.d; return; }
+    IO::st(wf, fidx(g, wf, tile, i, j, k), x);
+  };
+  // the values by the trajectory's limited profile, map1_ppm: cs_profile, iv = -1 (fv_mapz_tlm.F90:780-795, :817-830).  Values only
+  // (W = 1): this map alone, on a path of its own; with the tangent (W = 2) it follows the tangent map.  The early return is for the
+  // register allocation of RemapWindFn<MODE_TL, true>: 96 VGPRs with it, 98 (a wave per SIMD fewer than the parent) without.
+  auto wind_lim = [&]() {
+    if constexpr (!LIM) return;
     auto pe0d = [&](int k) -> double {
       if (k == 1) return a.pe.t[fidx(g, a.pe, tile, i, j, 1)];
       return 0.5 * (a.pe.t[fidx(g, a.pe, tile, im, jm, k)] + a.pe.t[fidx(g, a.pe, tile, i, j, k)]);
@@ -698,9 +763,18 @@ HD void remap_wind_col(const RemapArgs& a, int dir, int i, int j, int tile, size
     const double pssd = a.pe.t[fidx(g, a.pe, tile, im, jm, km + 1)] + a.pe.t[fidx(g, a.pe, tile, i, j, km + 1)];
     auto pe3d = [&](int k) -> double { return (dir == 1 && k == 1) ? a.ak[0] : a.ak[k - 1] + (0.5 * a.bk[k - 1]) * pssd; };
     auto q1d = [&](int k) { return wf.t[fidx(g, wf, tile, i, j, k)]; };
-    map_col_lim(LimProfile{a.kord_mt, -1, false, 0.}, km, pe0d, q1d, pe3d, [&](int k, double x) { ws.at(W::W * SO, k) = x; }, ws, W::W * SG, W::W * SE);
-  }
-  for (int k = 1; k <= km; ++k) IO::st(wf, fidx(g, wf, tile, i, j, k), W::get(ws, SO, k));
+    auto outd = [&](int k, double x) { wf.t[fidx(g, wf, tile, i, j, k)] = x; };
+    const LimProfile P{a.kord_mt, -1, false, 0.};
+    if constexpr (W::W == 1) {
+      // values only: the mapped wind goes through slot SA and a copy, lim_layer reads its neighbourhood from the field.  In place (the layer
+      // means through SA, as below) this kernel takes 86 VGPRs and 5 waves per SIMD; in this form 72 and the 7 it had.
+      map_col_lim(P, km, pe0d, q1d, pe3d, [&](int k, double x) { ws.at(SA, k) = x; }, ws, SG, SE);
+      for (int k = 1; k <= km; ++k) wf.t[fidx(g, wf, tile, i, j, k)] = ws.at(SA, k);
+    } else map_col_lim(P, km, pe0d, q1d, pe3d, outd, ws, W::W * SG, W::W * SE, W::W * SA);
+  };
+  if (lim && W::W == 1) { wind_lim(); return; }
+  map_col<T>(km, pe0, q1, pe3, out, ws, SG, SE, SA);
+  if (lim) wind_lim();
 }
 
 // adjoint of remap_wind_col: consumes wf.p (adjoint of the mapped wind), writes the adjoint of the
@@ -767,7 +841,11 @@ HD void remap_pe_gather_ad(const RemapArgs& a, int i, int j, int tile) {
 //   k3, per column:          sums the pressure adjoints of all maps, T_v -> pt, pk2 / pn2 chain, write-back
 // Workspace slots: 0..21 shared accumulators (as named below), 22 + 8 f .. for the map of field f: its pe1_ad, q1_ad (T map only),
 // pe2_ad outputs and the five work vectors of map_col_ad_s (whose SP / SQ streams share the output vectors).
-struct RemapAdSlots { static constexpr int SPE1 = 13, SPN1 = 14, SPK1 = 15, SPE2 = 16, SPN2 = 17, SPK2 = 18, ST2 = 19, SQ2 = 20, SV = 21, FBASE = 22, FN = 8; };
+// STV: T_v of the source levels, left by k1's forward T map (its slot of layer means) for the T map of k2, which reads it in place of
+// pt, pk and peln (five loads and a division per use).  0, 1: gam and the edge values of k1's maps.
+// remap_fields.ad 7.31 -> 7.10 ms per launch at C192 L127 (profiles/remap_window_cube_c192l127.txt).  The hand-over holds because run_remap
+// launches k1 before k2 on the same rectangle and nothing between them writes slot STV: k1's tracer map uses 0 and 1, the field maps 22 and up.
+struct RemapAdSlots { static constexpr int STV = 2, SPE1 = 13, SPN1 = 14, SPK1 = 15, SPE2 = 16, SPN2 = 17, SPK2 = 18, ST2 = 19, SQ2 = 20, SV = 21, FBASE = 22, FN = 8; };
 struct FieldAdSlots { int SP1, SQ1, SP2; MapAdWs w; };
 HD FieldAdSlots remap_field_slots(int f) { const int b = RemapAdSlots::FBASE + RemapAdSlots::FN * f; return FieldAdSlots{b, b + 1, b + 2, MapAdWs{b + 3, b + 4, b + 5, b + 6, b + 7, b + 1, b}}; }
 
@@ -784,15 +862,22 @@ HD void remap_ad_k1(const RemapArgs& a, int i, int j, int tile, size_t col) {
   auto pn2 = [&](int k) -> double { return (k == 1 || k == km + 1) ? pn1(k) : log(pe2(k)); };
   auto pk2 = [&](int k) -> double { return (k == 1 || k == km + 1) ? pk1(k) : exp(a.akap * pn2(k)); };
   auto ptin = [&](int k) { return a.pt.t[fidx(g, a.pt, tile, i, j, k)]; };
-  auto tv = [&](int k) -> double { return ptin(k) * (pk1(k + 1) - pk1(k)) / (a.akap * (pn1(k + 1) - pn1(k))); };
+  // T_v of the level the elimination sweep is on (layer_mean): pk of the lower interface stays for the next level
+  double pk_hi = pk1(1);
+  auto tv = [&](int k, const double& pn_k, const double& pn_k1) -> double {
+    const double pk_lo = pk1(k + 1);
+    const double t = ptin(k) * (pk_lo - pk_hi) / (a.akap * (pn_k1 - pn_k));
+    pk_hi = pk_lo;
+    return t;
+  };
   for (int k = 0; k <= km + 1; ++k)
     for (int s_ : {R_::SPE1, R_::SPN1, R_::SPK1, R_::SPE2, R_::SPN2, R_::SPK2}) ws.at(s_, k) = 0.;
   // trajectory of the remapped T_v and q_v (needed by the final conversion)
   {
     auto outT = [&](int k, double x) { ws.at(R_::ST2, k) = x; };
     bool done = false;
-    if constexpr (LIM) if (kord_limited(a.kord_tm)) { map_col_lim(LimProfile{a.kord_tm, 1, true, 184.}, km, pn1, tv, pn2, outT, ws, 0, 1); done = true; }
-    if (!done) map_col<double>(km, pn1, tv, pn2, outT, ws, 0, 1);
+    if constexpr (LIM) if (kord_limited(a.kord_tm)) { map_col_lim(LimProfile{a.kord_tm, 1, true, 184.}, km, pn1, tv, pn2, outT, ws, 0, 1, R_::STV); done = true; }
+    if (!done) map_col<double>(km, pn1, tv, pn2, outT, ws, 0, 1, R_::STV);
     if (a.nq > 0 && a.last_step) {
       auto q1 = [&](int k) { return a.q[0].t[fidx(g, a.q[0], tile, i, j, k)]; };
       auto outQ = [&](int k, double x) { ws.at(R_::SQ2, k) = x; };
@@ -841,9 +926,8 @@ HD void remap_ad_k2(const RemapArgs& a, int field, int i, int j, int tile, size_
   auto p2out = [&](int k, double x) { ws.at(S.SP2, k) = x; };
   if (field == 0) {   // T map (coordinates pn1 -> pn2)
     auto pn1 = [&](int k) { return a.peln.t[fidx(g, a.peln, tile, i, j, k)]; };
-    auto pk1 = [&](int k) { return a.pk.t[fidx(g, a.pk, tile, i, j, k)]; };
     auto pn2 = [&](int k) -> double { return (k == 1 || k == km + 1) ? pn1(k) : log(pe2(k)); };
-    auto tv = [&](int k) -> double { return a.pt.t[fidx(g, a.pt, tile, i, j, k)] * (pk1(k + 1) - pk1(k)) / (a.akap * (pn1(k + 1) - pn1(k))); };
+    auto tv = [&](int k) { return ws.at(RemapAdSlots::STV, k); };      // left by k1
     auto q2ad = [&](int k) { return ws.at(RemapAdSlots::SV, k); };
     map_col_ad_s(km, pn1, tv, pn2, q2ad, ws, S.w, [&](int k, double x) { ws.at(S.SQ1, k) = x; }, p1out, p2out);
   } else {            // tracer map (coordinates pe1 -> pe2)
